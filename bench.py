@@ -12,8 +12,11 @@ already resident in HBM.  value = events (waveform readouts) per second over all
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-At N = 1 the same JSON line also carries the exact-fp32 path of the same step ("f32_path": throughput and
-the logits/loss diff against the CPU oracle, the 1e-5 parity bar) and the CPU baseline.
+A plain run sets up, warms up, times exactly --steps steps (one region) and prints the JSON line.  With --full the
+timed region is repeated (--repeats, median reported) and, at N = 1, the same line also carries the exact-fp32 path of
+the same step ("f32_path": throughput and the logits/loss diff against the CPU oracle, the 1e-5 parity bar), the CPU
+baseline and the per-kernel roofline passes.  --dump-outputs DIR writes what the last timed step handed its caller
+(loss, updated parameters and BatchNorm statistics, gradients) as DIR/<name>.npy in float32.
 """
 import argparse
 import copy
@@ -68,9 +71,18 @@ def parse():
                     help="run the step eagerly instead of replaying it as one captured HIP graph")
     ap.add_argument("--batches", type=int, default=8,
                     help="distinct resident batches (different geometry each) the timed loop cycles through")
-    ap.add_argument("--repeats", type=int, default=5,
-                    help="the timed --steps region is run this many times; the line reports the median region")
-    return ap.parse_args()
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="the timed --steps region is run this many times; the line reports the median region "
+                         "(default: 5 with --full, else 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements beyond the headline: exact-fp32 path + parity vs the CPU oracle, CPU "
+                         "baseline, roofline passes, repeated timed regions")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (loss, parameters, buffers, gradients) as DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    return args
 
 
 def load_cfg(path, samples):
@@ -90,8 +102,38 @@ class Env(object):
     pass
 
 
-def measure(env, args, dtype, steps, warmup, roofline):
-    """Builds the module + batch for `dtype`, times `steps` steps, returns (json fields, extras)."""
+def step_outputs(module, reducer, loss):
+    """What the training step hands its caller: the loss, the updated parameters and BatchNorm running statistics, and
+    the step's gradients (their slots of the reducer's flat buffer) -- as host float32 arrays, by name."""
+    out = {"loss": loss.detach().reshape(1)}
+    trained = iter(range(len(reducer.params)))          # the reducer's slots follow the trainable parameters' order
+    for name, p in module.model.named_parameters():
+        out["param." + name] = p.detach()
+        if p.requires_grad:
+            o, n = reducer.slices[next(trained)]
+            out["grad." + name] = reducer.flat_grad[o:o + n].view_as(p)
+    for name, b in module.model.named_buffers():
+        if b.is_floating_point():
+            out["buffer." + name] = b
+    return {k: v.detach().float().cpu().numpy() for k, v in out.items()}
+
+
+def dump_outputs(outputs, path, limit=64 << 20):
+    """DIR/<name>.npy per output.  Past `limit` bytes in all, every array of more than 1 Mi elements is replaced by a
+    fixed seeded sample of its flattened elements (same indices from run to run)."""
+    os.makedirs(path, exist_ok=True)
+    if sum(a.nbytes for a in outputs.values()) > limit:
+        rng = np.random.default_rng(0)
+        outputs = {k: (a.reshape(-1)[np.sort(rng.choice(a.size, 1 << 20, replace=False))] if a.size > (1 << 20) else a)
+                   for k, a in sorted(outputs.items())}
+    for name, a in outputs.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    log("outputs of the last timed step: %d arrays -> %s" % (len(outputs), path))
+
+
+def measure(env, args, dtype, steps, warmup, roofline, parity_snapshot=True, outputs=False):
+    """Builds the module + batch for `dtype`, times `steps` steps, returns (json fields, extras).  `outputs`: extras
+    also holds the last timed step's outputs (step_outputs)."""
     from waveformml_amd import _lib
     from waveformml_amd.psd import synthetic
     from waveformml_amd.psd.config import DictionaryUtility
@@ -103,7 +145,8 @@ def measure(env, args, dtype, steps, warmup, roofline):
     module = LitPSD(DictionaryUtility.to_object(copy.deepcopy(env.cfg))).to(dev)
     module.train()
     broadcast_parameters(module)
-    init_state = {k: v.detach().cpu().clone() for k, v in module.state_dict().items()}
+    init_state = ({k: v.detach().cpu().clone() for k, v in module.state_dict().items()}     # the CPU leg's weights
+                  if parity_snapshot else None)
     # WFS_BENCH_ONE_RANK_RCCL=1 (a rehearsal, not a bench line): one rank with a real RCCL communicator and the whole
     # bucket / hook / in-graph all-reduce machinery of an N-rank step -- what that structure costs before any link does
     force = env.world == 1 and os.environ.get("WFS_BENCH_ONE_RANK_RCCL") == "1"
@@ -145,10 +188,12 @@ def measure(env, args, dtype, steps, warmup, roofline):
     # parity snapshot on the un-trained weights.  Train mode, so BatchNorm normalises with batch statistics over
     # the active voxels (in eval mode the fresh running stats leave the activations at ~1e-6 and the logits are just
     # the head's bias).
-    with torch.no_grad():
-        logits0 = module.model([coords.clone(), feats.clone()]).float()
-        loss0 = float(module.criterion(logits0, labels).item())
-        logits0 = logits0.cpu()
+    logits0, loss0 = None, None
+    if parity_snapshot:
+        with torch.no_grad():
+            logits0 = module.model([coords.clone(), feats.clone()]).float()
+            loss0 = float(module.criterion(logits0, labels).item())
+            logits0 = logits0.cpu()
     log("[%s] model + batch ready: %d voxels" % (dtype, coords.shape[0]))
 
     mode, gstep = "eager", None
@@ -182,6 +227,8 @@ def measure(env, args, dtype, steps, warmup, roofline):
         regions.append(float(t.item()))
     if gstep is not None:
         gstep.check()                       # raises if a captured capacity was exceeded
+    # taken before any pass below steps the module again
+    step_out = step_outputs(module, reducer, loss) if outputs else None
     elapsed = float(np.median(regions))
     per_step = [r / steps * 1e3 for r in regions]
     log("[%s] timed regions (%s): median %.3f ms/step (min %.3f, max %.3f over %d regions of %d steps, %d batches)"
@@ -269,7 +316,7 @@ def measure(env, args, dtype, steps, warmup, roofline):
                 rtf = by["flops"] / max(by["launches"], 1) / (rp_us * 1e-6) / 1e12
                 out["roofline"]["mfma"]["rocprof"] = {"achieved": rtf, "frac": rtf / F32_MFMA_PEAK_TFLOPS,
                                                       "avg_launch_us": rp_us}
-    extras = {"init_state": init_state, "batch_np": (c, f, y), "logits0": logits0, "loss0": loss0}
+    extras = {"init_state": init_state, "batch_np": (c, f, y), "logits0": logits0, "loss0": loss0, "outputs": step_out}
     # orderly end of this measurement: hooks off, device idle, the captured graph -- RCCL nodes included --
     # destroyed NOW, not by the garbage collector inside the next capture or after the process group is gone
     if gstep is not None:
@@ -561,11 +608,15 @@ def main():
         _ops.OVERLAP_DW = True
 
     single = env.world == 1
+    roofline = args.full and not args.no_roofline
     f32 = None
-    if single and args.dtype != "f32" and args.cpu_steps > 0:
+    if args.full and single and args.dtype != "f32" and args.cpu_steps > 0:
         # the exact-fp32 path of the same step first: it is what the 1e-5 parity bar applies to
-        f32, f32_extras = measure(env, args, "f32", min(args.steps, 30), args.warmup, not args.no_roofline)
-    main_out, extras = measure(env, args, args.dtype, args.steps, args.warmup, not args.no_roofline)
+        f32, f32_extras = measure(env, args, "f32", min(args.steps, 30), args.warmup, roofline)
+    main_out, extras = measure(env, args, args.dtype, args.steps, args.warmup, roofline, parity_snapshot=args.full,
+                               outputs=args.dump_outputs is not None and env.rank == 0)
+    if extras["outputs"] is not None:
+        dump_outputs(extras["outputs"], args.dump_outputs)
 
     if env.rank == 0:
         result = {
@@ -583,7 +634,7 @@ def main():
             result["roofline"] = main_out["roofline"]
             if single:
                 result["roofline_large_batch"] = large_batch_roofline(env, args.dtype)
-        if single and args.cpu_steps > 0:
+        if args.full and single and args.cpu_steps > 0:
             ref_extras = f32_extras if f32 is not None else extras
             cpu_logits, cpu_loss, base = cpu_reference(env, ref_extras, args.cpu_steps)
             result["cpu_baseline"] = base

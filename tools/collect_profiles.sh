@@ -8,7 +8,7 @@ mkdir -p $O
 cd $R
 timeout -k 10 700 python -m pytest tests -x -q -m gpu > $O/pytest_gpu.log 2>&1 || { tail -20 $O/pytest_gpu.log; exit 1; }
 tail -n 2 $O/pytest_gpu.log
-python bench.py > $O/bench_default.json 2> $O/bench_default.log || exit 1
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.log || exit 1
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --cpu-steps 0 --no-roofline --steps 100 > $O/stats.log 2>&1 || exit 1
 timeout -k 10 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -- python3 $R/bench.py --cpu-steps 0 --no-roofline --steps 20 > $O/pmc_fetch.log 2>&1 || exit 1

@@ -7,7 +7,7 @@ python tools/microbench_generic.py 256 bf16 wide > $O/microbench_wide_bf16.txt 2
 python tools/microbench_generic.py 256 f32 wide > $O/microbench_wide_f32.txt 2>/dev/null
 python tools/microbench_generic.py 256 bf16 > $O/microbench_generic_bf16.txt 2>/dev/null
 bash tools/exp/bench_2d_nets.sh > $O/bench_2d_nets.txt 2>&1
-python bench.py --config config/psd_c4_deep_fp16.json --samples 512 --dtype f16 --cpu-steps 4 > $O/c4_f16.json 2> $O/c4_f16.log
+python bench.py --full --config config/psd_c4_deep_fp16.json --samples 512 --dtype f16 --cpu-steps 4 > $O/c4_f16.json 2> $O/c4_f16.log
 python tools/bench_eval.py > $O/bench_eval.json 2> $O/bench_eval.log
 for dt in bf16 f32; do
   bash tools/exp/prof_c5.sh final_$dt $dt

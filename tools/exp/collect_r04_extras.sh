@@ -16,7 +16,7 @@ mkdir -p $O
 bash tools/exp/knock_ec.sh 256 > $O/event_local_conv_build_knockouts.txt 2>&1
 python tools/microbench_conv.py 30 bf16 2048 > $O/microbench_conv_bf16_batch2048.txt 2>/dev/null
 bash tools/exp/bench_2d_nets.sh > $O/bench_2d_nets.txt 2>&1
-python bench.py --config config/psd_c4_deep_fp16.json --samples 512 --dtype f16 --cpu-steps 4 > $O/c4_f16.json 2> $O/c4_f16.log
+python bench.py --full --config config/psd_c4_deep_fp16.json --samples 512 --dtype f16 --cpu-steps 4 > $O/c4_f16.json 2> $O/c4_f16.log
 python tools/bench_eval.py > $O/bench_eval.json 2> $O/bench_eval.log
 for dt in bf16 f32; do
   bash tools/exp/prof_c5.sh final_$dt $dt
