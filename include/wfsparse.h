@@ -476,6 +476,39 @@ int wfs_tcn_bwd(const void *X, const void *dY, int64_t N, int32_t L, const float
 int wfs_tcn_taps_fwd(const void *param_ptrs, int32_t n_conv, int32_t k, float *taps, float *bias, void *stream);
 int wfs_tcn_taps_bwd(const void *param_ptrs, int32_t n_conv, int32_t k, const float *partial, int64_t N, void *stream);
 
+/* waveform rows -> voxels (csrc/voxelize.hip) ---------------------------------------------------------
+ * The hand-over between the front end and a 3-D sparse stack (BASELINE configs[4]: feat [n, 1, 2T] -> TCN -> voxelise ->
+ * SubM3d head; the reference's 3-D datasets are voxelised offline, src/datasets/PulseDataset.py:543-625).  Row r of
+ * `rows` [n_cap, 2T] (left PMT samples, then right) has an ACTIVE sample t iff rows[r][t] > threshold ||
+ * rows[r][T + t] > threshold; every active (r, t) is one voxel, numbered row-major, t ascending (the order of the host
+ * 3-D layout: psd/synthetic.py; deterministic, no atomics: a ballot per 64 samples and a prefix over the rows).
+ *   coords     int32 [n_cap, 3] = (x, y, evt) -- the 2-D layout's column order
+ *   n_dev      valid rows as everywhere (NULL = n_cap); rows beyond it give no voxel whatever they hold
+ *   rows / values / feats / dfeat / dY share `dtype`; `values` (e.g. the TCN's output, may be `rows` itself) gives the
+ *   features; 1 <= T <= WFS_VOXELIZE_MAX_SAMPLES, n_cap * T < 2^31.
+ * wfs_voxelize_plan (two launches): row_offsets int32 [wfs_voxelize_offsets_ints(n_cap, T)] = exclusive voxel offset of
+ *   every 64-sample slice of every row (S = ceil(T / 64) per row; row r's voxels start at row_offsets[r * S], rows beyond
+ *   the valid count have none), row_offsets[n_cap * S] = V, the true voxel count; *v_dev (int64, device) = min(V, V_cap);
+ *   *overflow_dev = 1 if V > V_cap -- STICKY, set and never cleared, as wfs_rulebook_emit's.  event_offsets (may be
+ *   NULL; needs coords and batch_size): the wfs_event_offsets table of the voxels, taken from the offsets of each event's
+ *   first row (flag word 0 != 0 <=> the rows' evt column is not non-decreasing / in [0, batch_size)).  An eager caller
+ *   passes V_cap = n_cap * T, reads *v_dev back once and emits into exactly that many rows.
+ * wfs_voxelize_emit (one launch): indices int32 [V_cap, 4] = (evt, x, y, t), batch-first; feats [V_cap, 2] =
+ *   (values[r][t], values[r][T + t]); voxels beyond V_cap are not written.  Same rows, coords and threshold as the plan.
+ * wfs_voxelize_bwd (one launch): dY [n_cap, 2T] from dfeat [V_cap, 2] through the plan's row_offsets and the t column of
+ *   the emitted indices: dY[r][t] / dY[r][T + t] = dfeat of the voxel (r, t), EXACT ZEROS everywhere else -- every row
+ *   up to the capacity is written whole (wfs_tcn_bwd has no row count and sums its tap partials over padding rows too). */
+#define WFS_VOXELIZE_MAX_SAMPLES 4096
+size_t wfs_voxelize_offsets_ints(int64_t n_cap, int32_t T);
+int wfs_voxelize_plan(const void *rows, const int32_t *coords, int64_t n_cap, int32_t T, const int64_t *n_dev,
+                      float threshold, int32_t batch_size, int64_t V_cap, int32_t *row_offsets, int64_t *v_dev,
+                      int32_t *event_offsets, int32_t *overflow_dev, int32_t dtype, void *stream);
+int wfs_voxelize_emit(const void *rows, const void *values, const int32_t *coords, int64_t n_cap, int32_t T,
+                      float threshold, const int32_t *row_offsets, int64_t V_cap, int32_t *indices, void *feats,
+                      int32_t dtype, void *stream);
+int wfs_voxelize_bwd(const void *dfeat, const int32_t *indices, const int32_t *row_offsets, int64_t n_cap, int32_t T,
+                     int64_t V_cap, void *dY, int32_t dtype, void *stream);
+
 /* loss ---------------------------------------------------------------------------------------------
  * torch.nn.CrossEntropyLoss(reduction='mean') as the reference's LitPSD applies it to the [B, n_type] logits
  * (src/engineering/LitBase.py:38-43, LitPSD.py:102), forward AND d loss / d logits in one launch (torch runs six:

@@ -1,0 +1,193 @@
+"""The waveform voxeliser (include/wfsparse.h wfs_voxelize_*, csrc/voxelize.hip) against the host 3-D layout: voxelising
+the 2-D layout's rows by "either PMT sample > 0" reproduces psd/synthetic.generate(..., layout="3d") bit for bit --
+coordinates, features and order -- so the generator is an exact oracle for the forward; the backward is checked against
+the exact scatter of a random gradient."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+
+
+@functools.lru_cache(maxsize=None)
+def _layouts(E, T, seed=11):
+    from waveformml_amd.psd import synthetic
+    c2, f2, _ = synthetic.generate(E, T, 3, seed=seed, layout="2d")
+    c3, f3, _ = synthetic.generate(E, T, 3, seed=seed, layout="3d")
+    return c2, f2, c3, f3
+
+
+def _run(rows, coords, thr=0.0, B=None, n_valid=None, cap=None, overflow=None, values=None):
+    from waveformml_amd.psd.voxel import voxelize
+    out = voxelize(rows, values, coords, thr, B, n_valid, cap, overflow)
+    torch.cuda.synchronize()
+    return out
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
+@pytest.mark.parametrize("E", [1, 64, 256, 2048])
+@pytest.mark.parametrize("T", [150, 256, 1024])
+def test_bit_exact_against_host_3d_layout(T, E, dtype):
+    c2, f2, c3, f3 = _layouts(E, T)
+    rows = torch.from_numpy(f2).to(DEV).to(dtype)
+    coords = torch.from_numpy(c2).to(DEV)
+    feats, idx, v_dev, events, offsets = _run(rows, coords, B=E)
+    want_idx = c3[:, [3, 0, 1, 2]]
+    assert idx.shape == (len(c3), 4) and int(v_dev.item()) == len(c3)
+    assert np.array_equal(idx.cpu().numpy(), want_idx)
+    assert torch.equal(feats.cpu(), torch.from_numpy(f3).to(dtype))
+    assert feats.dtype == dtype
+    # exclusive offsets of every 64-sample slice; at the rows' first slices: the counts of the 2-D layout's rows
+    S = (T + 63) // 64
+    on = ((f2[:, :T] > 0) | (f2[:, T:] > 0)).sum(1)
+    assert offsets.shape == (len(c2) * S + 1,)
+    assert np.array_equal(offsets.cpu().numpy()[::S], np.concatenate([[0], np.cumsum(on)]).astype(np.int32))
+
+
+def test_values_come_from_the_second_tensor_and_mask_from_the_first():
+    E, T = 64, 256
+    c2, f2, c3, _ = _layouts(E, T)
+    rows = torch.from_numpy(f2).to(DEV)
+    values = torch.randn_like(rows)
+    feats, idx, _, _, _ = _run(rows, torch.from_numpy(c2).to(DEV), values=values)
+    r, t = torch.nonzero((rows[:, :T] > 0) | (rows[:, T:] > 0), as_tuple=True)
+    assert torch.equal(feats, torch.stack([values[r, t], values[r, T + t]], 1))
+    assert np.array_equal(idx.cpu().numpy(), c3[:, [3, 0, 1, 2]])
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
+def test_device_count_mode_ignores_stale_padding_rows(dtype):
+    E, T = 256, 1024
+    c2, f2, c3, f3 = _layouts(E, T)
+    n = len(c2)
+    cap_rows = n + 77
+    rows = torch.rand((cap_rows, 2 * T), device=DEV).to(dtype) + 0.5       # stale waveforms everywhere
+    rows[:n] = torch.from_numpy(f2).to(DEV).to(dtype)
+    coords = torch.randint(0, 5, (cap_rows, 3), dtype=torch.int32, device=DEV)
+    coords[:n] = torch.from_numpy(c2).to(DEV)
+    n_valid = torch.tensor([n], dtype=torch.int64, device=DEV)
+    V = len(c3)
+    cap = V + 1000
+    flag = torch.zeros((1,), dtype=torch.int32, device=DEV)
+    feats, idx, v_dev, events, offsets = _run(rows, coords, B=E, n_valid=n_valid, cap=cap, overflow=flag)
+    assert idx.shape == (cap, 4) and int(v_dev.item()) == V and int(flag.item()) == 0
+    assert np.array_equal(idx[:V].cpu().numpy(), c3[:, [3, 0, 1, 2]])
+    assert torch.equal(feats[:V].cpu(), torch.from_numpy(f3).to(dtype))
+    off = offsets.cpu().numpy()
+    assert off[n * 16] == V and np.all(off[n * 16:] == V)         # padding rows own no voxel (16 slices per row)
+
+
+def test_overflow_is_sticky_and_nothing_is_written_past_the_capacity():
+    from waveformml_amd import _lib
+    E, T = 64, 256
+    c2, f2, c3, f3 = _layouts(E, T)
+    rows = torch.from_numpy(f2).to(DEV)
+    coords = torch.from_numpy(c2).to(DEV)
+    n_valid = torch.tensor([len(c2)], dtype=torch.int64, device=DEV)
+    V = len(c3)
+    cap, guard = V // 2 + 3, 4096
+    lib = _lib.load()
+    n = rows.shape[0]
+    offsets = torch.empty((int(lib.wfs_voxelize_offsets_ints(n, T)),), dtype=torch.int32, device=DEV)
+    v_dev = torch.empty((1,), dtype=torch.int64, device=DEV)
+    events = torch.empty((int(lib.wfs_event_offsets_ints(E)),), dtype=torch.int32, device=DEV)
+    flag = torch.zeros((1,), dtype=torch.int32, device=DEV)
+    idx = torch.full((cap + guard, 4), -7, dtype=torch.int32, device=DEV)
+    feats = torch.full((cap + guard, 2), -3.0, device=DEV)
+
+    def launch(capacity):
+        s = _lib.stream_ptr()
+        _lib.check(lib.wfs_voxelize_plan(_lib.ptr(rows), _lib.ptr(coords), n, T, _lib.ptr(n_valid), 0.0, E, capacity,
+                                         _lib.ptr(offsets), _lib.ptr(v_dev), _lib.ptr(events), _lib.ptr(flag),
+                                         _lib.WFS_F32, s))
+        _lib.check(lib.wfs_voxelize_emit(_lib.ptr(rows), _lib.ptr(rows), _lib.ptr(coords), n, T, 0.0, _lib.ptr(offsets),
+                                         capacity, _lib.ptr(idx), _lib.ptr(feats), _lib.WFS_F32, s))
+        torch.cuda.synchronize()
+
+    launch(cap)
+    assert int(flag.item()) == 1 and int(v_dev.item()) == cap and int(offsets[-1].item()) == V
+    assert np.array_equal(idx[:cap].cpu().numpy(), c3[:cap, [3, 0, 1, 2]])
+    assert torch.equal(feats[:cap].cpu(), torch.from_numpy(f3[:cap]))
+    assert bool((idx[cap:] == -7).all()) and bool((feats[cap:] == -3.0).all())
+    ev = events.cpu().numpy()
+    assert ev[E] == cap and np.all(ev[:E + 1] <= cap) and np.all(np.diff(ev[:E + 1]) >= 0)
+    launch(cap + guard + V)                                 # fits: the flag stays set
+    assert int(flag.item()) == 1 and int(v_dev.item()) == V
+
+
+def test_hand_made_rows():
+    T = 100
+    rows = torch.zeros((4, 2 * T), device=DEV)
+    rows[1] = 1.0                                            # fully active
+    rows[2, 5] = 0.3                                         # left only: below 0.5
+    rows[2, T + 7] = 0.7                                     # right only: above 0.5
+    rows[2, 9] = 0.6
+    rows[2, T + 9] = 0.1
+    rows[3, T - 1] = 0.2
+    coords = torch.tensor([[0, 0, 0], [1, 2, 0], [3, 4, 1], [5, 6, 2]], dtype=torch.int32, device=DEV)
+    feats, idx, v_dev, _, offsets = _run(rows, coords, B=3)
+    assert int(v_dev.item()) == T + 3 + 1
+    assert offsets.tolist()[::2] == [0, 0, T, T + 3, T + 4]           # two slices per row
+    assert idx[:T].tolist() == [[0, 1, 2, t] for t in range(T)]
+    assert idx[T:].tolist() == [[1, 3, 4, 5], [1, 3, 4, 7], [1, 3, 4, 9], [2, 5, 6, T - 1]]
+    feats, idx, v_dev, _, offsets = _run(rows, coords, thr=0.5, B=3)
+    assert int(v_dev.item()) == T + 2
+    assert idx[T:].tolist() == [[1, 3, 4, 7], [1, 3, 4, 9]]
+    assert feats[T:].tolist() == [[0.0, pytest.approx(0.7)], [pytest.approx(0.6), pytest.approx(0.1)]]
+    # no sample above the threshold
+    feats, idx, v_dev, _, _ = _run(rows, coords, thr=1.0, B=3)
+    assert int(v_dev.item()) == 0 and idx.shape == (0, 4)
+
+
+@pytest.mark.parametrize("n_valid", [False, True])
+def test_event_table_equals_event_offsets_of_the_voxels(n_valid):
+    from waveformml_amd.spconv import ops
+    E, T = 256, 150
+    c2, f2, c3, _ = _layouts(E, T)
+    rows = torch.from_numpy(f2).to(DEV)
+    coords = torch.from_numpy(c2).to(DEV)
+    nv = torch.tensor([len(c2)], dtype=torch.int64, device=DEV) if n_valid else None
+    cap = len(c3) + 64 if n_valid else None
+    flag = torch.zeros((1,), dtype=torch.int32, device=DEV)
+    feats, idx, v_dev, events, _ = _run(rows, coords, B=E + 3, n_valid=nv, cap=cap, overflow=flag)   # 3 empty events
+    want = ops.event_offsets(idx, E + 3, v_dev)
+    torch.cuda.synchronize()
+    assert torch.equal(events, want)
+    assert int(events[E + 4:].abs().sum()) == 0
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
+@pytest.mark.parametrize("T", [150, 1024])
+def test_backward_is_the_exact_scatter_and_zero_elsewhere(T, dtype):
+    E = 64
+    c2, f2, c3, _ = _layouts(E, T)
+    n = len(c2)
+    pad = 13
+    rows = torch.zeros((n + pad, 2 * T), device=DEV).to(dtype)
+    rows[:n] = torch.from_numpy(f2).to(DEV).to(dtype)
+    rows[n:] = 1.0                                           # stale padding rows
+    coords = torch.zeros((n + pad, 3), dtype=torch.int32, device=DEV)
+    coords[:n] = torch.from_numpy(c2).to(DEV)
+    values = rows.clone().requires_grad_(True)
+    n_valid = torch.tensor([n], dtype=torch.int64, device=DEV)
+    V = len(c3)
+    for nv, cap in ((None, None), (n_valid, V + 100)):
+        flag = torch.zeros((1,), dtype=torch.int32, device=DEV)
+        if nv is None:
+            r_in, v_in, c_in = rows[:n].contiguous(), values[:n], coords[:n].contiguous()
+        else:
+            r_in, v_in, c_in = rows, values, coords
+        feats, idx, v_dev, _, _ = _run(r_in, c_in, B=E, n_valid=nv, cap=cap, overflow=flag, values=v_in)
+        g = torch.randn(feats.shape, device=DEV).to(dtype)
+        values.grad = None
+        feats.backward(g)
+        got = values.grad
+        r, t = torch.nonzero((rows[:n, :T] > 0) | (rows[:n, T:] > 0), as_tuple=True)
+        want = torch.zeros_like(rows)
+        want[r, t] = g[:V, 0]
+        want[r, T + t] = g[:V, 1]
+        assert torch.equal(got, want)
+        assert int((got[n:] != 0).sum()) == 0

@@ -107,6 +107,11 @@ SIGNATURES = {
     "wfs_tcn_fwd": (ctypes.c_int, [_vp, _i64, _i32, _vp, _vp, _i32, _i32, _vp, _i32, ctypes.c_float, _vp, _vp]),
     "wfs_tcn_bwd": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _i32, ctypes.c_float, _vp,
                                     _vp]),
+    "wfs_voxelize_offsets_ints": (_sz, [_i64, _i32]),
+    "wfs_voxelize_plan": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp, ctypes.c_float, _i32, _i64, _vp, _vp, _vp, _vp, _i32,
+                                         _vp]),
+    "wfs_voxelize_emit": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, ctypes.c_float, _vp, _i64, _vp, _vp, _i32, _vp]),
+    "wfs_voxelize_bwd": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _i64, _vp, _i32, _vp]),
     "wfs_xent_mean_fwd_bwd": (ctypes.c_int, [_vp, _vp, _i64, _i32, _i64, _vp, _vp, _vp]),
     "wfs_sgd_step": (ctypes.c_int, [_vp, _vp, _vp, _i64, _vp, ctypes.c_float, ctypes.c_float, ctypes.c_float, _i32, _i32,
                                     _vp]),

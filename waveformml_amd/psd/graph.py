@@ -125,16 +125,22 @@ class GraphedTrainStep(object):
         reducer.finish()
         optimizer.step()
         del loss
+        # in proportion to the ROW capacity, which min_rows (a re-capture's floor, the largest batch among the ranks)
+        # may have raised above headroom x this batch: a batch that fits the rows must fit the strided layers too
+        own = _round_up(headroom * coords.shape[0], granule)
+        factor = headroom if self.n_cap <= own else self.n_cap / max(1.0, float(coords.shape[0]))
+        # a tight row capacity (a re-capture sized from the row counts seen, Trainer._recapture_rows) says nothing
+        # about the outputs-per-input ratio of the strided layers, which varies by a few per cent from batch to
+        # batch: they keep 6 % on top (the conv kernels share out the VALID tiles, so this room is nearly free)
+        slack = 1.06 if headroom < 1.05 else 1.0
         for m in self._convs:
-            # in proportion to the ROW capacity, which min_rows (a re-capture's floor, the largest batch among the ranks)
-            # may have raised above headroom x this batch: a batch that fits the rows must fit the strided layers too
-            own = _round_up(headroom * coords.shape[0], granule)
-            factor = headroom if self.n_cap <= own else self.n_cap / max(1.0, float(coords.shape[0]))
-            # a tight row capacity (a re-capture sized from the row counts seen, Trainer._recapture_rows) says nothing
-            # about the outputs-per-input ratio of the strided layers, which varies by a few per cent from batch to
-            # batch: they keep 6 % on top (the conv kernels share out the VALID tiles, so this room is nearly free)
-            slack = 1.06 if headroom < 1.05 else 1.0
             m.out_capacity = _round_up(slack * factor * m.last_rulebook.M, granule)
+        # other modules with a data-dependent output size (psd/voxel.Voxelizer): the count of the calibration step, the
+        # same headroom and granule; their sticky flags join the strided layers' overflow flags in check()
+        self._sized = _sized_modules(module)
+        for m in self._sized:
+            m.out_capacity = _round_up(slack * factor * m.calibration_count(), granule)
+            m.fresh_sticky_flags()        # this graph's own flags (an eval graph captured later gets others)
         if self.exchange_after:
             reducer.remove()              # no collectives inside the graph: gradients are exchanged after the replay
         # ---- warm-up in device-count mode, then capture
@@ -161,10 +167,11 @@ class GraphedTrainStep(object):
             reducer.remove()
             self._warm_and_capture(warmup)
         self._overflow = [m.last_rulebook.overflow for m in self._convs if m.last_rulebook.overflow is not None]
+        self._sized_flags = [f for m in self._sized for f in m.sticky_flags()]
         self._event_flags = _event_flags(module)
         # the builds only ever SET these (sticky); allocated inside the capture they start undefined: cleared here and
         # after every read, so that check() sees a failure of ANY replay since the last check()
-        _clear_flags(self._overflow, self._event_flags)
+        _clear_flags(self._overflow, self._event_flags, self._sized_flags)
 
     @staticmethod
     def _headroom_granule(rows, labels, headroom=None, granule=None):
@@ -345,12 +352,12 @@ class GraphedTrainStep(object):
         return self.loss
 
     def check(self):
-        """Synchronises; raises if any strided layer produced more rows than its capacity in the last step -- on ANY
+        """Synchronises; raises if any strided layer produced more rows than its capacity in the last step (or a voxeliser
+        more voxels than its capacity: psd/voxel.Voxelizer, its own message) -- on ANY
         rank: the flag is all-reduced first, so every rank raises together instead of one rank leaving its peers
         blocked in the next collective."""
-        flag = torch.zeros((), dtype=torch.int32, device=self.coords.device)
-        if self._overflow:
-            flag = torch.stack([o.reshape(()) for o in self._overflow]).any().to(torch.int32)
+        flag = _any_set(self._overflow, self.coords.device)
+        vflag = _any_set(getattr(self, "_sized_flags", ()), self.coords.device)
         evf = torch.zeros((), dtype=torch.int32, device=self.coords.device)
         for f in getattr(self, "_event_flags", ()):
             evf = evf | f[: 2 * (f.numel() // 3)].any().to(torch.int32)
@@ -358,13 +365,15 @@ class GraphedTrainStep(object):
             dist.all_reduce(evf, op=dist.ReduceOp.MAX, group=self.reducer.group)
         if self.world > 1 and dist.is_available() and dist.is_initialized():
             dist.all_reduce(flag, op=dist.ReduceOp.MAX, group=self.reducer.group)
+            if getattr(self, "_sized_flags", None):
+                dist.all_reduce(vflag, op=dist.ReduceOp.MAX, group=self.reducer.group)
         bad_events, overflow = bool(evf.item()), bool(flag.item())
-        _clear_flags(self._overflow, getattr(self, "_event_flags", ()))
+        voxels = bool(vflag.item()) if getattr(self, "_sized_flags", None) else False
+        _clear_flags(self._overflow, getattr(self, "_event_flags", ()), getattr(self, "_sized_flags", ()))
         if bad_events:
             raise RuntimeError("a batch was not grouped by event (or an event exceeded the LDS tables of the event-local "
                                "rulebook build, or held duplicate coordinates); set WFS_EVENT_LOCAL=0 and re-capture")
-        if overflow:
-            raise RuntimeError("a sparse conv output exceeded its captured capacity; re-capture with more headroom")
+        _raise_overflow(overflow, voxels)
 
 
 def _collective_capture_works(group, dev):
@@ -460,6 +469,31 @@ class ShapeAgreement(object):
         return int(r[0]), -int(r[2]), int(r[1]), bool(r[3])
 
 
+def _sized_modules(module):
+    """Modules with a data-dependent output size besides the strided convs (psd/voxel.Voxelizer): a capacity calibrated
+    from ``calibration_count()``, overflow flags from ``sticky_flags()``, new flags per captured graph from
+    ``fresh_sticky_flags()``."""
+    return [m for m in module.modules()
+            if hasattr(m, "calibration_count") and hasattr(m, "sticky_flags") and hasattr(m, "fresh_sticky_flags")]
+
+
+def _any_set(flags, dev):
+    if not flags:
+        return torch.zeros((), dtype=torch.int32, device=dev)
+    return torch.stack([o.reshape(()) for o in flags]).any().to(torch.int32)
+
+
+def _raise_overflow(conv, voxels):
+    if conv and voxels:
+        raise RuntimeError("a batch exceeded the captured voxel capacity AND a sparse conv output exceeded its captured "
+                           "capacity; re-capture with more headroom")
+    if voxels:
+        raise RuntimeError("a batch had more voxels than the captured voxel capacity (psd/voxel.Voxelizer); re-capture "
+                           "with more headroom or on a busier batch")
+    if conv:
+        raise RuntimeError("a sparse conv output exceeded its captured capacity; re-capture with more headroom")
+
+
 def _clear_flags(*groups):
     for tensors in groups:
         for t in tensors:
@@ -534,6 +568,11 @@ class GraphedEvalStep(object):
                 net([coords, feats])
                 for m in self._convs:
                     m.out_capacity = _round_up(headroom * m.last_rulebook.M, granule)
+                self._sized = _sized_modules(module)
+                for m in self._sized:
+                    # this runner's own capacity (from ITS calibration batch) and flags, as GraphedTrainStep's
+                    m.out_capacity = _round_up(headroom * m.calibration_count(), granule)
+                    m.fresh_sticky_flags()
                 if self.indices is not None:
                     net.batch_first_indices = (self.coords, self.indices)
                 self._load(example_batch)
@@ -547,7 +586,9 @@ class GraphedEvalStep(object):
                 with torch.cuda.graph(self.graph, stream=self.stream):
                     self.logits = self._forward()
                 self._overflow = [m.last_rulebook.overflow for m in self._convs if m.last_rulebook.overflow is not None]
-                _clear_flags(self._overflow)            # sticky flags allocated inside the capture (see GraphedTrainStep)
+                self._sized_flags = [f for m in self._sized for f in m.sticky_flags()]
+                # sticky flags allocated inside the capture (see GraphedTrainStep)
+                _clear_flags(self._overflow, self._sized_flags)
                 self.graph_fwd = None
                 if sweep:
                     # second capture inside the same reuse context: every rulebook build is a cache hit (same static
@@ -596,9 +637,12 @@ class GraphedEvalStep(object):
         return self.logits_fwd
 
     def check(self):
-        if self._overflow and bool(torch.stack([o.reshape(()) for o in self._overflow]).any().item()):
-            _clear_flags(self._overflow)
-            raise RuntimeError("a sparse conv output exceeded its captured capacity; re-capture with more headroom")
+        dev = self.coords.device
+        conv = bool(self._overflow) and bool(_any_set(self._overflow, dev).item())
+        voxels = bool(self._sized_flags) and bool(_any_set(self._sized_flags, dev).item())
+        if conv or voxels:
+            _clear_flags(self._overflow, self._sized_flags)
+            _raise_overflow(conv, voxels)
 
     def close(self):
         if self._reuse is not None:

@@ -107,6 +107,10 @@ class SPConvNet(nn.Module):
         ev = getattr(self, "batch_events", None)
         if ev is not None and ev[0] is coords and handed is not None and handed[0] is coords:
             st.events = ev[1]                     # first row of every event: what the event-local rulebook build starts from
+        return self._head(st)
+
+    def _head(self, st):
+        """The sparse stack and the dense head on a SparseConvTensor (shared with SPConvHybrid3DNet)."""
         fsp = getattr(self.spconv, "functional", None)
         if fsp is not None and hasattr(fsp, "sparse_head") and hasattr(self.sparseModel, "run"):
             # ToDense -> view -> Linear off the sparse rows (csrc/shead.hip) when the tail has that shape
@@ -114,10 +118,12 @@ class SPConvNet(nn.Module):
             out = self.sparseModel.run(st, list(self.sparseModel._modules.values()), stop_before_dense=True)
             if hasattr(out, "features") and hasattr(out, "dense"):
                 if fsp.can_use_sparse_head(out, layers):
+                    self.head_route = "sparse_head"           # the route the last forward (or capture) took
                     return fsp.sparse_head(out, layers[0])
                 out = out.dense()
         else:
             out = self.sparseModel(st)
+        self.head_route = "dense"
         out = out.view(-1, self.n_linear)
         if fsp is not None and hasattr(fsp, "head_forward"):
             return fsp.head_forward(out, self.linear)         # per layer: streaming / matrix-core HIP kernels or torch
@@ -184,3 +190,45 @@ class SPConvNet(nn.Module):
         self.n_linear = flat
         head = LinearBlock(flat, self.ntype, hparams.n_lin)
         self.linear = head.func
+
+
+class SPConvHybrid3DNet(SPConvNet):
+    """BASELINE configs[4] ("C5") as BASELINE.md 3 spells it: feat [n, 1, 2T] -> TCN -> voxelise -> SubM3d head.  The
+    reference's hybrid SPConvNet feeds the TCN's rows to a 2-D sparse stack (its 3-D form is a TODO,
+    src/models/SPConvNet.py:72); here the rows [coords (x, y, evt), feats [n, 2T](, n_valid)] of the 2-D layout go
+    through the single-channel TemporalConvNet (``hparams.n_dil`` / ``hparams.wf_params``, as ``_from_hparams``) and are
+    voxelised on the GPU (psd/voxel.py: a voxel per sample where either PMT's RAW sample exceeds ``hparams.threshold``,
+    default 0 -- the zero-suppressed data's own voxel set) into the [14, 11, n_samples] grid, and the ``algorithm``
+    stack (first layer Cin = 2, built as SPConvNet builds it) with its head runs on the voxels."""
+
+    def __init__(self, config):
+        nn.Module.__init__(self)
+        from .tcn import TemporalConvNet
+        from .voxel import Voxelizer
+        self.log = logging.getLogger(__name__)
+        self.system_config = config.system_config
+        self.net_config = config.net_config
+        self.nsamples = self.system_config.n_samples
+        self.ntype = self.system_config.n_type
+        self.modules_util = ModuleUtility(self.net_config.imports)
+        self.spconv = self.modules_util.retrieve_module("spconv")
+        self.sequence_class = self.modules_util.retrieve_class(self.net_config.sequence_class)
+        self.batch_size_hint = None
+        hparams = self.net_config.hparams
+        params = DictionaryUtility.to_dict(hparams.wf_params) if hasattr(hparams, "wf_params") else {}
+        self.waveformLayer = TemporalConvNet(1, [1] * hparams.n_dil, **params)
+        self.voxelizer = Voxelizer(getattr(hparams, "threshold", 0.0))
+        self._from_algorithm(self.net_config.algorithm)
+        self.ndim = 3
+        self.spatial_size = [14, 11, int(self.nsamples)]
+
+    def forward(self, x, batch_size=None):
+        coords, feats = x[0], x[1]
+        n_valid = x[2] if len(x) > 2 else None
+        if batch_size is None:
+            batch_size = self.batch_size_hint
+        if batch_size is None:
+            batch_size = int(coords[-1, -1]) + 1          # one device->host read, as the reference's
+        values = self.waveformLayer(feats.unsqueeze(1)).squeeze(1)
+        st = self.voxelizer(feats, values, coords, batch_size, self.spatial_size, self.spconv, n_valid)
+        return self._head(st)
