@@ -95,8 +95,9 @@ def test_overflow_is_sticky_and_nothing_is_written_past_the_capacity():
     v_dev = torch.empty((1,), dtype=torch.int64, device=DEV)
     events = torch.empty((int(lib.wfs_event_offsets_ints(E)),), dtype=torch.int32, device=DEV)
     flag = torch.zeros((1,), dtype=torch.int32, device=DEV)
-    idx = torch.full((cap + guard, 4), -7, dtype=torch.int32, device=DEV)
-    feats = torch.full((cap + guard, 2), -3.0, device=DEV)
+    # room for every voxel: the last launch below is given a capacity of cap + guard + V rows and writes all V of them
+    idx = torch.full((cap + guard + V, 4), -7, dtype=torch.int32, device=DEV)
+    feats = torch.full((cap + guard + V, 2), -3.0, device=DEV)
 
     def launch(capacity):
         s = _lib.stream_ptr()

@@ -169,6 +169,7 @@ class GraphedTrainStep(object):
         self._overflow = [m.last_rulebook.overflow for m in self._convs if m.last_rulebook.overflow is not None]
         self._sized_flags = [f for m in self._sized for f in m.sticky_flags()]
         self._event_flags = _event_flags(module)
+        self._conv_states = _conv_states(module)      # written by every replay: alive for as long as the graph is
         # the builds only ever SET these (sticky); allocated inside the capture they start undefined: cleared here and
         # after every read, so that check() sees a failure of ANY replay since the last check()
         _clear_flags(self._overflow, self._event_flags, self._sized_flags)
@@ -358,9 +359,7 @@ class GraphedTrainStep(object):
         blocked in the next collective."""
         flag = _any_set(self._overflow, self.coords.device)
         vflag = _any_set(getattr(self, "_sized_flags", ()), self.coords.device)
-        evf = torch.zeros((), dtype=torch.int32, device=self.coords.device)
-        for f in getattr(self, "_event_flags", ()):
-            evf = evf | f[: 2 * (f.numel() // 3)].any().to(torch.int32)
+        evf = _any_event_flag(getattr(self, "_event_flags", ()), self.coords.device)
         if self.world > 1 and dist.is_available() and dist.is_initialized():
             dist.all_reduce(evf, op=dist.ReduceOp.MAX, group=self.reducer.group)
         if self.world > 1 and dist.is_available() and dist.is_initialized():
@@ -371,8 +370,7 @@ class GraphedTrainStep(object):
         voxels = bool(vflag.item()) if getattr(self, "_sized_flags", None) else False
         _clear_flags(self._overflow, getattr(self, "_event_flags", ()), getattr(self, "_sized_flags", ()))
         if bad_events:
-            raise RuntimeError("a batch was not grouped by event (or an event exceeded the LDS tables of the event-local "
-                               "rulebook build, or held duplicate coordinates); set WFS_EVENT_LOCAL=0 and re-capture")
+            raise RuntimeError(_EVENTS_MESSAGE)
         _raise_overflow(overflow, voxels)
 
 
@@ -500,6 +498,30 @@ def _clear_flags(*groups):
             t.zero_()
 
 
+_EVENTS_MESSAGE = ("a batch was not grouped by event (or an event exceeded the LDS tables of the event-local rulebook "
+                   "build, or held duplicate coordinates); set WFS_EVENT_LOCAL=0 and re-capture")
+
+
+def _any_event_flag(flags, dev):
+    """int32 scalar: 1 if any failure word (the first two thirds of each flag tensor) of the event-local builds is set."""
+    evf = torch.zeros((), dtype=torch.int32, device=dev)
+    for f in flags:
+        evf = evf | f[: 2 * (f.numel() // 3)].any().to(torch.int32)
+    return evf
+
+
+def _conv_states(module):
+    """The look-back state tensors (epoch + per-event counts) of the module's event-local conv builds: a captured graph
+    writes them on every replay, so its runner keeps them alive."""
+    out, seen = [], set()
+    for m in module.modules():
+        st = getattr(getattr(m, "last_rulebook", None), "conv_state", None)
+        if st is not None and st.data_ptr() not in seen:
+            seen.add(st.data_ptr())
+            out.append(st)
+    return out
+
+
 def _event_flags(module):
     """Failure flags of the event-local rulebook builds of the module's conv layers (spconv.ops.EVENT_LOCAL)."""
     out, seen = [], set()
@@ -587,8 +609,10 @@ class GraphedEvalStep(object):
                     self.logits = self._forward()
                 self._overflow = [m.last_rulebook.overflow for m in self._convs if m.last_rulebook.overflow is not None]
                 self._sized_flags = [f for m in self._sized for f in m.sticky_flags()]
+                self._event_flags = _event_flags(module)
+                self._conv_states = _conv_states(module)
                 # sticky flags allocated inside the capture (see GraphedTrainStep)
-                _clear_flags(self._overflow, self._sized_flags)
+                _clear_flags(self._overflow, self._sized_flags, self._event_flags)
                 self.graph_fwd = None
                 if sweep:
                     # second capture inside the same reuse context: every rulebook build is a cache hit (same static
@@ -637,12 +661,17 @@ class GraphedEvalStep(object):
         return self.logits_fwd
 
     def check(self):
+        """Synchronises; raises if a replay since the last check() met a batch that was not grouped by event (the
+        event-local builds then leave empty tables: bias-only logits) or exceeded a capacity.  Clears the flags."""
         dev = self.coords.device
         conv = bool(self._overflow) and bool(_any_set(self._overflow, dev).item())
         voxels = bool(self._sized_flags) and bool(_any_set(self._sized_flags, dev).item())
-        if conv or voxels:
-            _clear_flags(self._overflow, self._sized_flags)
-            _raise_overflow(conv, voxels)
+        bad_events = bool(self._event_flags) and bool(_any_event_flag(self._event_flags, dev).item())
+        if conv or voxels or bad_events:
+            _clear_flags(self._overflow, self._sized_flags, self._event_flags)
+        if bad_events:
+            raise RuntimeError(_EVENTS_MESSAGE)
+        _raise_overflow(conv, voxels)
 
     def close(self):
         if self._reuse is not None:

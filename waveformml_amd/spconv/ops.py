@@ -138,6 +138,7 @@ class Rulebook(object):
         self.events_in = None
         self.events_out = None       # event-local conv build: the event offsets of the OUTPUT rows
         self.event_flags = None
+        self.conv_state = None       # event-local conv build: the epoch and per-event counts its launches exchange
         self._pairs = None
         self._pair_num = None
 
@@ -270,16 +271,22 @@ def _sticky_flags(n, dev, store=None, name=None):
     capture, and handed to every later build of that layer -- memory allocated inside a capture can be the recycled block
     of an earlier temporary of the same graph, which every replay then writes before the build runs: fine for a flag the
     build rewrites, fatal for one it only sets.  Without a store: zeros (empty inside a capture: such a flag is only good
-    until the next replay)."""
+    until the next replay).
+
+    Every tensor is kept under (name, size): a build for another batch size (the look-back state of the event-local conv
+    build grows with the number of events) gets a tensor of its own and never replaces the one that a graph captured at
+    the other size still writes on every replay.  ``store[name]`` is the tensor the layer's latest build was handed."""
     capturing = dev.type == "cuda" and torch.cuda.is_current_stream_capturing()
     if store is not None:
-        t = store.get(name)
-        if t is None or t.numel() != n or t.device != dev:
+        key = (name, int(n))
+        t = store.get(key)
+        if t is None or t.device != dev:
             if capturing:
                 raise RuntimeError("waveformml_amd.spconv: the layer's failure flags must exist before a graph capture "
                                    "(run the step once in device-count mode first, as psd/graph.py does)")
             t = torch.zeros((n,), dtype=torch.int32, device=dev)
-            store[name] = t
+            store[key] = t
+        store[name] = t
         return t
     if capturing:
         return torch.empty((n,), dtype=torch.int32, device=dev)
@@ -332,6 +339,7 @@ def _event_local_conv(rb, g, lib, indices, batch_size, n_dev, m_cap, events, fla
         state = _sticky_flags(n_state, dev, flags, "conv_state")
     else:
         state = torch.zeros((n_state,), dtype=torch.int32, device=dev)      # inside a capture: re-zeroed by every replay
+    rb.conv_state = state            # the captured runners hold it for as long as their graphs write it
     rb.events_in = events if events is not None else event_offsets(indices, B, n_dev)
     rb.events_out = torch.empty((int(lib.wfs_event_offsets_ints(B)),), dtype=torch.int32, device=dev)
     rb.out_indices = torch.empty((m_cap, ndim + 1), dtype=torch.int32, device=dev)
