@@ -204,6 +204,52 @@ def test_eval_graph_has_its_own_voxel_capacity_and_flag():
     step.check()                                             # the eval graph's overflow is not the training step's
 
 
+def _spread(batch, T, seed):
+    """The same rows, features and labels, every event's rows moved to distinct random cells of the whole 14 x 11 x T grid
+    (ascending in row order): far fewer rows share a strided layer's output cell, so its outputs outgrow the capacity a
+    compact batch calibrated, while the rows still fit."""
+    (c, f), y = batch
+    cc = c.cpu().numpy().copy()
+    rng = np.random.default_rng(seed)
+    for e in np.unique(cc[:, -1]):
+        rows = np.nonzero(cc[:, -1] == e)[0]
+        cells = np.sort(rng.choice(14 * 11 * T, size=len(rows), replace=False))
+        cc[rows, 0], cc[rows, 1], cc[rows, 2] = cells // (11 * T), cells // T % 11, cells % T
+    return ([torch.from_numpy(cc).to(c.device), f], y)
+
+
+def test_train_and_eval_graphs_keep_their_own_conv_overflow_flags():
+    """A GraphedTrainStep and a GraphedEvalStep captured on one C2 module at the same batch size: a batch that fits the
+    rows but overflows the strided layers raises in the check() of the runner that replayed it and never in the other's,
+    in both directions -- the strided layers' flags are per runner, as the voxeliser's."""
+    from test_gpu_event_conv import _batch, _cfg, _module, _train_step
+    from waveformml_amd.psd.graph import GraphedEvalStep
+    T, B = 64, 32
+    mod = _module(_cfg(T))
+    good = _batch(B, T, 71)
+    spread = _spread(good, T, 72)
+    step, _red, _opt = _train_step(mod, good)
+    ev = GraphedEvalStep(mod, good)
+    assert step.fits(spread) and ev.fits(spread)
+    assert np.isfinite(float(step(good))) and bool(torch.isfinite(ev(good)).all())
+    step.check()
+    ev.check()
+    ev(spread)
+    step.check()                                             # the eval graph's overflow is not the training step's
+    with pytest.raises(RuntimeError, match="sparse conv output exceeded its captured capacity"):
+        ev.check()
+    step(spread)
+    ev.check()                                               # ... nor the training step's the eval graph's
+    with pytest.raises(RuntimeError, match="sparse conv output exceeded its captured capacity"):
+        step.check()
+    ev(good)
+    step(good)
+    ev.check()
+    step.check()
+    ev.close()
+    step.close()
+
+
 def test_trainer_validation_on_a_busier_batch_raises():
     """Trainer(capture=True).fit with a validation loader: a validation batch with more voxels than the eval graph's
     capacity raises instead of giving wrong metrics."""

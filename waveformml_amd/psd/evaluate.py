@@ -29,23 +29,27 @@ def test_loop(module, loader, device, feature_dtype=None, capture=False):
     module.eval()
     tot, acc, n = 0.0, 0.0, 0          # tot / acc become device scalars: one read-back at the end of the loop
     step = None
-    for i, batch in enumerate(loader):
-        batch = to_device(batch, device, feature_dtype)
-        b = int(batch[1].shape[0])
-        if capture:
-            if step is None:
-                from .graph import GraphedEvalStep
-                step = GraphedEvalStep(module, batch)
-            if step.fits(batch):
-                loss, a = _score(module, step(batch, module.occlude_index), batch[1])
-                tot, acc, n = tot + loss * b, acc + a * b, n + b
-                continue
-        res = module.test_step(batch, i)
-        tot = tot + res["test_loss"].detach().float() * b
-        acc = acc + res["test_acc"].detach().float() * b
-        n += b
-    if step is not None:
-        step.check()
+    try:
+        for i, batch in enumerate(loader):
+            batch = to_device(batch, device, feature_dtype)
+            b = int(batch[1].shape[0])
+            if capture:
+                if step is None:
+                    from .graph import GraphedEvalStep
+                    step = GraphedEvalStep(module, batch)
+                if step.fits(batch):
+                    loss, a = _score(module, step(batch, module.occlude_index), batch[1])
+                    tot, acc, n = tot + loss * b, acc + a * b, n + b
+                    continue
+            res = module.test_step(batch, i)
+            tot = tot + res["test_loss"].detach().float() * b
+            acc = acc + res["test_acc"].detach().float() * b
+            n += b
+        if step is not None:
+            step.check()
+    finally:
+        if step is not None:
+            step.close()
     import torch.distributed as dist
     if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
         # every rank ran its own share of the items (data.rank_sampler): event-weighted sums over all ranks

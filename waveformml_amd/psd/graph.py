@@ -19,6 +19,10 @@ import sys
 import torch
 import torch.distributed as dist
 
+from .. import _lib
+from ..spconv import ops
+from .voxel import Voxelizer
+
 
 @contextlib.contextmanager
 def _no_gc():
@@ -41,50 +45,213 @@ def _round_up(v, m):
     return int((int(v) + m - 1) // m * m)
 
 
-class GraphedTrainStep(object):
-    def __init__(self, module, optimizer, reducer, example_batch, headroom=None, granule=None, warmup=2, min_rows=0):
+class _CapturedRunner(object):
+    """What the captured runners share: the capacity-padded buffers a batch is copied into, the calling thread's stream,
+    capacity calibration, the sticky failure flags their graphs may set (spconv.ops.StickyFlags), check() and close()."""
+
+    @staticmethod
+    def _headroom_granule(rows, labels, headroom=None, granule=None):
         # headroom: row capacities = headroom x the example batch's row counts.  Capacity is not free (the
         # register-resident BatchNorm kernels and the rulebook grids are sized by it: 1.25 -> 1.12 measured -4 % per
         # step).  The voxel count of an E-event PSD batch varies by sigma ~ 0.5 / sqrt(E) of its mean (3.1 % at 256
         # events: psd/synthetic, 40 batches), so the default is 6 sigma above the example batch: 1 + 3 / sqrt(E), i.e.
         # 1.19 at 256 events.  A batch beyond a capacity is detected (check()), never silently cut.
+        if headroom is None and os.environ.get("WFS_CAPTURE_HEADROOM"):
+            headroom = float(os.environ["WFS_CAPTURE_HEADROOM"])          # experiments: tools/exp (capacity is not free)
+        if headroom is None:
+            headroom = max(1.1, 1.0 + 3.0 / max(1.0, float(labels)) ** 0.5)
+        if granule is None:
+            # capacities are rounded up to a granule; padded rows cost real work in the wide-channel (GEMM route) layers
+            # of the 2-D nets, whose batches are a few hundred rows, so the granule follows the batch
+            granule = 512 if rows >= 32768 else (256 if rows >= 2048 else 64)
+        return headroom, granule
+
+    @classmethod
+    def capacity_for(cls, rows, labels):
+        """The row capacity a step captured on a batch of ``rows`` rows and ``labels`` labels gets: ranks that capture
+        together pass the LARGEST row count among them as ``min_rows`` so that they all hold the same capacity (their
+        replay-or-ordinary-step decisions are derived from agreed counts and must come out alike)."""
+        headroom, granule = cls._headroom_granule(int(rows), int(labels))
+        return _round_up(headroom * int(rows), granule)
+
+    def _static_buffers(self, module, example_batch, headroom, granule, min_rows=0, per_row=False):
+        """The buffers every batch is copied into, ``n_cap`` rows each.  Returns the net (``module.model``)."""
         (coords, feats), labels = example_batch
-        headroom, granule = self._headroom_granule(int(coords.shape[0]), int(labels.shape[0]), headroom, granule)
-        assert coords.is_cuda and feats.is_cuda and labels.is_cuda
-        self.module, self.optimizer, self.reducer = module, optimizer, reducer
+        assert coords.is_cuda and feats.is_cuda
         dev = coords.device
+        self.module, self.per_row = module, per_row
+        self.graph, self._graphs = None, []
         self.n_cap = max(_round_up(headroom * coords.shape[0], granule), _round_up(min_rows, granule))
         self.coords = torch.zeros((self.n_cap, coords.shape[1]), dtype=coords.dtype, device=dev)
         self.feats = torch.zeros((self.n_cap, feats.shape[1]), dtype=feats.dtype, device=dev)
         # targets: one per EVENT (LitPSD: a fixed number per batch), or one per ROW (per-segment modules with
         # ``per_row_targets``: LitSegClassifier) -- then the buffer has the rows' capacity and everything beyond the valid
         # rows holds the criterion's ignore_index, so that the padding rows neither count nor receive a gradient
-        self.per_row = bool(getattr(module, "per_row_targets", False)) and labels.shape[0] == coords.shape[0]
-        if self.per_row:
-            self.ignore_index = int(getattr(getattr(module, "criterion", None), "ignore_index", -100))
-            self.labels = torch.full((self.n_cap,) + tuple(labels.shape[1:]), self.ignore_index, dtype=labels.dtype, device=dev)
+        if per_row:
+            self.labels = torch.full((self.n_cap,) + tuple(labels.shape[1:]), self.ignore_index, dtype=labels.dtype,
+                                     device=dev)
         else:
             self.labels = torch.zeros_like(labels)
         self.n_valid = torch.zeros((1,), dtype=torch.int64, device=dev)
+        self.n_events = int(self.n_cap if per_row else labels.shape[0])
         # the coordinates in the reference's batch-first column order, written by the same hand-over launch; the net
         # takes them instead of permuting when it is given exactly self.coords (psd/net.py)
         net = getattr(module, "model", None)
-        if self.per_row and net is not None and hasattr(net, "batch_size_hint"):
-            # the nets read the number of events off the last coordinate row (a host read-back of a padding row here).
-            # All the site tables need is an upper bound, and every event has at least one row: the row capacity is one
-            net.batch_size_hint = self.n_cap
         perm = getattr(net, "permute_tensor", None)
         self._perm = [int(v) for v in perm.tolist()] if perm is not None else None
         self.indices = torch.zeros_like(self.coords) if self._perm is not None else None
+        self.events = None            # event offsets of the loaded batch, when the hand-over launch writes them
+        return net
+
+    def _own_stream(self, dev):
+        # Stream discipline.  (1) Autograd's AccumulateGrad nodes remember the stream they were created on, and a
+        # node born on the legacy default stream cannot take part in a capture.  (2) On ROCm 7.2 ANY eager work on
+        # the legacy default (null) stream between two replays makes the next replay hang.  So the runner moves the
+        # calling thread onto an ordinary stream for good -- calibration, warm-up, capture, replays and whatever
+        # eager work the caller does afterwards (loss.item(), logging, the next batch's copies) all run there.
+        if torch.cuda.current_stream(dev) == torch.cuda.default_stream(dev):
+            st = torch.cuda.Stream(dev)
+            st.wait_stream(torch.cuda.default_stream(dev))
+            torch.cuda.set_stream(st)
+        self.stream = torch.cuda.current_stream(dev)
+
+    def _fresh_flags(self):
+        """Before the calibration step: every module whose captured output can fail takes a new flag store, which this
+        runner's graph alone then writes."""
+        self._owners = [m for m in self.module.modules() if isinstance(m, ops.StickyFlags)]
+        for m in self._owners:
+            m.fresh_sticky_flags()
+
+    def _calibrate(self, factor, slack, granule):
+        """After the calibration step: every module that reports a count gets ``slack x factor x count`` rows of output
+        capacity, rounded up to the granule."""
+        for m in self._owners:
+            count = m.calibration_count()
+            if count is not None:
+                m.out_capacity = _round_up(slack * factor * count, granule)
+
+    def _capture(self, fn):
+        """``fn()`` captured into a new graph on the runner's stream: (graph, what ``fn`` returned)."""
+        graph = torch.cuda.CUDAGraph()
+        # thread_local: the process group's watchdog thread queries events while this thread captures
+        mode = "thread_local" if (dist.is_available() and dist.is_initialized()) else "global"
+        with _no_gc(), torch.cuda.graph(graph, stream=self.stream, capture_error_mode=mode):
+            out = fn()
+        self._graphs.append(graph)
+        return graph, out
+
+    def _collect_flags(self):
+        """After the capture: the flags its graph may set, by kind, and the stores it writes -- the look-back state of the
+        event-local conv builds included, written by every replay -- kept alive for as long as this runner."""
+        self._stores = [m._sticky_flags() for m in self._owners]
+        self._overflow, self._voxel_overflow, self._event_flags = [], [], []
+        for m, store in zip(self._owners, self._stores):
+            if "overflow" in store:
+                (self._voxel_overflow if isinstance(m, Voxelizer) else self._overflow).append(store["overflow"])
+            self._event_flags += [store[k] for k in ("events", "conv_events") if k in store]
+        # the builds only ever SET these (sticky): cleared here (whatever the warm-up left) and after every read, so that
+        # check() sees a failure of ANY replay since the last check()
+        for t in self._overflow + self._voxel_overflow + self._event_flags:
+            t.zero_()
+
+    def check(self):
+        """Synchronises; raises if a replay since the last check() met a batch that was not grouped by event (the
+        event-local builds then leave empty tables) or exceeded a captured capacity.  Clears the flags."""
+        _check_flags(self._overflow, self._voxel_overflow, self._event_flags, self.coords.device)
+
+    def close(self):
+        """Orderly end: the device drains, the captured graphs are destroyed and their memory pools released, the
+        references the net holds to the static buffers are dropped.  Idempotent; the runner cannot be called
+        afterwards."""
+        if self.graph is None:
+            return
+        torch.cuda.synchronize(self.coords.device)
+        for g in self._graphs:
+            g.reset()
+        self.graph, self._graphs = None, []
+        net = getattr(self.module, "model", None)
+        if net is not None:
+            if getattr(net, "batch_events", None) is not None and net.batch_events[0] is self.coords:
+                net.batch_events = None
+            if getattr(net, "batch_first_indices", None) is not None and net.batch_first_indices[0] is self.coords:
+                net.batch_first_indices = None
+        torch.cuda.synchronize(self.coords.device)
+
+    def fits(self, batch):
+        (coords, _f), labels = batch
+        if self.per_row:
+            return coords.shape[0] <= self.n_cap and labels.shape[0] == coords.shape[0]
+        return coords.shape[0] <= self.n_cap and tuple(labels.shape) == tuple(self.labels.shape)
+
+    def _load(self, batch):
+        if torch.cuda.current_stream(self.coords.device) == torch.cuda.default_stream(self.coords.device):
+            torch.cuda.set_stream(self.stream)         # see "Stream discipline" (_own_stream)
+        (coords, feats), labels = batch
+        n = coords.shape[0]
+        if n > self.n_cap:
+            raise RuntimeError("batch has %d voxels, the captured step holds %d" % (n, self.n_cap))
+        if self.per_row:
+            self.coords[:n].copy_(coords, non_blocking=True)
+            self.feats[:n].copy_(feats, non_blocking=True)
+            self.labels.fill_(self.ignore_index)
+            self.labels[:n].copy_(labels, non_blocking=True)
+            self.n_valid.fill_(n)
+            if self.indices is not None:
+                self.indices[:n].copy_(coords[:, self._perm], non_blocking=True)
+            self._event_offsets()
+            return
+        if (coords.is_cuda and coords.dtype == torch.int32 and coords.is_contiguous() and feats.is_cuda
+                and feats.is_contiguous() and feats.dtype == self.feats.dtype and labels.is_cuda
+                and labels.dtype == torch.int64 and labels.is_contiguous() and labels.shape == self.labels.shape):
+            # one launch: coordinates (as they are and batch-first), features, labels, row count
+            lib = _lib.load()
+            perm = _lib.i32_array(self._perm) if self._perm is not None else None
+            ev = self.events if (self.events is not None and perm is not None) else None
+            _lib.check(lib.wfs_load_batch(_lib.ptr(coords), n, coords.shape[1], perm, _lib.ptr(self.coords),
+                                          _lib.ptr(self.indices), _lib.ptr(feats), _lib.ptr(self.feats),
+                                          feats.numel() * feats.element_size(), _lib.ptr(labels), _lib.ptr(self.labels),
+                                          labels.numel(), _lib.ptr(self.n_valid), _lib.ptr(ev), self.n_events,
+                                          _lib.stream_ptr()))
+            if ev is None:
+                self._event_offsets()
+            return
+        self.coords[:n].copy_(coords, non_blocking=True)
+        self.feats[:n].copy_(feats, non_blocking=True)
+        self.labels.copy_(labels, non_blocking=True)
+        self.n_valid.fill_(n)
+        if self.indices is not None:
+            self.indices[:n].copy_(coords[:, self._perm], non_blocking=True)
+        self._event_offsets()
+
+    def _event_offsets(self):
+        """The event offsets of the loaded batch when the hand-over launch did not write them (its own launch)."""
+        if self.events is None:
+            return
+        _lib.check(_lib.load().wfs_event_offsets(_lib.ptr(self.indices), self.indices.shape[0], self.indices.shape[1] - 1,
+                                                 self.n_events, _lib.ptr(self.n_valid), _lib.ptr(self.events),
+                                                 _lib.stream_ptr()))
+
+
+class GraphedTrainStep(_CapturedRunner):
+    def __init__(self, module, optimizer, reducer, example_batch, headroom=None, granule=None, warmup=2, min_rows=0):
+        (coords, feats), labels = example_batch
+        headroom, granule = self._headroom_granule(int(coords.shape[0]), int(labels.shape[0]), headroom, granule)
+        assert labels.is_cuda
+        per_row = bool(getattr(module, "per_row_targets", False)) and labels.shape[0] == coords.shape[0]
+        if per_row:
+            self.ignore_index = int(getattr(getattr(module, "criterion", None), "ignore_index", -100))
+        net = self._static_buffers(module, example_batch, headroom, granule, min_rows, per_row)
+        self.optimizer, self.reducer = optimizer, reducer
+        dev = coords.device
+        if per_row and net is not None and hasattr(net, "batch_size_hint"):
+            # the nets read the number of events off the last coordinate row (a host read-back of a padding row here).
+            # All the site tables need is an upper bound, and every event has at least one row: the row capacity is one
+            net.batch_size_hint = self.n_cap
         # the event offsets the event-local rulebook build starts from (spconv.ops.EVENT_LOCAL) are written by the
         # hand-over launch as well: one graph node fewer at the head of the step
-        from ..spconv import ops as _ops
-        self.n_events = int(self.n_cap if self.per_row else labels.shape[0])
-        self.events = None
-        if (_ops.EVENT_LOCAL and self.indices is not None and 1 <= self.n_events <= _ops.EVENT_LOCAL_MAX_BATCH
+        if (ops.EVENT_LOCAL and self.indices is not None and 1 <= self.n_events <= ops.EVENT_LOCAL_MAX_BATCH
                 and hasattr(net, "batch_events")):
-            from .. import _lib as _l
-            self.events = torch.zeros((int(_l.load().wfs_event_offsets_ints(self.n_events)),), dtype=torch.int32,
+            self.events = torch.zeros((int(_lib.load().wfs_event_offsets_ints(self.n_events)),), dtype=torch.int32,
                                       device=dev)
             net.batch_events = (self.coords, self.events)
         self.world = reducer.world
@@ -106,19 +273,10 @@ class GraphedTrainStep(object):
             self.in_graph_exchange = _collective_capture_works(reducer.group, dev)
         self.exchange_after = exchange and not self.in_graph_exchange
         self.in_graph_optimizer = not self.exchange_after
-        self._convs = [m for m in module.modules()
-                       if hasattr(m, "subm") and hasattr(m, "conv1x1") and not m.subm and not m.conv1x1 and not m.inverse]
-        # Stream discipline.  (1) Autograd's AccumulateGrad nodes remember the stream they were created on, and a
-        # node born on the legacy default stream cannot take part in a capture.  (2) On ROCm 7.2 ANY eager work on
-        # the legacy default (null) stream between two replays makes the next replay hang.  So the runner moves the
-        # calling thread onto an ordinary stream for good -- calibration, warm-up, capture, replays and whatever
-        # eager work the caller does afterwards (loss.item(), logging, the next batch's copies) all run there.
-        if torch.cuda.current_stream(dev) == torch.cuda.default_stream(dev):
-            st = torch.cuda.Stream(dev)
-            st.wait_stream(torch.cuda.default_stream(dev))
-            torch.cuda.set_stream(st)
-        self.stream = torch.cuda.current_stream(dev)
-        # ---- calibration: one ordinary (exact-size) step tells how many rows each strided layer produces
+        self._own_stream(dev)
+        # ---- calibration: one ordinary (exact-size) step tells how many rows each strided layer (and a voxeliser)
+        # produces
+        self._fresh_flags()
         reducer.reset()
         loss = module.training_step(([coords, feats], labels), 0)
         loss.backward()
@@ -133,14 +291,7 @@ class GraphedTrainStep(object):
         # about the outputs-per-input ratio of the strided layers, which varies by a few per cent from batch to
         # batch: they keep 6 % on top (the conv kernels share out the VALID tiles, so this room is nearly free)
         slack = 1.06 if headroom < 1.05 else 1.0
-        for m in self._convs:
-            m.out_capacity = _round_up(slack * factor * m.last_rulebook.M, granule)
-        # other modules with a data-dependent output size (psd/voxel.Voxelizer): the count of the calibration step, the
-        # same headroom and granule; their sticky flags join the strided layers' overflow flags in check()
-        self._sized = _sized_modules(module)
-        for m in self._sized:
-            m.out_capacity = _round_up(slack * factor * m.calibration_count(), granule)
-            m.fresh_sticky_flags()        # this graph's own flags (an eval graph captured later gets others)
+        self._calibrate(factor, slack, granule)
         if self.exchange_after:
             reducer.remove()              # no collectives inside the graph: gradients are exchanged after the replay
         # ---- warm-up in device-count mode, then capture
@@ -166,33 +317,7 @@ class GraphedTrainStep(object):
             self.in_graph_exchange, self.exchange_after, self.in_graph_optimizer = False, True, False
             reducer.remove()
             self._warm_and_capture(warmup)
-        self._overflow = [m.last_rulebook.overflow for m in self._convs if m.last_rulebook.overflow is not None]
-        self._sized_flags = [f for m in self._sized for f in m.sticky_flags()]
-        self._event_flags = _event_flags(module)
-        self._conv_states = _conv_states(module)      # written by every replay: alive for as long as the graph is
-        # the builds only ever SET these (sticky); allocated inside the capture they start undefined: cleared here and
-        # after every read, so that check() sees a failure of ANY replay since the last check()
-        _clear_flags(self._overflow, self._event_flags, self._sized_flags)
-
-    @staticmethod
-    def _headroom_granule(rows, labels, headroom=None, granule=None):
-        if headroom is None and os.environ.get("WFS_CAPTURE_HEADROOM"):
-            headroom = float(os.environ["WFS_CAPTURE_HEADROOM"])          # experiments: tools/exp (capacity is not free)
-        if headroom is None:
-            headroom = max(1.1, 1.0 + 3.0 / max(1.0, float(labels)) ** 0.5)
-        if granule is None:
-            # capacities are rounded up to a granule; padded rows cost real work in the wide-channel (GEMM route) layers
-            # of the 2-D nets, whose batches are a few hundred rows, so the granule follows the batch
-            granule = 512 if rows >= 32768 else (256 if rows >= 2048 else 64)
-        return headroom, granule
-
-    @classmethod
-    def capacity_for(cls, rows, labels):
-        """The row capacity a step captured on a batch of ``rows`` rows and ``labels`` labels gets: ranks that capture
-        together pass the LARGEST row count among them as ``min_rows`` so that they all hold the same capacity (their
-        replay-or-ordinary-step decisions are derived from agreed counts and must come out alike)."""
-        headroom, granule = cls._headroom_granule(int(rows), int(labels))
-        return _round_up(headroom * int(rows), granule)
+        self._collect_flags()
 
     def _warm_and_capture(self, warmup):
         for _ in range(warmup):
@@ -200,33 +325,17 @@ class GraphedTrainStep(object):
             if self.exchange_after:
                 self._after()
         torch.cuda.synchronize()
-        self.graph = torch.cuda.CUDAGraph()
-        # thread_local: the process group's watchdog thread queries events while this thread captures
-        mode = "thread_local" if (dist.is_available() and dist.is_initialized()) else "global"
-        with _no_gc(), torch.cuda.graph(self.graph, stream=self.stream, capture_error_mode=mode):
-            self.loss = self._body()
+        self.graph, self.loss = self._capture(self._body)
 
     def close(self, remove_hooks=True):
         """Orderly end of a captured step, BEFORE its process group is destroyed or another step is captured on the same
-        reducer: the reducer's hooks come off (``remove_hooks=False``: the reducer goes on to serve the next capture), the
-        device drains, the graph (whose nodes include the RCCL kernels and the communicator's stream when the exchange
-        was captured) is destroyed and its memory pool released, the references the net holds to the static buffers are
-        dropped.  Idempotent; the step cannot be called afterwards."""
-        if getattr(self, "graph", None) is None:
-            return
-        if remove_hooks:
+        reducer: the reducer's hooks come off (``remove_hooks=False``: the reducer goes on to serve the next capture),
+        then as _CapturedRunner.close() -- the graph destroyed includes the RCCL kernels and the communicator's stream
+        when the exchange was captured."""
+        if self.graph is not None and remove_hooks:
             self.reducer.remove()
-        torch.cuda.synchronize(self.coords.device)
-        self.graph.reset()
-        self.graph = None
+        super().close()
         self.loss = None
-        net = getattr(self.module, "model", None)
-        if net is not None:
-            if getattr(net, "batch_events", None) is not None and net.batch_events[0] is self.coords:
-                net.batch_events = None
-            if getattr(net, "batch_first_indices", None) is not None and net.batch_first_indices[0] is self.coords:
-                net.batch_first_indices = None
-        torch.cuda.synchronize(self.coords.device)
 
     def _static_batch(self):
         return ([self.coords, self.feats, self.n_valid], self.labels)
@@ -280,12 +389,6 @@ class GraphedTrainStep(object):
         self.optimizer.step()
         return loss.detach()
 
-    def fits(self, batch):
-        (coords, _f), labels = batch
-        if self.per_row:
-            return coords.shape[0] <= self.n_cap and labels.shape[0] == coords.shape[0]
-        return coords.shape[0] <= self.n_cap and tuple(labels.shape) == tuple(self.labels.shape)
-
     def fits_counts(self, rows_max, labels_min, labels_max, rows_ne_labels):
         """``fits`` from the counts the ranks agreed on (ShapeAgreement): the largest row count, the smallest / largest
         label count and whether any rank's batch has a label count other than its row count."""
@@ -293,57 +396,7 @@ class GraphedTrainStep(object):
             return rows_max <= self.n_cap and not rows_ne_labels
         return rows_max <= self.n_cap and labels_min == labels_max == int(self.labels.shape[0])
 
-    def _load(self, batch):
-        (coords, feats), labels = batch
-        n = coords.shape[0]
-        if n > self.n_cap:
-            raise RuntimeError("batch has %d voxels, the captured step holds %d" % (n, self.n_cap))
-        if getattr(self, "per_row", False):
-            self.coords[:n].copy_(coords, non_blocking=True)
-            self.feats[:n].copy_(feats, non_blocking=True)
-            self.labels.fill_(self.ignore_index)
-            self.labels[:n].copy_(labels, non_blocking=True)
-            self.n_valid.fill_(n)
-            if self.indices is not None:
-                self.indices[:n].copy_(coords[:, self._perm], non_blocking=True)
-            self._event_offsets()
-            return
-        if (coords.is_cuda and coords.dtype == torch.int32 and coords.is_contiguous() and feats.is_cuda
-                and feats.is_contiguous() and feats.dtype == self.feats.dtype and labels.is_cuda
-                and labels.dtype == torch.int64 and labels.is_contiguous() and labels.shape == self.labels.shape):
-            # one launch: coordinates (as they are and batch-first), features, labels, row count
-            from .. import _lib
-            lib = _lib.load()
-            perm = _lib.i32_array(self._perm) if self._perm is not None else None
-            ev = self.events if (self.events is not None and perm is not None) else None
-            _lib.check(lib.wfs_load_batch(_lib.ptr(coords), n, coords.shape[1], perm, _lib.ptr(self.coords),
-                                          _lib.ptr(self.indices), _lib.ptr(feats), _lib.ptr(self.feats),
-                                          feats.numel() * feats.element_size(), _lib.ptr(labels), _lib.ptr(self.labels),
-                                          labels.numel(), _lib.ptr(self.n_valid), _lib.ptr(ev), self.n_events,
-                                          _lib.stream_ptr()))
-            if ev is None:
-                self._event_offsets()
-            return
-        self.coords[:n].copy_(coords, non_blocking=True)
-        self.feats[:n].copy_(feats, non_blocking=True)
-        self.labels.copy_(labels, non_blocking=True)
-        self.n_valid.fill_(n)
-        if self.indices is not None:
-            self.indices[:n].copy_(coords[:, self._perm], non_blocking=True)
-        self._event_offsets()
-
-    def _event_offsets(self):
-        """The event offsets of the loaded batch when the hand-over launch did not write them (its own launch)."""
-        if self.events is None:
-            return
-        from .. import _lib
-        _lib.check(_lib.load().wfs_event_offsets(_lib.ptr(self.indices), self.indices.shape[0], self.indices.shape[1] - 1,
-                                                 self.n_events, _lib.ptr(self.n_valid), _lib.ptr(self.events),
-                                                 _lib.stream_ptr()))
-
     def __call__(self, batch):
-        if torch.cuda.current_stream(self.coords.device) == torch.cuda.default_stream(self.coords.device):
-            torch.cuda.set_stream(self.stream)         # see "Stream discipline" in __init__
         self._load(batch)
         if hasattr(self.optimizer, "sync_hyperparameters"):
             self.optimizer.sync_hyperparameters()      # a scheduler's new lr reaches the captured update
@@ -353,25 +406,14 @@ class GraphedTrainStep(object):
         return self.loss
 
     def check(self):
-        """Synchronises; raises if any strided layer produced more rows than its capacity in the last step (or a voxeliser
-        more voxels than its capacity: psd/voxel.Voxelizer, its own message) -- on ANY
-        rank: the flag is all-reduced first, so every rank raises together instead of one rank leaving its peers
-        blocked in the next collective."""
-        flag = _any_set(self._overflow, self.coords.device)
-        vflag = _any_set(getattr(self, "_sized_flags", ()), self.coords.device)
-        evf = _any_event_flag(getattr(self, "_event_flags", ()), self.coords.device)
+        """Synchronises; raises if a replay since the last check() exceeded a capacity (a strided layer's output rows, a
+        voxeliser's voxels: psd/voxel.Voxelizer, its own message) or met a batch that was not grouped by event -- on ANY
+        rank: the flags are all-reduced first, in one collective, so every rank raises together instead of one rank
+        leaving its peers blocked in the next collective."""
+        reduce = None
         if self.world > 1 and dist.is_available() and dist.is_initialized():
-            dist.all_reduce(evf, op=dist.ReduceOp.MAX, group=self.reducer.group)
-        if self.world > 1 and dist.is_available() and dist.is_initialized():
-            dist.all_reduce(flag, op=dist.ReduceOp.MAX, group=self.reducer.group)
-            if getattr(self, "_sized_flags", None):
-                dist.all_reduce(vflag, op=dist.ReduceOp.MAX, group=self.reducer.group)
-        bad_events, overflow = bool(evf.item()), bool(flag.item())
-        voxels = bool(vflag.item()) if getattr(self, "_sized_flags", None) else False
-        _clear_flags(self._overflow, getattr(self, "_event_flags", ()), getattr(self, "_sized_flags", ()))
-        if bad_events:
-            raise RuntimeError(_EVENTS_MESSAGE)
-        _raise_overflow(overflow, voxels)
+            reduce = lambda t: dist.all_reduce(t, op=dist.ReduceOp.MAX, group=self.reducer.group)    # noqa: E731
+        _check_flags(self._overflow, self._voxel_overflow, self._event_flags, self.coords.device, reduce)
 
 
 def _collective_capture_works(group, dev):
@@ -467,74 +509,38 @@ class ShapeAgreement(object):
         return int(r[0]), -int(r[2]), int(r[1]), bool(r[3])
 
 
-def _sized_modules(module):
-    """Modules with a data-dependent output size besides the strided convs (psd/voxel.Voxelizer): a capacity calibrated
-    from ``calibration_count()``, overflow flags from ``sticky_flags()``, new flags per captured graph from
-    ``fresh_sticky_flags()``."""
-    return [m for m in module.modules()
-            if hasattr(m, "calibration_count") and hasattr(m, "sticky_flags") and hasattr(m, "fresh_sticky_flags")]
-
-
-def _any_set(flags, dev):
-    if not flags:
-        return torch.zeros((), dtype=torch.int32, device=dev)
-    return torch.stack([o.reshape(()) for o in flags]).any().to(torch.int32)
-
-
-def _raise_overflow(conv, voxels):
-    if conv and voxels:
-        raise RuntimeError("a batch exceeded the captured voxel capacity AND a sparse conv output exceeded its captured "
-                           "capacity; re-capture with more headroom")
-    if voxels:
-        raise RuntimeError("a batch had more voxels than the captured voxel capacity (psd/voxel.Voxelizer); re-capture "
-                           "with more headroom or on a busier batch")
-    if conv:
-        raise RuntimeError("a sparse conv output exceeded its captured capacity; re-capture with more headroom")
-
-
-def _clear_flags(*groups):
-    for tensors in groups:
-        for t in tensors:
-            t.zero_()
-
-
 _EVENTS_MESSAGE = ("a batch was not grouped by event (or an event exceeded the LDS tables of the event-local rulebook "
                    "build, or held duplicate coordinates); set WFS_EVENT_LOCAL=0 and re-capture")
 
 
-def _any_event_flag(flags, dev):
-    """int32 scalar: 1 if any failure word (the first two thirds of each flag tensor) of the event-local builds is set."""
-    evf = torch.zeros((), dtype=torch.int32, device=dev)
-    for f in flags:
-        evf = evf | f[: 2 * (f.numel() // 3)].any().to(torch.int32)
-    return evf
+def _check_flags(conv, voxels, events, dev, reduce=None):
+    """Reads and clears the sticky flags of a captured runner, then raises if any was set: ``conv`` / ``voxels`` are the
+    capacity flags of strided conv layers / voxelisers, ``events`` those of the event-local builds (a failure is a set
+    word in the first two thirds of each).  ``reduce``: an in-place MAX of the three answers over the ranks."""
+    def any_set(flags):
+        if not flags:
+            return torch.zeros((), dtype=torch.bool, device=dev)
+        return torch.stack([f.any() for f in flags]).any()
+    words = torch.stack([any_set([f[: 2 * (f.numel() // 3)] for f in events]), any_set(conv),
+                         any_set(voxels)]).to(torch.int32)
+    if reduce is not None:
+        reduce(words)
+    bad_events, conv_over, voxel_over = (bool(w) for w in words.tolist())
+    for t in conv + voxels + events:
+        t.zero_()
+    if bad_events:
+        raise RuntimeError(_EVENTS_MESSAGE)
+    if conv_over and voxel_over:
+        raise RuntimeError("a batch exceeded the captured voxel capacity AND a sparse conv output exceeded its captured "
+                           "capacity; re-capture with more headroom")
+    if voxel_over:
+        raise RuntimeError("a batch had more voxels than the captured voxel capacity (psd/voxel.Voxelizer); re-capture "
+                           "with more headroom or on a busier batch")
+    if conv_over:
+        raise RuntimeError("a sparse conv output exceeded its captured capacity; re-capture with more headroom")
 
 
-def _conv_states(module):
-    """The look-back state tensors (epoch + per-event counts) of the module's event-local conv builds: a captured graph
-    writes them on every replay, so its runner keeps them alive."""
-    out, seen = [], set()
-    for m in module.modules():
-        st = getattr(getattr(m, "last_rulebook", None), "conv_state", None)
-        if st is not None and st.data_ptr() not in seen:
-            seen.add(st.data_ptr())
-            out.append(st)
-    return out
-
-
-def _event_flags(module):
-    """Failure flags of the event-local rulebook builds of the module's conv layers (spconv.ops.EVENT_LOCAL)."""
-    out, seen = [], set()
-    for m in module.modules():
-        rb = getattr(m, "last_rulebook", None)
-        f = getattr(rb, "event_flags", None) if rb is not None else None
-        if f is not None and f.data_ptr() not in seen:
-            seen.add(f.data_ptr())
-            out.append(f)
-    return out
-
-
-class GraphedEvalStep(object):
+class GraphedEvalStep(_CapturedRunner):
     """Forward-only counterpart for the inference loops (validation, ``test_step``, the occlusion study): the eval-mode
     forward of ``module.model`` -- rulebook builds included -- captured once over capacity-padded buffers and replayed per
     batch.  ``logits = step(batch)`` returns the STATIC logits tensor (consume it before the next call).
@@ -551,76 +557,38 @@ class GraphedEvalStep(object):
     """
 
     def __init__(self, module, example_batch, headroom=None, granule=None, sweep=False):
-        from ..spconv import ops
         (coords, feats), labels = example_batch
-        assert coords.is_cuda and feats.is_cuda
-        self.module = module
-        dev = coords.device
-        if headroom is None:
-            headroom = max(1.1, 1.0 + 3.0 / max(1.0, float(labels.shape[0])) ** 0.5)
-        if granule is None:
-            n0 = int(coords.shape[0])
-            granule = 512 if n0 >= 32768 else (256 if n0 >= 2048 else 64)
-        self.n_cap = _round_up(headroom * coords.shape[0], granule)
-        self.coords = torch.zeros((self.n_cap, coords.shape[1]), dtype=coords.dtype, device=dev)
-        self.feats = torch.zeros((self.n_cap, feats.shape[1]), dtype=feats.dtype, device=dev)
+        headroom, granule = self._headroom_granule(int(coords.shape[0]), int(labels.shape[0]), headroom, granule)
+        net = self._static_buffers(module, example_batch, headroom, granule)
         self.feats_loaded = torch.zeros_like(self.feats) if sweep else None     # the batch's own features (sweeps)
-        self.labels = torch.zeros_like(labels)
-        self.n_valid = torch.zeros((1,), dtype=torch.int64, device=dev)
-        net = getattr(module, "model", None)
-        perm = getattr(net, "permute_tensor", None)
-        self._perm = [int(v) for v in perm.tolist()] if perm is not None else None
-        self.indices = torch.zeros_like(self.coords) if self._perm is not None else None
-        self._convs = [m for m in module.modules()
-                       if hasattr(m, "subm") and hasattr(m, "conv1x1") and not m.subm and not m.conv1x1 and not m.inverse]
-        if torch.cuda.current_stream(dev) == torch.cuda.default_stream(dev):     # see GraphedTrainStep "Stream discipline"
-            st = torch.cuda.Stream(dev)
-            st.wait_stream(torch.cuda.default_stream(dev))
-            torch.cuda.set_stream(st)
-        self.stream = torch.cuda.current_stream(dev)
-        self.n_events = int(labels.shape[0])
+        self._own_stream(coords.device)
+        self._reuse, self.graph_fwd = None, None
         was_training = module.training
         module.eval()
-        self._reuse = None
         try:
             with torch.no_grad():
                 # calibration: an ordinary exact-size forward tells how many rows each strided layer produces
+                self._fresh_flags()
                 if hasattr(net, "batch_size_hint"):
                     net.batch_size_hint = self.n_events
                 net([coords, feats])
-                for m in self._convs:
-                    m.out_capacity = _round_up(headroom * m.last_rulebook.M, granule)
-                self._sized = _sized_modules(module)
-                for m in self._sized:
-                    # this runner's own capacity (from ITS calibration batch) and flags, as GraphedTrainStep's
-                    m.out_capacity = _round_up(headroom * m.calibration_count(), granule)
-                    m.fresh_sticky_flags()
+                self._calibrate(headroom, 1.0, granule)
                 if self.indices is not None:
                     net.batch_first_indices = (self.coords, self.indices)
                 self._load(example_batch)
                 if sweep:
-                    self._reuse = ops.reuse_rulebooks()          # stays open for the life of this runner
+                    self._reuse = ops.reuse_rulebooks()          # stays open until close()
                     self._reuse.__enter__()
                 for _ in range(2):
                     self._forward()
                 torch.cuda.synchronize()
-                self.graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self.graph, stream=self.stream):
-                    self.logits = self._forward()
-                self._overflow = [m.last_rulebook.overflow for m in self._convs if m.last_rulebook.overflow is not None]
-                self._sized_flags = [f for m in self._sized for f in m.sticky_flags()]
-                self._event_flags = _event_flags(module)
-                self._conv_states = _conv_states(module)
-                # sticky flags allocated inside the capture (see GraphedTrainStep)
-                _clear_flags(self._overflow, self._sized_flags, self._event_flags)
-                self.graph_fwd = None
+                self.graph, self.logits = self._capture(self._forward)
+                self._collect_flags()
                 if sweep:
                     # second capture inside the same reuse context: every rulebook build is a cache hit (same static
                     # index buffers, same geometry) -> a graph of the forward kernels alone
                     before = ops.BUILD_COUNT
-                    self.graph_fwd = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(self.graph_fwd, stream=self.stream):
-                        self.logits_fwd = self._forward()
+                    self.graph_fwd, self.logits_fwd = self._capture(self._forward)
                     assert ops.BUILD_COUNT == before, "the forward-only capture rebuilt a rulebook"
         finally:
             module.train(was_training)
@@ -631,17 +599,7 @@ class GraphedEvalStep(object):
             net.batch_size_hint = self.n_events
         return net([self.coords, self.feats, self.n_valid]).float()
 
-    _load = GraphedTrainStep._load
-    _event_offsets = GraphedTrainStep._event_offsets
-    events = None                 # the forward-only graphs compute their event offsets inside the graph
-
-    def fits(self, batch):
-        (coords, _f), labels = batch
-        return coords.shape[0] <= self.n_cap and tuple(labels.shape) == tuple(self.labels.shape)
-
     def __call__(self, batch, occlude_index=None):
-        if torch.cuda.current_stream(self.coords.device) == torch.cuda.default_stream(self.coords.device):
-            torch.cuda.set_stream(self.stream)
         self._load(batch)
         if self.feats_loaded is not None:
             self.feats_loaded.copy_(self.feats)
@@ -660,20 +618,10 @@ class GraphedEvalStep(object):
         self.graph_fwd.replay()
         return self.logits_fwd
 
-    def check(self):
-        """Synchronises; raises if a replay since the last check() met a batch that was not grouped by event (the
-        event-local builds then leave empty tables: bias-only logits) or exceeded a capacity.  Clears the flags."""
-        dev = self.coords.device
-        conv = bool(self._overflow) and bool(_any_set(self._overflow, dev).item())
-        voxels = bool(self._sized_flags) and bool(_any_set(self._sized_flags, dev).item())
-        bad_events = bool(self._event_flags) and bool(_any_event_flag(self._event_flags, dev).item())
-        if conv or voxels or bad_events:
-            _clear_flags(self._overflow, self._sized_flags, self._event_flags)
-        if bad_events:
-            raise RuntimeError(_EVENTS_MESSAGE)
-        _raise_overflow(conv, voxels)
-
     def close(self):
+        """Leaves the sweep's reuse context, then as _CapturedRunner.close()."""
         if self._reuse is not None:
             self._reuse.__exit__(None, None, None)
             self._reuse = None
+        super().close()
+        self.graph_fwd = None

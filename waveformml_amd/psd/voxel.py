@@ -14,6 +14,7 @@ from torch import nn
 from torch.autograd import Function
 
 from .. import _lib
+from ..spconv import ops
 
 
 class VoxelizeFunction(Function):
@@ -85,47 +86,28 @@ def voxelize(rows, values=None, coords=None, threshold=0.0, batch_size=None, n_v
                                   max(1, int(batch_size)), n_valid, out_capacity, overflow)
 
 
-class Voxelizer(nn.Module):
+class Voxelizer(nn.Module, ops.StickyFlags):
     """The hybrid net's voxeliser: ``threshold`` on the raw rows, and -- once a captured step has calibrated it --
-    ``out_capacity`` voxels in device-count mode.  Exposes the generic capacity hooks psd/graph.py looks for:
-    ``calibration_count()`` (the voxels of the last eager call), ``sticky_flags()`` (its current overflow flag) and
-    ``fresh_sticky_flags()``: a captured graph keeps the flag it was captured with, so every runner (training step,
-    eval step) takes new flags before its capture and reads only its own."""
+    ``out_capacity`` voxels in device-count mode.  Its overflow flag follows the sticky-flag protocol of the conv layers
+    (spconv.ops.StickyFlags): ``calibration_count()`` is the voxel count of the last eager call."""
 
     def __init__(self, threshold=0.0):
         super().__init__()
         self.threshold = float(threshold)
         self.out_capacity = None
         self.last_count = None
-        self._overflow = {}
 
     def calibration_count(self):
         return self.last_count
-
-    def sticky_flags(self):
-        return list(self._overflow.values())
-
-    def fresh_sticky_flags(self):
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("waveformml_amd.psd.voxel: new overflow flags must be made before a graph capture")
-        self._overflow = {}
-
-    def _flag(self, dev):
-        t = self._overflow.get(dev)
-        if t is None:
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("waveformml_amd.psd.voxel: the overflow flag must exist before a graph capture (run "
-                                   "the step once in device-count mode first, as psd/graph.py does)")
-            t = self._overflow[dev] = torch.zeros((1,), dtype=torch.int32, device=dev)
-        return t
 
     def forward(self, rows, values, coords, batch_size, spatial_shape, spconv, n_valid=None):
         if n_valid is None:
             feats, indices, v_dev, events, _ = voxelize(rows, values, coords, self.threshold, batch_size)
             self.last_count = int(indices.shape[0])
         else:
+            flag = ops._sticky_flags(1, rows.device, self._sticky_flags(), "overflow")
             feats, indices, v_dev, events, _ = voxelize(rows, values, coords, self.threshold, batch_size, n_valid,
-                                                        self.out_capacity, self._flag(rows.device))
+                                                        self.out_capacity, flag)
         st = spconv.SparseConvTensor(feats, indices, spatial_shape, batch_size)
         if n_valid is not None:
             st.n_valid = v_dev

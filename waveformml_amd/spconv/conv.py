@@ -14,7 +14,7 @@ from .modules import SparseModule
 from .tensor import IndiceData, SparseConvTensor
 
 
-class SparseConvolution(SparseModule):
+class SparseConvolution(SparseModule, ops.StickyFlags):
     def __init__(self, ndim, in_channels, out_channels, kernel_size=3, stride=1, padding=0, dilation=1,
                  groups=1, bias=True, subm=False, output_padding=0, transposed=False, inverse=False,
                  indice_key=None, fused_bn=False, use_hash=False, algo=None):
@@ -46,13 +46,11 @@ class SparseConvolution(SparseModule):
             self.register_parameter('bias', None)
         self.reset_parameters()
 
-    def _sticky_flags(self):
-        """This layer's store of failure flags that rulebook builds only ever set (ops._sticky_flags): plain tensors kept
-        across steps and graph replays, not parameters or buffers."""
-        store = self.__dict__.get("_flag_store")
-        if store is None:
-            store = self.__dict__["_flag_store"] = {}
-        return store
+    def calibration_count(self):
+        """A strided layer's output rows in its last build (its capacity in a captured step follows them)."""
+        if self.subm or self.conv1x1 or self.inverse:
+            return None
+        return self.last_rulebook.M
 
     def reset_parameters(self):
         init.kaiming_uniform_(self.weight, a=math.sqrt(5))

@@ -293,6 +293,35 @@ def _sticky_flags(n, dev, store=None, name=None):
     return torch.zeros((n,), dtype=torch.int32, device=dev)
 
 
+class StickyFlags(object):
+    """Mixin of a module whose captured output can fail (a capacity exceeded, an event-local build failed): its builds
+    take their sticky flags and state from ``_sticky_flags()``, a store of :func:`_sticky_flags`.  A captured runner
+    (psd/graph.py) calls ``fresh_sticky_flags()`` before its calibration step, so that its graph writes a store of its
+    own: another runner's graph never sets this runner's flags, and no runner reads or clears another's."""
+
+    def _sticky_flags(self):
+        """The current store (plain tensors kept across steps and graph replays, not parameters or buffers)."""
+        store = self.__dict__.get("_flag_store")
+        if store is None:
+            store = self.__dict__["_flag_store"] = {}
+        return store
+
+    def fresh_sticky_flags(self):
+        """A new, empty store; whoever captured a graph on the old one keeps that alive."""
+        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("waveformml_amd: new sticky flags must be made before a graph capture")
+        self.__dict__["_flag_store"] = {}
+
+    def sticky_flags(self):
+        """The failure flags of the current store: the latest tensor of every name but the look-back state."""
+        return [t for k, t in self._sticky_flags().items() if isinstance(k, str) and k != "conv_state"]
+
+    def calibration_count(self):
+        """Output rows of the last ordinary (exact-size) call, for a captured runner to size ``out_capacity`` from; None:
+        the output has no capacity of its own."""
+        return None
+
+
 def build_rulebook(indices, batch_size, spatial_shape, ksize, stride, padding, dilation, subm,
                    known_unique=None, n_dev=None, out_capacity=None, transposed=False, output_padding=None,
                    events=None, flags=None, want_cell_map=True):
