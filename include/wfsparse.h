@@ -527,6 +527,20 @@ int wfs_sgd_step(float *param, const float *grad, float *momentum_buf, int64_t n
                  float momentum, float dampening, float weight_decay, int32_t nesterov, int32_t first_step,
                  void *stream);
 
+/* torch.optim.Adam / AdamW's update (optimizer_class "optim.Adam" / "optim.AdamW", built by
+ * src/engineering/LitPSD.py:60-76) on one flat fp32 parameter buffer of n elements; arithmetic and order of
+ * torch/optim/adam.py _single_tensor_adam with capturable=False (maximize, L2 or decoupled weight decay, lerp of
+ * exp_avg, mul + addcmul of exp_avg_sq, bias corrections in double, amsgrad's running maximum, addcdiv).  Two launches:
+ * a one-thread prologue advances the step and computes the step's coefficients, then the elementwise update.
+ * hyper_dev: device doubles {lr, beta1, beta2, eps, weight_decay}, read by every call so that a scheduler reaches a
+ * captured graph.  step_dev: torch's state["step"] as a device float; the call computes with step + 1 and stores it.
+ * coef_dev: device workspace of WFS_ADAM_COEF_FLOATS floats (4-byte aligned) that the call writes and reads.
+ * max_exp_avg_sq may be NULL when amsgrad == 0.  decoupled != 0 is AdamW.  n == 0 still advances the step. */
+#define WFS_ADAM_COEF_FLOATS 16
+int wfs_adam_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, float *max_exp_avg_sq,
+                  int64_t n, const double *hyper_dev, float *step_dev, float *coef_dev, int32_t amsgrad,
+                  int32_t maximize, int32_t decoupled, void *stream);
+
 /* batch hand-over -------------------------------------------------------------------------------------
  * One launch that places a device-resident batch into the fixed buffers a captured step reads: coords [n, cols]
  * int32 (copied as is to coords_dst and, columns permuted by perm_host, to indices_dst -- the batch-first order the

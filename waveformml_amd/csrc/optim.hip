@@ -50,6 +50,146 @@ extern "C" int wfs_sgd_step(float *param, const float *grad, float *momentum_buf
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// Adam / AdamW on the same flat buffer.  The config's optimizer_class may name torch.optim.Adam or
+// AdamW (LitPSD.configure_optimizers); torch's non-capturable step refuses a graph capture, its capturable one bakes the
+// Python-float lr into the graph and costs ~10 elementwise launches.  Arithmetic and order of torch/optim/adam.py
+// _single_tensor_adam (capturable=False), element by element in fp32 with the scalars rounded as torch rounds them:
+//     g = maximize ? -grad : grad
+//     weight_decay != 0:  decoupled ? p *= (float)(1 - lr * wd)  :  g = g + (float)wd * p
+//     m = lerp(m, g, (float)(1 - beta1))                       (torch's two-branch lerp)
+//     v = v * (float)beta2;  v = v + (float)(1 - beta2) * g * g
+//     t = step + 1;  bc1 = 1 - beta1^t;  bc2s = sqrt(1 - beta2^t)          (double, as torch does on the host)
+//     vmax = amsgrad ? (vm = maximum(vm, v)) : v
+//     p = p + (float)(-lr / bc1) * (m / (sqrt(vmax) / (float)bc2s + (float)eps))
+// lr, betas, eps and weight_decay are read from a device block of doubles, so that a scheduler (ExponentialLR,
+// OneCycleLR's cycled momentum) reaches a replayed graph.  The step count is a device float, torch's state["step"].
+// Two launches: a one-thread prologue reads the step, stores step + 1 and turns t and the doubles into the fp32
+// coefficients above (the double pow() runs once, not per block), then the update reads those coefficients beside its
+// first rows.  The alternative, one launch whose blocks all read the step and whose LAST block out (an atomic ticket)
+// stores step + 1, measured slower (tools/microbench_optim.py, profiles/optim_adam_variants_ab.txt and
+// optim_microbench_update.jsonl): C2 (220 k elements) 6.7 us against 5.4, GEP (1.05 M) 17.3 against 7.9.  The
+// ticket's cost grows with the blocks that finish together (GEP: 10.5 us at 256 blocks, 17.3 at 1022).
+namespace {
+
+struct AdamCoef {
+    float decay, wd, w1, omw1, b2, omb2, bc2s, eps, neg_step;
+    int has_wd;
+};
+static_assert(sizeof(AdamCoef) <= WFS_ADAM_COEF_FLOATS * sizeof(float), "coefficient workspace");
+
+__global__ void __launch_bounds__(64) k_adam_prologue(const double *__restrict__ hp, float *__restrict__ step,
+                                                      AdamCoef *__restrict__ coef) {
+    if (threadIdx.x != 0) return;
+    const float t = *step + 1.f;
+    *step = t;
+    const double lr = hp[0], beta1 = hp[1], beta2 = hp[2], eps = hp[3], wd = hp[4];
+    AdamCoef c;
+    c.has_wd = wd != 0.0;
+    c.decay = (float)(1.0 - lr * wd);
+    c.wd = (float)wd;
+    c.w1 = (float)(1.0 - beta1);
+    c.omw1 = 1.f - c.w1;
+    c.b2 = (float)beta2;
+    c.omb2 = (float)(1.0 - beta2);
+    const double bc1 = 1.0 - pow(beta1, (double)t), bc2 = 1.0 - pow(beta2, (double)t);
+    c.bc2s = (float)sqrt(bc2);
+    c.eps = (float)eps;
+    c.neg_step = (float)(-(lr / bc1));
+    *coef = c;
+}
+
+template <bool AMS>
+__device__ __forceinline__ void adam1(float &p, float g, float &m, float &v, float &vm, const AdamCoef &c, int maximize,
+                                      int decoupled) {
+    if (maximize) g = -g;
+    if (c.has_wd) {
+        if (decoupled)
+            p = p * c.decay;
+        else
+            g = g + c.wd * p;
+    }
+    const float d = g - m;
+    m = c.w1 < 0.5f ? m + c.w1 * d : g - d * c.omw1;
+    v = v * c.b2;
+    v = v + c.omb2 * g * g;
+    float den = v;
+    if (AMS) {
+        vm = (vm > v || vm != vm) ? vm : v;        // torch.maximum: NaN propagates
+        den = vm;
+    }
+    p = p + c.neg_step * (m / (sqrtf(den) / c.bc2s + c.eps));
+}
+
+template <bool AMS>
+__global__ void __launch_bounds__(256) k_adam_step(float *__restrict__ P, const float *__restrict__ G, float *__restrict__ M,
+                                                   float *__restrict__ V, float *__restrict__ VM, long long n, int vec4,
+                                                   const AdamCoef *__restrict__ coef, int maximize, int decoupled) {
+    const AdamCoef c = *coef;
+    const long long tid = (long long)blockIdx.x * 256 + threadIdx.x, nth = (long long)gridDim.x * 256;
+    long long done = 0;
+    if (vec4) {
+        // rows of four; every pointer is 16-byte aligned (checked by the caller)
+        const long long n4 = n >> 2;
+        float4 *P4 = reinterpret_cast<float4 *>(P), *M4 = reinterpret_cast<float4 *>(M);
+        float4 *V4 = reinterpret_cast<float4 *>(V), *VM4 = reinterpret_cast<float4 *>(VM);
+        const float4 *G4 = reinterpret_cast<const float4 *>(G);
+        for (long long i = tid; i < n4; i += nth) {
+            float4 p = P4[i], m = M4[i], v = V4[i], vm = AMS ? VM4[i] : float4{0.f, 0.f, 0.f, 0.f};
+            const float4 g = G4[i];
+            adam1<AMS>(p.x, g.x, m.x, v.x, vm.x, c, maximize, decoupled);
+            adam1<AMS>(p.y, g.y, m.y, v.y, vm.y, c, maximize, decoupled);
+            adam1<AMS>(p.z, g.z, m.z, v.z, vm.z, c, maximize, decoupled);
+            adam1<AMS>(p.w, g.w, m.w, v.w, vm.w, c, maximize, decoupled);
+            P4[i] = p;
+            M4[i] = m;
+            V4[i] = v;
+            if (AMS) VM4[i] = vm;
+        }
+        done = n4 << 2;
+    }
+    // the scalar tail (at most three elements), or everything when a pointer is not 16-byte aligned
+    for (long long i = done + tid; i < n; i += nth) {
+        float p = P[i], m = M[i], v = V[i], vm = AMS ? VM[i] : 0.f;
+        adam1<AMS>(p, G[i], m, v, vm, c, maximize, decoupled);
+        P[i] = p;
+        M[i] = m;
+        V[i] = v;
+        if (AMS) VM[i] = vm;
+    }
+}
+
+}  // namespace
+
+extern "C" int wfs_adam_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, float *max_exp_avg_sq,
+                             int64_t n, const double *hyper_dev, float *step_dev, float *coef_dev, int32_t amsgrad,
+                             int32_t maximize, int32_t decoupled, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    WFS_REQUIRE(n >= 0, WFS_EINVAL, "negative size");
+    WFS_REQUIRE(param && grad && exp_avg && exp_avg_sq && hyper_dev && step_dev && coef_dev, WFS_EINVAL,
+                "NULL device pointer");
+    WFS_REQUIRE(max_exp_avg_sq || !amsgrad, WFS_EINVAL, "amsgrad needs max_exp_avg_sq");
+    WFS_REQUIRE((uintptr_t)coef_dev % 4 == 0, WFS_EINVAL, "unaligned coefficient workspace");
+    AdamCoef *coef = reinterpret_cast<AdamCoef *>(coef_dev);
+    k_adam_prologue<<<dim3(1), dim3(64), 0, stream>>>(hyper_dev, step_dev, coef);
+    WFS_LAUNCH_CHECK();
+    if (n == 0) return WFS_OK;                     // the step count still advances, as torch's does
+    float *vm = amsgrad ? max_exp_avg_sq : nullptr;
+    const bool vec4 = (((uintptr_t)param | (uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq |
+                        (uintptr_t)vm) & 15) == 0;
+    // at most 512 blocks: C5's 28.7 M elements took 154 us at 512, 166 us at 2048 (profiles/optim_adam_variants_ab.txt)
+    long long blocks = wfs_cdiv(vec4 ? wfs_cdiv(n, 4) : n, 256);
+    if (blocks > 512) blocks = 512;
+    if (amsgrad)
+        k_adam_step<true><<<dim3((unsigned)blocks), dim3(256), 0, stream>>>(param, grad, exp_avg, exp_avg_sq, vm, n,
+                                                                            vec4 ? 1 : 0, coef, maximize, decoupled);
+    else
+        k_adam_step<false><<<dim3((unsigned)blocks), dim3(256), 0, stream>>>(param, grad, exp_avg, exp_avg_sq, nullptr, n,
+                                                                             vec4 ? 1 : 0, coef, maximize, decoupled);
+    WFS_LAUNCH_CHECK();
+    return WFS_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // Hand-over of a batch to a captured step in ONE launch: a replayed HIP graph reads its inputs from fixed buffers, so
 // every step starts by copying the batch there -- coordinates, features, labels, the row count -- and the reference's
 // forward then permutes the coordinate columns to batch-first (src/models/SPConvNet.py:64).  Five launches (three

@@ -45,6 +45,15 @@ def _round_up(v, m):
     return int((int(v) + m - 1) // m * m)
 
 
+def steps_in_graph(optimizer):
+    """Can ``optimizer.step()`` be captured into the training graph?  The flat optimizers with a HIP step (psd/optim:
+    FlatSGD, FlatAdam, FlatAdamW) always; torch's own unless a group has ``capturable`` off -- Adam, AdamW, RMSprop,
+    Adagrad ... refuse a capture then (SGD has no such flag).  Those step eagerly after the replay instead."""
+    if getattr(optimizer, "flat_device_step", False):
+        return True
+    return all(g.get("capturable", True) for g in optimizer.param_groups)
+
+
 class _CapturedRunner(object):
     """What the captured runners share: the capacity-padded buffers a batch is copied into, the calling thread's stream,
     capacity calibration, the sticky failure flags their graphs may set (spconv.ops.StickyFlags), check() and close()."""
@@ -261,7 +270,8 @@ class GraphedTrainStep(_CapturedRunner):
         # stream, i.e. a fork off the captured stream right after that bucket's last dW, running beside the rest of
         # the backward -- and reducer.finish() joins them in front of the optimizer launch, which is then back inside
         # the graph too.  Other backends (gloo: the one-GPU rehearsal; host copies cannot be captured) exchange the
-        # packed buffer after the replay, followed by an eager optimizer launch.
+        # packed buffer after the replay, followed by an eager optimizer launch.  So does an optimizer whose step cannot
+        # be captured (steps_in_graph), whatever the exchange.
         exchange = bool(getattr(reducer, "exchange", self.world > 1))
         self.in_graph_exchange = (exchange and dist.is_available() and dist.is_initialized()
                                   and dist.get_backend(reducer.group) == "nccl"
@@ -272,7 +282,7 @@ class GraphedTrainStep(_CapturedRunner):
             # that contained collectives)
             self.in_graph_exchange = _collective_capture_works(reducer.group, dev)
         self.exchange_after = exchange and not self.in_graph_exchange
-        self.in_graph_optimizer = not self.exchange_after
+        self.in_graph_optimizer = not self.exchange_after and steps_in_graph(optimizer)
         self._own_stream(dev)
         # ---- calibration: one ordinary (exact-size) step tells how many rows each strided layer (and a voxeliser)
         # produces
@@ -322,7 +332,7 @@ class GraphedTrainStep(_CapturedRunner):
     def _warm_and_capture(self, warmup):
         for _ in range(warmup):
             self._body()
-            if self.exchange_after:
+            if not self.in_graph_optimizer:
                 self._after()
         torch.cuda.synchronize()
         self.graph, self.loss = self._capture(self._body)
@@ -362,7 +372,10 @@ class GraphedTrainStep(_CapturedRunner):
         return loss.detach()
 
     def _after(self):
-        self.reducer.exchange_packed()
+        """What follows a replay when the graph ends before the optimizer: the exchange (exchange_after), then the
+        optimizer's eager step."""
+        if self.exchange_after:
+            self.reducer.exchange_packed()
         self.optimizer.step()
 
     def eager_step(self, batch):
@@ -401,7 +414,7 @@ class GraphedTrainStep(_CapturedRunner):
         if hasattr(self.optimizer, "sync_hyperparameters"):
             self.optimizer.sync_hyperparameters()      # a scheduler's new lr reaches the captured update
         self.graph.replay()
-        if self.exchange_after:
+        if not self.in_graph_optimizer:
             self._after()
         return self.loss
 

@@ -67,11 +67,17 @@ class LitPSD(nn.Module):
             # one flat tensor: torch's multi-tensor ("foreach") kernels would run it on a handful of blocks (and so
             # does its "fused" SGD: measured 74 us against 19 us for the four single-tensor launches)
             import inspect
-            if opt_class is torch.optim.SGD and all(p.is_cuda for p in self.optimizer_parameters):
+            on_gpu = all(p.is_cuda for p in self.optimizer_parameters)
+            if opt_class is torch.optim.SGD and on_gpu:
                 from .optim import FlatSGD
                 opt_class = FlatSGD               # the whole update in one HIP launch, lr in device memory
-            elif "foreach" in inspect.signature(opt_class.__init__).parameters and "foreach" not in kwargs:
-                kwargs["foreach"] = False
+            else:
+                if opt_class in (torch.optim.Adam, torch.optim.AdamW) and on_gpu:
+                    from .optim import FlatAdam, FlatAdamW
+                    # one HIP launch, hyperparameters in device memory: steps inside a captured graph
+                    opt_class = FlatAdamW if opt_class is torch.optim.AdamW else FlatAdam
+                if "foreach" in inspect.signature(opt_class.__init__).parameters and "foreach" not in kwargs:
+                    kwargs["foreach"] = False
         optimizer = opt_class(params, lr=self.lr, **kwargs)
         if getattr(oc, "scheduler_class", None):
             if not hasattr(oc, "scheduler_params"):
