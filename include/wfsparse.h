@@ -343,6 +343,30 @@ int wfs_scatter_conv(const int32_t *table, int32_t K, int32_t identity_k, int64_
                      int32_t Cx, const float *W, int32_t Cw_in, int32_t Cw_out, int32_t transpose_w,
                      float *Y_accum, int32_t dtype, void *stream);
 
+/* SparseMaxPool2d / 3d (csrc/pool.hip) ---------------------------------------------------------------
+ * Replaces torch.ops.spconv.indice_maxpool / indice_maxpool_backward (spconv 1.2.1 functional.py SparseMaxPoolFunction;
+ * the reference constructs no pool -- SURVEY.md A.5 -- but config strings can name one).  The rulebook is that of a
+ * regular conv of the same geometry (or of a SubM one): the forward gathers through the by-output table, the backward
+ * through the by-input table, as the convolutions do; no atomics, every row written once, fixed summation order.
+ *     forward   Y[r, c]  = max(0, max_k X[table[k, r], c])      -- the output row starts at ZERO, as spconv's does:
+ *                          for rows with negative entries this is NOT the plain maximum.  `x > y` decides, so NaN and
+ *                          -0 never win; Y holds bit patterns of input elements or +0 in every dtype.
+ *     backward  dX[j, c] = sum_k (X[j, c] == Y[o, c]) ? dY[o, c] : 0,  o = table[k, j] >= 0  -- ties all receive the
+ *                          gradient, and so does a 0 under an output that stayed 0; fp32 sums in ascending k, rounded
+ *                          once to the row type.
+ * wfs_maxpool_fwd: table [K, R] by OUTPUT rows (nbr_in; for SubM nbr_out with its mirrored kmap_host -- a maximum does
+ *   not depend on which offset a column stands for, the map only has to be a permutation); X [X_rows, C], Y [R, C].
+ * wfs_maxpool_bwd: table by INPUT rows, dense [K, N] (packed_kl == 0) or the packed [K / packed_kl, N] of
+ *   wfs_event_rulebook_conv when wfs_maxpool_packed_ok says so (same dX bit for bit); X / dX [N, C], Y / dY [M_rows, C].
+ * Any C >= 1: rows of whole 16-byte pieces (C * sizeof(T) % 16 == 0) take vector kernels, every other C scalar ones.
+ * r_dev / n_dev as everywhere: rows beyond the valid count are neither read nor written.  Table entries outside
+ * [0, X_rows) / [0, M_rows) count as "no neighbour" (an overflowed build leaves such entries until its flag is read). */
+int wfs_maxpool_fwd(const int32_t *table, const int32_t *kmap_host, int32_t K, int64_t R, const void *X, int64_t X_rows,
+                    int32_t C, void *Y, int32_t dtype, const int64_t *r_dev, void *stream);
+int wfs_maxpool_packed_ok(int32_t packed_kl, int32_t K, int32_t C, int32_t dtype);
+int wfs_maxpool_bwd(const int32_t *table, int32_t K, int32_t packed_kl, int64_t N, const void *X, const void *Y,
+                    const void *dY, int64_t M_rows, int32_t C, void *dX, int32_t dtype, const int64_t *n_dev, void *stream);
+
 /* BatchNorm1d (+ReLU) over the active rows ------------------------------------------------------
  * What spconv.SparseSequential does with the plain nn.BatchNorm1d / nn.ReLU modules the reference
  * puts after every sparse conv (src/models/SPConvBlocks.py:505-508): applied to .features [N, C],

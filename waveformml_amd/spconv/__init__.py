@@ -13,6 +13,7 @@ from . import functional, ops
 from .conv import (SparseConv1d, SparseConv2d, SparseConv3d, SparseConv4d, SparseConvolution,
                    SparseConvTranspose2d, SparseConvTranspose3d, SparseInverseConv2d, SparseInverseConv3d,
                    SubMConv1d, SubMConv2d, SubMConv3d, SubMConv4d)
+from .pool import SparseMaxPool, SparseMaxPool2d, SparseMaxPool3d
 from .modules import RemoveGrid, SparseModule, SparseSequential, ToDense
 from .tensor import IndiceData, SparseConvTensor
 
@@ -20,5 +21,6 @@ __version__ = "1.2.1+wfsparse"
 
 __all__ = ["SparseConvTensor", "SparseConvolution", "SparseConv1d", "SparseConv2d", "SparseConv3d",
            "SparseConv4d", "SubMConv1d", "SubMConv2d", "SubMConv3d", "SubMConv4d", "SparseInverseConv2d",
-           "SparseInverseConv3d", "SparseConvTranspose2d", "SparseConvTranspose3d", "SparseSequential",
+           "SparseInverseConv3d", "SparseConvTranspose2d", "SparseConvTranspose3d", "SparseMaxPool", "SparseMaxPool2d",
+           "SparseMaxPool3d", "SparseSequential",
            "SparseModule", "ToDense", "RemoveGrid", "ops", "functional", "IndiceData"]

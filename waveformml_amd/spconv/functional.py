@@ -436,6 +436,71 @@ class SparseConvFunction(Function):
         return dX, dW, db, None, None
 
 
+def maxpool_fwd(table, kmap, K, R, X, r_dev=None):
+    """Y[r] = max(0, max_k X[table[k, r]]) through the by-output table (include/wfsparse.h wfs_maxpool_fwd)."""
+    lib = _lib.load()
+    C = int(X.shape[1])
+    assert X.dim() == 2 and table.dtype == torch.int32 and table.shape == (K, R), (X.shape, table.shape, K, R)
+    Y = _rows((R, C), X, r_dev)
+    _lib.check(lib.wfs_maxpool_fwd(_lib.ptr(table), kmap, K, R, _lib.ptr(X), X.shape[0], C, _lib.ptr(Y),
+                                   _lib.dtype_code(X), _lib.ptr(r_dev), _lib.stream_ptr()))
+    _account("maxpool_fwd", table, R, X.shape[0], C, R, C, K, 0, 0, X.element_size())
+    return Y
+
+
+def maxpool_bwd(table, K, packed_kl, N, X, Y, dY, n_dev=None):
+    """dX[j] = sum_k (X[j] == Y[o]) ? dY[o] : 0 with o = table[k, j] through the by-input table, dense or packed
+    (include/wfsparse.h wfs_maxpool_bwd)."""
+    lib = _lib.load()
+    C = int(X.shape[1])
+    assert X.shape[0] == N and Y.shape == dY.shape and Y.shape[1] == C and X.dtype == Y.dtype == dY.dtype
+    assert table.dtype == torch.int32 and table.shape == ((K // packed_kl if packed_kl else K), N), (table.shape, K, N)
+    dX = _rows((N, C), X, n_dev)
+    _lib.check(lib.wfs_maxpool_bwd(_lib.ptr(table), K, packed_kl, N, _lib.ptr(X), _lib.ptr(Y), _lib.ptr(dY), Y.shape[0], C,
+                                   _lib.ptr(dX), _lib.dtype_code(X), _lib.ptr(n_dev), _lib.stream_ptr()))
+    if ACCOUNT is not None:
+        # X read and dX written once each; Y and dY once each; the rulebook at 8 bytes per pair
+        pairs = int(((table >> 3).clamp_(min=-1) if packed_kl else table).ge(0).sum().item())
+        ACCOUNT.append(dict(kind="maxpool_bwd", pairs=pairs, flops=0,
+                            bytes=(2 * N + 2 * Y.shape[0]) * C * X.element_size() + pairs * 8))
+    return dX
+
+
+class SparseMaxPoolFunction(Function):
+    """features [n_in, C] -> [n_out, C]: spconv's indice_maxpool over a rulebook (csrc/pool.hip).  No parameters."""
+
+    @staticmethod
+    def forward(ctx, features, rulebook):
+        rb = rulebook
+        features = _features_ok(features)
+        if rb.has_dup:
+            raise RuntimeError("waveformml_amd.spconv: SparseMaxPool needs distinct input coordinates")
+        assert features.shape[0] == rb.N
+        table, kmap = rb.table_by_out()
+        out = maxpool_fwd(table, kmap, rb.K, rb.M, features, rb.m_dev)
+        ctx.save_for_backward(features, out)
+        ctx.rb = rb
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        features, out = ctx.saved_tensors
+        rb = ctx.rb
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        dY = grad_output.contiguous()
+        if dY.dtype != features.dtype:
+            dY = dY.to(features.dtype)
+        table, pk = rb.nbr_out_packed, rb.packed_kl
+        if table is None or not _lib.load().wfs_maxpool_packed_ok(pk, rb.K, int(features.shape[1]), _lib.dtype_code(features)):
+            table, pk = rb.nbr_out, 0
+        return maxpool_bwd(table, rb.K, pk, rb.N, features, out, dY, rb.n_dev), None
+
+
+def indice_maxpool(features, rulebook):
+    return SparseMaxPoolFunction.apply(features, rulebook)
+
+
 class PointwiseConvFunction(Function):
     """1 x 1 convolution with >= 128 channels on a side: Y = X . W (+ bias) on the matrix cores of
     csrc/wide.hip instead of spconv's ``torch.mm(features, weight.view(in, out))`` (spconv 1.2.1 conv.py; the hybrid

@@ -88,6 +88,7 @@ class SparseSequential(SparseModule):
         branch forks BEFORE it (its output has the input's rows, so nothing on the branch depends on it)."""
         from . import ops
         from .conv import SparseConvolution
+        from .pool import SparseMaxPool
         main = torch.cuda.current_stream()
         side = ops.side_stream(x.features.device)
         side.wait_stream(main)
@@ -123,6 +124,19 @@ class SparseSequential(SparseModule):
                     if not m.subm:
                         indices, spatial, n_dev = rb.out_indices, rb.out_spatial_shape, rb.m_dev
                         events = getattr(rb, "events_out", None)
+                elif isinstance(m, SparseMaxPool) and not m.subm:
+                    # a strided pool's rulebook is a strided conv's: built here, the stack goes on with its output rows
+                    rb = ops.build_rulebook(indices, x.batch_size, spatial, m.kernel_size, m.stride, m.padding,
+                                            m.dilation, False, known_unique=True, n_dev=n_dev,
+                                            out_capacity=getattr(m, "out_capacity", None), events=events,
+                                            flags=m._sticky_flags(),
+                                            want_cell_map=SparseSequential._dense_follows(mods, at))
+                    built.append(rb)
+                    if ops.JOIN_PER_BUILD:
+                        rb.ready = _SideJoin(side)
+                    plan[id(m)] = rb
+                    indices, spatial, n_dev = rb.out_indices, rb.out_spatial_shape, rb.m_dev
+                    events = getattr(rb, "events_out", None)
                 elif isinstance(m, SparseModule):
                     break                           # ToDense or an unknown sparse module ends the sparse stack
             if built and not ops.JOIN_PER_BUILD:
