@@ -500,6 +500,46 @@ int wfs_tcn_bwd(const void *X, const void *dY, int64_t N, int32_t L, const float
 int wfs_tcn_taps_fwd(const void *param_ptrs, int32_t n_conv, int32_t k, float *taps, float *bias, void *stream);
 int wfs_tcn_taps_bwd(const void *param_ptrs, int32_t n_conv, int32_t k, const float *partial, int64_t N, void *stream);
 
+/* multi-channel front end (csrc/tcnc.hip) ----------------------------------------------------------------
+ * TemporalConvNet(c0, channels[0 .. levels-1], kernel_size = k) as the reference's TemporalWaveformNet builds it
+ * (src/models/WaveformModels.py:8-45, TemporalBlock of src/models/ConvBlocks.py:114-152): level i (dilation 2^i) is
+ * drop(relu(conv1)), drop(relu(conv2)), + residual (the 1x1 downsample when its input and output channels differ), relu.
+ * X / Y [N][c0 | channels[levels-1]][L] in `dtype`; fp32 arithmetic.  channels is a HOST array.  Bounds: 1 <= every
+ * channel count <= WFS_TCNC_MAX_CHANNELS, 2 <= k <= WFS_TCNC_MAX_K (k = 1 has no causal padding to chomp), 1 <= levels <= WFS_TCNC_MAX_LEVELS,
+ * 1 <= L <= WFS_TCNC_MAX_L; wfs_tcnc_ok says WFS_OK or WFS_EINVAL (and every entry point refuses the same shapes).
+ * param_ptrs: DEVICE array of wfs_tcnc_n_conv() records of six device addresses {v, g, b, dv, dg, db}, convolutions in
+ * parameter order: per level conv1 (weight_v [cout][cin][k], weight_g [cout], bias [cout]), conv2 (the same with cin =
+ * cout), then the downsample when cin != cout (its weight [cout][cin] as v, g = 0: no weight norm).  A gradient address
+ * 0 is not written.
+ * wfs_tcnc_taps_fwd: effective weights w = g v / |v| (norm over (cin, k) per output channel) into wts
+ *   [wfs_tcnc_weights_floats] fp32 -- one launch, no host round trip.
+ * wfs_tcnc_fwd: Y, and `saved` [wfs_tcnc_saved_floats] fp32 for the backward: per level relu(conv1) and relu(conv2)
+ *   BEFORE dropout, and the level output.
+ * wfs_tcnc_bwd: dX (dtype) from dY (dtype) and `saved`, and d weight_v / weight_g / bias / downsample straight into the
+ *   gradient slots of param_ptrs; workspace [wfs_tcnc_bwd_workspace_floats] fp32.  Deterministic (fixed-order partial
+ *   sums, no atomics).  N >= 1.
+ * Dropout as wfs_tcn_fwd: dropout_p in [0, 1), seed_dev one int64 in device memory; element (row, level, conv, channel,
+ * t) is kept by a counter-based hash of the seed; no mask is stored: wfs_tcnc_fwd's second conv of a level and every
+ * mask pass of wfs_tcnc_bwd rebuild the masks from the same seed (pass the forward's seed and p to the backward).  */
+#define WFS_TCNC_MAX_CHANNELS 32
+#define WFS_TCNC_MAX_K 8
+#define WFS_TCNC_MAX_LEVELS 8
+#define WFS_TCNC_MAX_L 4096
+int wfs_tcnc_ok(int32_t c0, const int32_t *channels, int32_t levels, int32_t k, int32_t L, int32_t dtype);
+int wfs_tcnc_n_conv(int32_t c0, const int32_t *channels, int32_t levels, int32_t k);
+size_t wfs_tcnc_weights_floats(int32_t c0, const int32_t *channels, int32_t levels, int32_t k);
+size_t wfs_tcnc_saved_floats(int64_t N, int32_t L, int32_t c0, const int32_t *channels, int32_t levels);
+size_t wfs_tcnc_bwd_workspace_floats(int64_t N, int32_t L, int32_t c0, const int32_t *channels, int32_t levels,
+                                     int32_t k);
+int wfs_tcnc_taps_fwd(const void *param_ptrs, int32_t c0, const int32_t *channels, int32_t levels, int32_t k,
+                      float *wts, void *stream);
+int wfs_tcnc_fwd(const void *X, int64_t N, int32_t L, int32_t c0, const int32_t *channels, int32_t levels, int32_t k,
+                 const float *wts, float *saved, void *Y, int32_t dtype, float dropout_p, const int64_t *seed_dev,
+                 void *stream);
+int wfs_tcnc_bwd(const void *X, const void *dY, int64_t N, int32_t L, int32_t c0, const int32_t *channels,
+                 int32_t levels, int32_t k, const float *wts, const float *saved, void *dX, float *workspace,
+                 const void *param_ptrs, int32_t dtype, float dropout_p, const int64_t *seed_dev, void *stream);
+
 /* waveform rows -> voxels (csrc/voxelize.hip) ---------------------------------------------------------
  * The hand-over between the front end and a 3-D sparse stack (BASELINE configs[4]: feat [n, 1, 2T] -> TCN -> voxelise ->
  * SubM3d head; the reference's 3-D datasets are voxelised offline, src/datasets/PulseDataset.py:543-625).  Row r of

@@ -110,6 +110,16 @@ SIGNATURES = {
     "wfs_tcn_fwd": (ctypes.c_int, [_vp, _i64, _i32, _vp, _vp, _i32, _i32, _vp, _i32, ctypes.c_float, _vp, _vp]),
     "wfs_tcn_bwd": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _i32, ctypes.c_float, _vp,
                                     _vp]),
+    "wfs_tcnc_ok": (ctypes.c_int, [_i32, c_i32p, _i32, _i32, _i32, _i32]),
+    "wfs_tcnc_n_conv": (ctypes.c_int, [_i32, c_i32p, _i32, _i32]),
+    "wfs_tcnc_weights_floats": (_sz, [_i32, c_i32p, _i32, _i32]),
+    "wfs_tcnc_saved_floats": (_sz, [_i64, _i32, _i32, c_i32p, _i32]),
+    "wfs_tcnc_bwd_workspace_floats": (_sz, [_i64, _i32, _i32, c_i32p, _i32, _i32]),
+    "wfs_tcnc_taps_fwd": (ctypes.c_int, [_vp, _i32, c_i32p, _i32, _i32, _vp, _vp]),
+    "wfs_tcnc_fwd": (ctypes.c_int, [_vp, _i64, _i32, _i32, c_i32p, _i32, _i32, _vp, _vp, _vp, _i32, ctypes.c_float, _vp,
+                                    _vp]),
+    "wfs_tcnc_bwd": (ctypes.c_int, [_vp, _vp, _i64, _i32, _i32, c_i32p, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32,
+                                    ctypes.c_float, _vp, _vp]),
     "wfs_voxelize_offsets_ints": (_sz, [_i64, _i32]),
     "wfs_voxelize_plan": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp, ctypes.c_float, _i32, _i64, _vp, _vp, _vp, _vp, _i32,
                                          _vp]),

@@ -52,6 +52,24 @@ class PulseDataset2D(_ConfigMixin, h5data.PulseDataset2D):
                                label_file_pattern, data_cache_size, use_half)
 
 
+class PulseDatasetWaveformNorm(_ConfigMixin, h5data.PulseDatasetWaveformNorm):
+    """[N, nsamples] pulse rows of ``*PulseNorm.h5`` files, one target row per pulse, ``label_index`` slicing the label
+    columns (reference PulseDataset.py:1128-1178; no normalisation, ranges count rows)."""
+
+    def __init__(self, config, dataset_type, n_per_dir, device, data_name="pulse", file_excludes=None,
+                 label_file_pattern=None, data_cache_size=3, model_dir=None, data_dir=None, dataset_dir=None,
+                 use_half=False, label_index=None, label_name="EZ", additional_fields=None, label_map=None):
+        self.config = config.dataset_config
+        self.dataset_type = dataset_type
+        self.n_paths = self.n_categories = len(self.config.paths)
+        self.use_half = use_half
+        h5data.PulseDatasetWaveformNorm.__init__(self, _dirs(config), n_per_dir, device, data_name=data_name,
+                                                 label_index=label_index, file_excludes=file_excludes,
+                                                 label_name=label_name, label_file_pattern=label_file_pattern,
+                                                 data_cache_size=data_cache_size, use_half=use_half,
+                                                 additional_fields=additional_fields, label_map=label_map)
+
+
 class PulseDataset3D(_ConfigMixin, h5data.PulseDataset3D):
     """[N, 2] rows, N = active (cell, sample) voxels of the item's events (reference PulseDataset.py:582-621)."""
 

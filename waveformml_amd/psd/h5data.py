@@ -343,6 +343,25 @@ class PulseDataset2D(HDF5Dataset):
                          device, batch_index=2, **kw)
 
 
+class PulseDatasetWaveformNorm(HDF5Dataset):
+    """``WaveformNorm`` tables of ``*PulseNorm.h5`` files: one row per PMT pulse, coord ``det`` [1], features
+    ``data_name`` (default ``pulse``) [nsamples], stored normalised (``normalize=False``), no ``nevents``: an item's range
+    counts ROWS (``event_based=False``); ``label_index`` picks label columns (reference src/datasets/PulseDataset.py:
+    1128-1178)."""
+    layout = "pulse"
+
+    def __init__(self, file_paths, n_per_dir, device=None, data_name="pulse", label_index=None, **kw):
+        super().__init__(file_paths, "*PulseNorm.h5", "WaveformNorm", "det", data_name, n_per_dir, device,
+                         normalize=False, event_based=False, **kw)
+        self.label_index = label_index
+
+    def __getitem__(self, idx):
+        val, label = super().__getitem__(idx)
+        if self.label_index is not None:
+            return val, label[:, self.label_index]
+        return val, label
+
+
 class PulseDataset3D(HDF5Dataset):
     """``Waveform3DPairs`` tables of ``*Waveform3DPairSim.h5`` files: coord (x, y, t, evt), waveform [2]
     (reference src/datasets/PulseDataset.py:582-621)."""

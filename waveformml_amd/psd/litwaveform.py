@@ -1,0 +1,169 @@
+"""``LitWaveform``: host-side mirror of the reference's per-pulse module (src/engineering/LitWaveform.py on
+src/engineering/LitBase.py:13-55): one waveform row per PMT pulse, one target per ROW, a mean-reduced criterion
+(``L1Loss``, ``MSELoss`` or ``CrossEntropyLoss``).  As psd/lit.LitPSD, a plain ``nn.Module`` with Lightning's step
+methods; ``configure_optimizers`` is LitPSD's, so FlatSGD / FlatAdam / FlatAdamW take over a flat GPU parameter.
+
+``use_detector_number`` appends the pulse's detector position to its row (n_samples += 3, fill_coords), for the
+308-PMT detector only.  (The reference's error message for another count reads a misspelt attribute and raises
+AttributeError instead of the IOError it builds; here it is the IOError.)
+
+Captured training (psd/graph.GraphedTrainStep, ``per_row_targets``): the batch is padded to a row capacity and the
+step gets the valid row count in device memory.  The loss is then the mean over the valid rows only -- the
+reduction='none' criterion summed under a row mask, divided by the count -- so padding rows add nothing to the loss
+and receive a zero gradient whatever the criterion (``ignore_index`` covers CrossEntropy alone).
+
+Out of scope: TensorEvaluator (and the evaluator plumbing of test_step), ``write_script`` / TorchScript export, and the
+recurrent net (RecurrentWaveformNet; ``squeeze_index`` 2 is kept for it).
+"""
+import logging
+
+import torch
+from torch import nn
+
+from .config import ModuleUtility
+from .lit import LitPSD
+
+
+class LitWaveform(nn.Module):
+    per_row_targets = True            # one target per pulse (row): the captured step pads them per row
+    # Trainer.validate: the captured eval runner (psd/evaluate) scores logits as a classifier; this module validates
+    # through its own validation_step (L1 / MSE have no accuracy: val_acc is NaN)
+    captured_validation = False
+
+    def __init__(self, config, trial=None):
+        super().__init__()
+        nc = config.net_config
+        self.use_detector_number = False
+        if hasattr(nc, "use_detector_number"):
+            self.use_detector_number = nc.use_detector_number
+            if self.use_detector_number:
+                if not hasattr(nc, "num_detectors"):
+                    raise IOError("net config must contain 'num_detectors' property if 'use_detector_number' set to true")
+                config.system_config.n_samples = config.system_config.n_samples + 3
+                self.nx, self.ny = 14, 11
+                if nc.num_detectors == 308:
+                    self.detector_num_factor_x = 1. / (self.nx - 1)
+                    self.detector_num_factor_y = 1. / (self.ny - 1)
+                else:
+                    raise IOError("num detectors " + str(nc.num_detectors) + " not supported")
+        # LitBase (event_predictions=True)
+        self.trial = trial
+        self.pylog = logging.getLogger(__name__)
+        self.config = config
+        self.lr = config.optimize_config.lr
+        self.modules_util = ModuleUtility(nc.imports + config.dataset_config.imports + config.optimize_config.imports)
+        self.model = self.modules_util.retrieve_class(nc.net_class)(config)
+        self.criterion_class = self.modules_util.retrieve_class(nc.criterion_class)
+        self.criterion = self.criterion_class(*nc.criterion_params, reduction="mean")
+        self.write_script = False
+        self.occlude_index = getattr(config.dataset_config, "occlude_index", None)
+        self.optimizer_parameters = None
+        self.logged = {}
+        # LitWaveform
+        self.squeeze_index = 2 if nc.net_class.endswith("RecurrentWaveformNet") else 1
+        dc = config.dataset_config
+        self.test_has_phys = False
+        if hasattr(dc, "test_dataset_params"):
+            if dc.test_dataset_params.label_name == "phys" and not hasattr(dc.test_dataset_params, "label_index"):
+                self.test_has_phys = True
+        self.target_index = dc.dataset_params.label_index if hasattr(dc.dataset_params, "label_index") else None
+        self.use_accuracy = False
+        if nc.criterion_class == "L1Loss":
+            self.metric_name = "mean absolute error"
+        elif nc.criterion_class == "MSELoss":
+            self.metric_name = "mean squared error"
+        elif nc.criterion_class.startswith("BCE") or nc.criterion_class.startswith("CrossEntropy"):
+            self.use_accuracy = True
+            self.metric_name = "Accuracy"
+        else:
+            self.metric_name = "?"
+        self.loss_no_reduce = self.criterion_class(*nc.criterion_params, reduction="none")
+        if self.use_accuracy:
+            self.softmax = nn.Softmax(dim=1)
+
+    configure_optimizers = LitPSD.configure_optimizers
+    log = LitPSD.log
+    log_dict = LitPSD.log_dict
+
+    def forward(self, x):
+        return self.model(x)
+
+    def fill_coords(self, coords, det):
+        """Detector number -> (x, y, end) of the pulse (reference LitWaveform.fill_coords): segment det // 2 on the
+        14 x 11 grid, scaled to [0, 1]; the PMT end det % 2."""
+        seg = torch.floor_divide(det, 2)
+        coords[:, 0] = (seg % 14) * self.detector_num_factor_x
+        coords[:, 1] = torch.floor_divide(seg, 14) * self.detector_num_factor_y
+        coords[:, 2] = det % 2
+
+    def _rows(self, c, f):
+        if self.use_detector_number:
+            det = c.reshape(-1) if c.dim() == 2 and c.shape[1] == 1 else c
+            coords = torch.zeros((f.shape[0], 3), dtype=f.dtype, device=f.device)
+            self.fill_coords(coords, det)
+            f = torch.cat((f, coords), dim=1)
+        return f
+
+    def _predict(self, f, target, phys=False):
+        predictions = self.model(f.unsqueeze(self.squeeze_index)).squeeze(1)
+        if predictions.dim() == 2 and (target.dim() == 1 or (target.dim() == 2 and phys)):
+            predictions = predictions.squeeze(1)
+        if predictions.dtype != torch.float32:
+            predictions = predictions.float()            # 16-bit rows: the criterion in fp32 (LitPSD does the same)
+        return predictions
+
+    def _loss(self, predictions, target, n_valid=None):
+        if predictions.is_cuda:
+            from ..spconv import functional as Fsp
+            if Fsp.can_fuse_cross_entropy(self.criterion, predictions, target):
+                # one HIP launch (LitPSD._loss); the padding rows of a captured batch hold ignore_index (psd/graph.py)
+                return Fsp.cross_entropy_mean(predictions, target, self.criterion.ignore_index)
+        if n_valid is None:
+            return self.criterion.forward(predictions, target)
+        # a capacity-padded batch: the mean over the first n_valid rows, with no host read-back of the count
+        per = self.loss_no_reduce(predictions, target)
+        valid = torch.arange(per.shape[0], device=per.device) < n_valid.reshape(())
+        if per.dim() > 1:
+            valid = valid.reshape((-1,) + (1,) * (per.dim() - 1))
+        count = n_valid.reshape(()).to(per.dtype) * (per[0].numel() if per.dim() > 1 else 1)
+        return torch.where(valid, per, torch.zeros_like(per)).sum() / count
+
+    @staticmethod
+    def _unpack(batch):
+        inputs, target = batch
+        return inputs[0], inputs[1], (inputs[2] if len(inputs) > 2 else None), target
+
+    def training_step(self, batch, batch_idx):
+        c, f, n_valid, target = self._unpack(batch)
+        predictions = self._predict(self._rows(c, f), target)
+        loss = self._loss(predictions, target, n_valid)
+        self.log("train_loss", loss, on_epoch=True, prog_bar=True, logger=True)
+        return loss
+
+    def validation_step(self, batch, batch_idx):
+        c, f, n_valid, target = self._unpack(batch)
+        predictions = self._predict(self._rows(c, f), target)
+        loss = self._loss(predictions, target, n_valid)
+        results = {"val_loss": loss}
+        if self.use_accuracy:
+            pred = torch.argmax(self.softmax(predictions), dim=1)
+            results["val_accuracy"] = (pred == target).float().mean()
+        self.log_dict(results, on_epoch=True, prog_bar=True, logger=True)
+        return results
+
+    def test_step(self, batch, batch_idx):
+        c, f, _n_valid, target = self._unpack(batch)
+        f = self._rows(c, f)
+        if self.occlude_index:                       # falsy for index 0, exactly as the reference
+            f[:, self.occlude_index] = 0
+        predictions = self._predict(f, target, phys=self.test_has_phys)
+        if self.test_has_phys:
+            loss = self.criterion.forward(predictions, target[:, self.target_index])
+        else:
+            loss = self.criterion.forward(predictions, target)
+        results = {"test_loss": loss}
+        if self.use_accuracy:
+            pred = torch.argmax(self.softmax(predictions), dim=1)
+            results["val_accuracy"] = (pred == target).float().mean()     # the reference's key in test_step
+        self.log_dict(results, on_epoch=True, logger=True)
+        return results

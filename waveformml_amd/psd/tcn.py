@@ -9,6 +9,11 @@ wfs_tcn_bwd; csrc/tcn.hip), dropout included (training mode: masks from a counte
 generator -- the same distribution as nn.Dropout, not the same bits).  Same modules, parameters and state_dict as the
 torch composition below, which remains the path for everything else (more channels, CPU tensors, rows too long for the
 LDS-resident backward).
+
+Any other channel plan -- TemporalWaveformNet's ``TemporalConvNet(1, planes, ...)`` -- runs on the multi-channel kernels
+(wfs_tcnc_*, csrc/tcnc.hip) when the module is built with ``fused=True`` (default off: the torch composition, as
+before): weight norm in one launch, two launches per level forward, four per level and one for all weight gradients
+backward.  Plans outside wfs_tcnc_ok's bounds take the torch composition.
 """
 import torch
 from torch import nn
@@ -167,8 +172,75 @@ class FusedNormedTCNFunction(Function):
         return (dx, None, None, None, None) + tuple(grads)
 
 
+TCNC_CALLS = [0]      # forward calls that ran on the multi-channel kernels (tests and tools read it)
+
+
+class FusedMultiTCNFunction(Function):
+    """[N, c0, L] through TemporalConvNet(c0, channels, k) on the multi-channel kernels.  ``params``: per convolution in
+    the order of wfs_tcnc_n_conv (per level conv1, conv2, then the downsample if any) its (weight_v, weight_g, bias) --
+    the downsample's (weight, None, bias).  The backward writes every parameter gradient from ONE launch into the
+    gradient slots (spconv/functional.grad_like)."""
+
+    @staticmethod
+    def forward(ctx, x, c0, channels, k, dropout, seed, cache, *params):
+        lib = _lib.load()
+        x = x.contiguous()
+        N, _c, L = x.shape
+        levels = len(channels)
+        ch = _lib.i32_array(channels)
+        rows = []
+        for c in range(len(params) // 3):
+            v, g, b = params[3 * c: 3 * c + 3]
+            rows.append([v.data_ptr(), g.data_ptr() if g is not None else 0, b.data_ptr() if b is not None else 0, 0, 0, 0])
+        tab = _ptr_table(cache, ("mfwd",) + tuple(x_ for r in rows for x_ in r[:3]), rows, x.device)
+        wts = torch.empty((int(lib.wfs_tcnc_weights_floats(c0, ch, levels, k)),), dtype=torch.float32, device=x.device)
+        saved = torch.empty((int(lib.wfs_tcnc_saved_floats(N, L, c0, ch, levels)),), dtype=torch.float32, device=x.device)
+        y = torch.empty((N, channels[-1], L), dtype=x.dtype, device=x.device)
+        _lib.check(lib.wfs_tcnc_taps_fwd(_lib.ptr(tab), c0, ch, levels, k, _lib.ptr(wts), _lib.stream_ptr()))
+        _lib.check(lib.wfs_tcnc_fwd(_lib.ptr(x), N, L, c0, ch, levels, k, _lib.ptr(wts), _lib.ptr(saved), _lib.ptr(y),
+                                    _lib.dtype_code(x), float(dropout), _lib.ptr(seed), _lib.stream_ptr()))
+        TCNC_CALLS[0] += 1
+        ctx.save_for_backward(x, wts, saved)
+        ctx.params, ctx.plan = params, (c0, tuple(channels), k)
+        ctx.dropout, ctx.seed, ctx.cache = float(dropout), seed, cache
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        from ..spconv.functional import grad_like
+        lib = _lib.load()
+        x, wts, saved = ctx.saved_tensors
+        c0, channels, k = ctx.plan
+        params = ctx.params
+        N, _c, L = x.shape
+        levels = len(channels)
+        ch = _lib.i32_array(channels)
+        dy = grad_output.contiguous()
+        if dy.dtype != x.dtype:
+            dy = dy.to(x.dtype)
+        dx = torch.empty_like(x)
+        grads, rows = [], []
+        for c in range(len(params) // 3):
+            v, g, b = params[3 * c: 3 * c + 3]
+            need = ctx.needs_input_grad[7 + 3 * c: 7 + 3 * c + 3]
+            dv = grad_like(v) if need[0] else None
+            dg = grad_like(g) if (g is not None and need[1]) else None
+            db = grad_like(b) if (b is not None and need[2]) else None
+            grads += [dv, dg, db]
+            rows.append([v.data_ptr(), g.data_ptr() if g is not None else 0, b.data_ptr() if b is not None else 0,
+                         dv.data_ptr() if dv is not None else 0, dg.data_ptr() if dg is not None else 0,
+                         db.data_ptr() if db is not None else 0])
+        tab = _ptr_table(ctx.cache, ("mbwd",) + tuple(x_ for r in rows for x_ in r), rows, x.device)
+        ws = torch.empty((int(lib.wfs_tcnc_bwd_workspace_floats(N, L, c0, ch, levels, k)),), dtype=torch.float32,
+                         device=x.device)
+        _lib.check(lib.wfs_tcnc_bwd(_lib.ptr(x), _lib.ptr(dy), N, L, c0, ch, levels, k, _lib.ptr(wts), _lib.ptr(saved),
+                                    _lib.ptr(dx), _lib.ptr(ws), _lib.ptr(tab), _lib.dtype_code(x), ctx.dropout,
+                                    _lib.ptr(ctx.seed), _lib.stream_ptr()))
+        return (dx, None, None, None, None, None, None) + tuple(grads)
+
+
 class TemporalConvNet(nn.Module):
-    def __init__(self, num_inputs, num_channels, kernel_size=3, dropout=0.2):
+    def __init__(self, num_inputs, num_channels, kernel_size=3, dropout=0.2, fused=False):
         super().__init__()
         blocks = []
         for i, n_out in enumerate(num_channels):
@@ -178,6 +250,48 @@ class TemporalConvNet(nn.Module):
         self.network = nn.Sequential(*blocks)
         self.kernel_size, self.dropout = kernel_size, dropout
         self.single_channel = num_inputs == 1 and all(c == 1 for c in num_channels)
+        # fused=True: any other channel plan runs on the multi-channel kernels (wfs_tcnc_*) where they take it
+        self.fused = bool(fused)
+        self.num_inputs, self.channels = int(num_inputs), [int(c) for c in num_channels]
+
+    def _can_fuse_multi(self, x):
+        """The multi-channel kernels take this call: opted in, GPU rows of a supported dtype, a plan inside
+        wfs_tcnc_ok's bounds, and parameters the kernels read (contiguous fp32 on the GPU)."""
+        if not (self.fused and x.is_cuda and x.dim() == 3 and x.shape[1] == self.num_inputs and x.shape[0] > 0
+                and x.dtype in (torch.float32, torch.bfloat16, torch.float16)):
+            return False
+        if self.training and self.dropout != 0 and not 0.0 <= self.dropout < 1.0:
+            return False
+        lib = _lib.load()
+        if lib.wfs_tcnc_ok(self.num_inputs, _lib.i32_array(self.channels), len(self.channels), self.kernel_size,
+                           int(x.shape[2]), _lib.dtype_code(x)) != _lib.WFS_OK:
+            return False
+        return self._multi_params() is not None
+
+    def _multi_params(self):
+        """(v, g, b) per convolution in the kernels' order; the downsample as (weight, None, bias).  None unless every
+        tensor is contiguous fp32 on the GPU."""
+        out = []
+        for blk in self.network:
+            trip = [(conv.weight_v, conv.weight_g, conv.bias) for conv in blk.convs]
+            if blk.downsample is not None:
+                trip.append((blk.downsample.weight, None, blk.downsample.bias))
+            for t3 in trip:
+                for t in t3:
+                    if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda):
+                        return None
+                out += list(t3)
+        return out
+
+    def _forward_multi(self, x):
+        seed, p = None, 0.0
+        if self.training and self.dropout > 0:
+            seed = torch.randint(-2 ** 62, 2 ** 62, (1,), dtype=torch.int64, device=x.device)
+            p = self.dropout
+        if not hasattr(self, "_ptr_cache"):
+            self._ptr_cache = {}
+        return FusedMultiTCNFunction.apply(x, self.num_inputs, tuple(self.channels), self.kernel_size, p, seed,
+                                           self._ptr_cache, *self._multi_params())
 
     def _can_fuse(self, x):
         levels, k = len(self.network), self.kernel_size
@@ -229,4 +343,6 @@ class TemporalConvNet(nn.Module):
                 if not hasattr(self, "_ptr_cache"):
                     self._ptr_cache = {}
                 return FusedNormedTCNFunction.apply(rows, self.kernel_size, p, seed, self._ptr_cache, *params).reshape(x.shape)
+        if self.fused and not self.single_channel and self._can_fuse_multi(x):
+            return self._forward_multi(x)
         return self.network(x)

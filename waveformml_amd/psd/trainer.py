@@ -392,7 +392,7 @@ class Trainer(object):
 
     @torch.no_grad()
     def validate(self, module, loader):
-        if self.capture and not module.occlude_index:
+        if self.capture and not module.occlude_index and getattr(module, "captured_validation", True):
             # same numbers as validation_step (loss + accuracy of the eval-mode forward), from replays of a captured
             # forward (psd/graph.GraphedEvalStep)
             from .evaluate import test_loop
@@ -405,7 +405,8 @@ class Trainer(object):
             res = module.validation_step(batch, i)
             b = batch[1].shape[0]
             tot += float(res["val_loss"]) * b
-            acc += float(res["val_acc"]) * b
+            # LitWaveform names it val_accuracy (the reference's key), and a regression module has none: NaN
+            acc += float(res.get("val_acc", res.get("val_accuracy", float("nan")))) * b
             n += b
         if _world() > 1:
             # each rank validated its own share of the items: event-weighted sums over all ranks
