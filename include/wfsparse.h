@@ -540,6 +540,48 @@ int wfs_tcnc_bwd(const void *X, const void *dY, int64_t N, int32_t L, int32_t c0
                  int32_t levels, int32_t k, const float *wts, const float *saved, void *dX, float *workspace,
                  const void *param_ptrs, int32_t dtype, float dropout_p, const int64_t *seed_dev, void *stream);
 
+/* recurrent front end (csrc/rnn.hip) ------------------------------------------------------------------------
+ * torch.nn.RNN(I, H, layers, nonlinearity, bias, dropout, bidirectional, batch_first=True) as the reference's
+ * RecurrentNet builds it (src/models/RecurrentBlocks.py): per layer l and direction d (0 forward in t, 1 backward)
+ *   h[t] = act(W_ih in_l[t] + b_ih + W_hh h[t -+ 1] + b_hh), h[start] = 0;  in_0 = X, in_l = drop(out_{l-1}),
+ *   out_l[t] = h[t] of direction 0 then of direction 1;  Y = out_{layers-1}.
+ * X [N][T][I], Y / dY [N][T][dirs H], dX [N][T][I], hidden [layers dirs][N][H] in `dtype`; parameters, arithmetic and
+ * saved state fp32.  Bounds: 1 <= I <= WFS_RNN_MAX_INPUT, 1 <= H <= WFS_RNN_MAX_HIDDEN, 1 <= layers <=
+ * WFS_RNN_MAX_LAYERS, dirs 1 or 2, 1 <= T <= WFS_RNN_MAX_T, nonlinearity WFS_RNN_RELU or WFS_RNN_TANH; wfs_rnn_ok says
+ * WFS_OK or WFS_EINVAL (and every entry point refuses the same shapes).
+ * param_ptrs: DEVICE array of wfs_rnn_n_params() = layers dirs records of eight device addresses
+ *   {w_ih, w_hh, b_ih, b_hh, dw_ih, dw_hh, db_ih, db_hh}, record layer * dirs + d, torch's shapes: w_ih [H][I] (layer 0)
+ *   or [H][dirs H], w_hh [H][H], biases [H] (0: no bias).  A gradient address 0 is not written.
+ * wfs_rnn_fwd: Y, hidden (may be NULL: not written) and `saved` [wfs_rnn_saved_floats] fp32 for the backward -- opaque:
+ *   X and every layer's outputs before dropout, lane-contiguous ([t][channel][N rounded up to 64]).
+ * wfs_rnn_bwd: dX (may be NULL: not computed) from dY and `saved`, and every parameter gradient straight into the
+ *   gradient slots of param_ptrs; workspace [wfs_rnn_bwd_workspace_floats] fp32.  Deterministic (fixed-order partial
+ *   sums, no atomics).  N >= 1.  (The gradient of `hidden` is not an input: hidden is an output for inspection only.)
+ * Dropout: torch's placement -- the outputs of every layer but the last -- with this library's generator: dropout_p in
+ *   [0, 1), seed_dev one int64 in device memory (pass the forward's p and seed to the backward; p = 0 in eval mode).
+ *   Element (row n, layer l, channel c of out_l (c < dirs H <= 64), sample t) has the counter
+ *       ctr = (((n << 3 | l) << 6 | c) << 12) | t
+ *   and z = splitmix64-finaliser(seed + ctr * 0x9E3779B97F4A7C15) (xor-shift 30, * 0xBF58476D1CE4E5B9, xor-shift 27,
+ *   * 0x94D049BB133111EB, xor-shift 31); it is dropped when z >> 32 < (uint32)(p * 2^32), else scaled by the fp32
+ *   1 / (1 - p).  No mask is stored: the next layer's passes and the backward rebuild it from the seed.
+ * Nothing here allocates, synchronises or reads back: every launch goes to `stream` (capturable).  */
+#define WFS_RNN_MAX_INPUT 32
+#define WFS_RNN_MAX_HIDDEN 32
+#define WFS_RNN_MAX_LAYERS 8
+#define WFS_RNN_MAX_T 4096
+#define WFS_RNN_RELU 0
+#define WFS_RNN_TANH 1
+int wfs_rnn_ok(int32_t I, int32_t H, int32_t layers, int32_t dirs, int32_t nonlinearity, int32_t T, int32_t dtype);
+int wfs_rnn_n_params(int32_t layers, int32_t dirs);
+size_t wfs_rnn_saved_floats(int64_t N, int32_t T, int32_t I, int32_t H, int32_t layers, int32_t dirs);
+size_t wfs_rnn_bwd_workspace_floats(int64_t N, int32_t T, int32_t I, int32_t H, int32_t layers, int32_t dirs);
+int wfs_rnn_fwd(const void *X, int64_t N, int32_t T, int32_t I, int32_t H, int32_t layers, int32_t dirs,
+                int32_t nonlinearity, const void *param_ptrs, float *saved, void *Y, void *hidden, int32_t dtype,
+                float dropout_p, const int64_t *seed_dev, void *stream);
+int wfs_rnn_bwd(const void *dY, int64_t N, int32_t T, int32_t I, int32_t H, int32_t layers, int32_t dirs,
+                int32_t nonlinearity, const void *param_ptrs, const float *saved, void *dX, float *workspace,
+                int32_t dtype, float dropout_p, const int64_t *seed_dev, void *stream);
+
 /* waveform rows -> voxels (csrc/voxelize.hip) ---------------------------------------------------------
  * The hand-over between the front end and a 3-D sparse stack (BASELINE configs[4]: feat [n, 1, 2T] -> TCN -> voxelise ->
  * SubM3d head; the reference's 3-D datasets are voxelised offline, src/datasets/PulseDataset.py:543-625).  Row r of

@@ -12,6 +12,7 @@ LIB_PATH = os.environ.get("WFS_LIB") or os.path.join(_HERE, "lib", "libwfsparse.
 WFS_OK, WFS_EINVAL, WFS_EOVERFLOW, WFS_EHIP, WFS_EWORKSPACE = 0, 1, 2, 3, 4
 WFS_F32, WFS_BF16, WFS_F16 = 0, 1, 2
 WFS_MAX_DIM = 4
+WFS_RNN_RELU, WFS_RNN_TANH = 0, 1
 WFS_ABI_VERSION = 6         # include/wfsparse.h: this binding's struct layouts and signatures
 TIMER_GATHER_CONV, TIMER_GATHER_DW, TIMER_RULEBOOK, TIMER_CONV_BACKWARD = 0, 1, 2, 3
 
@@ -120,6 +121,14 @@ SIGNATURES = {
                                     _vp]),
     "wfs_tcnc_bwd": (ctypes.c_int, [_vp, _vp, _i64, _i32, _i32, c_i32p, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32,
                                     ctypes.c_float, _vp, _vp]),
+    "wfs_rnn_ok": (ctypes.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, _i32]),
+    "wfs_rnn_n_params": (ctypes.c_int, [_i32, _i32]),
+    "wfs_rnn_saved_floats": (_sz, [_i64, _i32, _i32, _i32, _i32, _i32]),
+    "wfs_rnn_bwd_workspace_floats": (_sz, [_i64, _i32, _i32, _i32, _i32, _i32]),
+    "wfs_rnn_fwd": (ctypes.c_int, [_vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, ctypes.c_float,
+                                   _vp, _vp]),
+    "wfs_rnn_bwd": (ctypes.c_int, [_vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, ctypes.c_float,
+                                   _vp, _vp]),
     "wfs_voxelize_offsets_ints": (_sz, [_i64, _i32]),
     "wfs_voxelize_plan": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp, ctypes.c_float, _i32, _i64, _vp, _vp, _vp, _vp, _i32,
                                          _vp]),

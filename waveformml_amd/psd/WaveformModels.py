@@ -1,3 +1,4 @@
 """Alias module: ``"net_class": "WaveformModels.TemporalWaveformNet"`` with ``"waveformml_amd.psd.WaveformModels"`` in
-``net_config.imports`` (cf. reference config/examples/SingleWaveformTCN.json)."""
-from .waveform import TemporalWaveformNet  # noqa: F401
+``net_config.imports`` (cf. reference config/examples/SingleWaveformTCN.json); ``WaveformModels.RecurrentWaveformNet`` likewise
+(config/examples/SingleWaveformRNN.json)."""
+from .waveform import RecurrentWaveformNet, TemporalWaveformNet  # noqa: F401

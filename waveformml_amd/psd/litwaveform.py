@@ -12,8 +12,10 @@ step gets the valid row count in device memory.  The loss is then the mean over 
 reduction='none' criterion summed under a row mask, divided by the count -- so padding rows add nothing to the loss
 and receive a zero gradient whatever the criterion (``ignore_index`` covers CrossEntropy alone).
 
-Out of scope: TensorEvaluator (and the evaluator plumbing of test_step), ``write_script`` / TorchScript export, and the
-recurrent net (RecurrentWaveformNet; ``squeeze_index`` 2 is kept for it).
+``net_class`` ``WaveformModels.RecurrentWaveformNet`` gets its rows as [N, n_samples, 1] (``squeeze_index`` 2), every
+other net as [N, 1, n_samples].
+
+Out of scope: TensorEvaluator (and the evaluator plumbing of test_step) and ``write_script`` / TorchScript export.
 """
 import logging
 

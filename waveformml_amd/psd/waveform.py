@@ -5,6 +5,10 @@
 The TCN is psd/tcn.TemporalConvNet with ``fused=True``: its multi-channel plans run on the wfs_tcnc_* kernels
 (csrc/tcnc.hip); the linear head runs through spconv.functional.head_forward (skinny / wide HIP linears).  Same
 modules, parameters and state_dict as the reference's net.
+
+``RecurrentWaveformNet`` (WaveformModels.py:93-110): [N, n_samples, 1] -> psd/recurrent.RecurrentNet(n_samples, 1, n_hidden,
+n_layers, n_lin, out_size, **rnn_params) with ``fused=True``: the Elman RNN runs on the wfs_rnn_* scan kernels
+(csrc/rnn.hip), the linear head as above.
 """
 import logging
 
@@ -12,6 +16,7 @@ from torch import nn
 
 from .blocks import LinearBlock
 from .config import DictionaryUtility
+from .recurrent import RecurrentNet
 from .tcn import TemporalConvNet
 
 
@@ -51,3 +56,21 @@ class TemporalWaveformNet(nn.Module):
             x = self.flatten(x)
             x = head_forward(x, self.linear)
         return x
+
+
+class RecurrentWaveformNet(nn.Module):
+    def __init__(self, config):
+        super().__init__()
+        self.log = logging.getLogger(__name__)
+        self.system_config = config.system_config
+        self.net_config = config.net_config
+        self.nsamples = self.system_config.n_samples
+        hp = self.net_config.hparams
+        if config.net_config.net_type == "RNN":
+            self.model = RecurrentNet(self.nsamples, 1, hp.n_hidden, hp.n_layers, hp.n_lin, hp.out_size, fused=True,
+                                      **DictionaryUtility.to_dict(hp.rnn_params))
+        else:
+            raise IOError("{} not supported net type".format(config.net_config.net_type))
+
+    def forward(self, x):
+        return self.model(x)
