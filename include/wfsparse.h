@@ -468,6 +468,16 @@ int wfs_head_bwd(const void *X, const float *G, int64_t B, int64_t I, const floa
                  wfs_dw_job *defer, void *stream);
 
 
+/* dropout generator (the three waveform front ends below; csrc/wfs_rows.h) ------------------------------------
+ * dropout_p in [0, 1) and seed_dev = one int64 in DEVICE memory (drawn by the caller, e.g. torch.randint, so that a
+ * captured graph gets a fresh seed per replay).  Every element that a front end drops out has a 64-bit counter ctr,
+ * unique per element (the layout is given with each front end), and
+ *     z = splitmix64-finaliser(seed + ctr * 0x9E3779B97F4A7C15)
+ * (xor-shift 30, * 0xBF58476D1CE4E5B9, xor-shift 27, * 0x94D049BB133111EB, xor-shift 31); the element is dropped when
+ * z >> 32 < (uint32)(p * 2^32), else scaled by the fp32 1 / (1 - p).  No mask is stored: every later pass, the backward's
+ * included, rebuilds it from the seed (pass the forward's p and seed to the backward).  dropout_p == 0 (seed_dev may be
+ * NULL) is the eval-mode identity.  Same distribution as nn.Dropout, not the same bits. */
+
 /* hybrid front end -----------------------------------------------------------------------------------
  * TemporalConvNet(1, [1] * levels, kernel_size = k) as the reference's SPConvNet applies it to the waveform rows
  * before the sparse stack (src/models/SPConvNet.py:56-61,83-92; src/models/ConvBlocks.py:114-173): per level i two
@@ -477,11 +487,9 @@ int wfs_head_bwd(const void *X, const float *G, int64_t B, int64_t I, const floa
  * L <= 4096; the backward needs wfs_tcn_lds_bytes(L, levels, 1) <= 150 KiB (else WFS_EINVAL: use another path).
  * wfs_tcn_bwd writes per-row partial sums partial[N][levels][2][k + 1] (taps, then the bias); their sum over rows is
  * d loss / d (taps, bias).
- * Dropout (the nn.Dropout(p) after each of a level's two ReLUs, ConvBlocks.py:125-134): dropout_p in [0, 1) and
- * seed_dev = one int64 in DEVICE memory (drawn by the caller, e.g. torch.randint, so that a captured graph gets a
- * fresh seed per replay).  Kept elements are scaled by 1 / (1 - p); the decision for element (row, level, conv, t)
- * is a counter-based hash of the seed, so the backward pass reproduces the forward's masks from the same seed and
- * nothing is stored.  dropout_p == 0 (seed_dev may be NULL) is the eval-mode identity. */
+ * Dropout (the nn.Dropout(p) after each of a level's two ReLUs, ConvBlocks.py:125-134): the dropout generator above;
+ * element (row n, conv c = 2 * level + {0, 1} (c < 2^4), sample t (t < 2^12)) has the counter
+ *     ctr = n << 16 | c << 12 | t                                                                        */
 size_t wfs_tcn_lds_bytes(int32_t L, int32_t levels, int32_t backward);
 
 int wfs_tcn_fwd(const void *X, int64_t N, int32_t L, const float *taps, const float *bias, int32_t levels,
@@ -518,9 +526,10 @@ int wfs_tcn_taps_bwd(const void *param_ptrs, int32_t n_conv, int32_t k, const fl
  * wfs_tcnc_bwd: dX (dtype) from dY (dtype) and `saved`, and d weight_v / weight_g / bias / downsample straight into the
  *   gradient slots of param_ptrs; workspace [wfs_tcnc_bwd_workspace_floats] fp32.  Deterministic (fixed-order partial
  *   sums, no atomics).  N >= 1.
- * Dropout as wfs_tcn_fwd: dropout_p in [0, 1), seed_dev one int64 in device memory; element (row, level, conv, channel,
- * t) is kept by a counter-based hash of the seed; no mask is stored: wfs_tcnc_fwd's second conv of a level and every
- * mask pass of wfs_tcnc_bwd rebuild the masks from the same seed (pass the forward's seed and p to the backward).  */
+ * Dropout: the dropout generator above, after each of a level's two ReLUs; element (row n, conv c = 2 * level + {0, 1},
+ * channel ch of that conv's output (ch < 2^5), sample t) has the counter
+ *     ctr = (((n << 4 | c) << 5 | ch) << 12) | t
+ * wfs_tcnc_fwd's second conv of a level and every mask pass of wfs_tcnc_bwd rebuild the masks from the seed.  */
 #define WFS_TCNC_MAX_CHANNELS 32
 #define WFS_TCNC_MAX_K 8
 #define WFS_TCNC_MAX_LEVELS 8
@@ -557,13 +566,10 @@ int wfs_tcnc_bwd(const void *X, const void *dY, int64_t N, int32_t L, int32_t c0
  * wfs_rnn_bwd: dX (may be NULL: not computed) from dY and `saved`, and every parameter gradient straight into the
  *   gradient slots of param_ptrs; workspace [wfs_rnn_bwd_workspace_floats] fp32.  Deterministic (fixed-order partial
  *   sums, no atomics).  N >= 1.  (The gradient of `hidden` is not an input: hidden is an output for inspection only.)
- * Dropout: torch's placement -- the outputs of every layer but the last -- with this library's generator: dropout_p in
- *   [0, 1), seed_dev one int64 in device memory (pass the forward's p and seed to the backward; p = 0 in eval mode).
- *   Element (row n, layer l, channel c of out_l (c < dirs H <= 64), sample t) has the counter
+ * Dropout: torch's placement -- the outputs of every layer but the last -- with the dropout generator above (p = 0 in
+ *   eval mode); element (row n, layer l, channel c of out_l (c < dirs H <= 64), sample t) has the counter
  *       ctr = (((n << 3 | l) << 6 | c) << 12) | t
- *   and z = splitmix64-finaliser(seed + ctr * 0x9E3779B97F4A7C15) (xor-shift 30, * 0xBF58476D1CE4E5B9, xor-shift 27,
- *   * 0x94D049BB133111EB, xor-shift 31); it is dropped when z >> 32 < (uint32)(p * 2^32), else scaled by the fp32
- *   1 / (1 - p).  No mask is stored: the next layer's passes and the backward rebuild it from the seed.
+ *   The next layer's passes and the backward rebuild the mask from the seed.
  * Nothing here allocates, synchronises or reads back: every launch goes to `stream` (capturable).  */
 #define WFS_RNN_MAX_INPUT 32
 #define WFS_RNN_MAX_HIDDEN 32

@@ -8,22 +8,17 @@ Measured on an MI355X (worst tensor of a case, error over the tensor's max): fp3
 5.6e-7, 16384 rows 4.2e-7 (the table is in DESIGN.md section 4, "Elman RNN").
 """
 import copy
-import json
 import math
-import os
 
 import numpy as np
 import pytest
 import torch
 
+import waveform_cases as wc
 from recurrent_cases import CASES, assert_live, case_id, make_inputs, make_rnn, run_torch
+from waveform_cases import DEV, TOL, max_err as _err
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEV = "cuda:0"
-# the project's bars (tests/test_gpu_parity.py): fp32 within 1e-5 of each tensor's max magnitude; 16-bit rows on the
-# same rounded inputs within 2e-2 (bf16) / 3e-3 (fp16)
-TOL = {torch.float32: 1e-5, torch.bfloat16: 2e-2, torch.float16: 3e-3}
 
 
 def _block(rnn, case, dropout=0.0):
@@ -33,11 +28,6 @@ def _block(rnn, case, dropout=0.0):
     blk = RecurrentBlock(I, H, layers, nonlinearity=nonlin, bias=bias, dropout=dropout, bidirectional=dirs == 2, fused=True)
     blk.rnn.load_state_dict(rnn.state_dict())
     return blk.to(DEV)
-
-
-def _err(a, ref):
-    a, ref = a.detach().double().cpu(), ref.detach().double().cpu()
-    return float((a - ref).abs().max()), float(ref.abs().max())
 
 
 def _run_fused(blk, x, dy):
@@ -90,9 +80,6 @@ def test_forward_dx_and_parameter_gradients_against_float64(case, dtype):
     _compare("%s %s" % (case_id(case), dtype), [("hidden", hidden)], [("hidden", href)], [("hidden", h32)], dtype)
 
 
-_M64 = (1 << 64) - 1
-
-
 def _hash_masks(seed, p, N, C, T, layer):
     """The kernels' dropout multipliers of layer `layer`'s outputs, [N, T, C] in float64, from the documented scheme
     (include/wfsparse.h, recurrent front end): splitmix64 finaliser over seed + counter * golden ratio, counter =
@@ -101,16 +88,7 @@ def _hash_masks(seed, p, N, C, T, layer):
     row = np.arange(N, dtype=np.uint64)[:, None, None]
     t = np.arange(T, dtype=np.uint64)[None, :, None]
     ch = np.arange(C, dtype=np.uint64)[None, None, :]
-    ctr = ((((row << np.uint64(3)) | np.uint64(layer)) << np.uint64(6) | ch) << np.uint64(12)) | t
-    with np.errstate(over="ignore"):
-        z = np.uint64(seed & _M64) + ctr * np.uint64(0x9E3779B97F4A7C15)
-        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
-        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
-        z = z ^ (z >> np.uint64(31))
-    th = float(np.float32(p)) * 4294967296.0
-    thr = 0xFFFFFFFF if th >= 4294967295.0 else int(th)
-    scale = float(np.float32(1.0) / (np.float32(1.0) - np.float32(p)))
-    return torch.from_numpy(np.where((z >> np.uint64(32)) < np.uint64(thr), 0.0, scale))
+    return wc.hash_masks(seed, p, ((((row << np.uint64(3)) | np.uint64(layer)) << np.uint64(6) | ch) << np.uint64(12)) | t)
 
 
 def _elman(rnn, x, masks, dtype=torch.float64):
@@ -236,156 +214,40 @@ def test_bounds_take_the_torch_module_and_the_flag_off_never_calls_the_kernels()
     assert not recurrent.RecurrentBlock(1, 4, 4).fused and not recurrent.RecurrentNet(59, 1, 4, 4, 4, 1).rnn_block.fused
 
 
-def _config(criterion="L1Loss", detector=False, n_samples=59):
-    with open(os.path.join(ROOT, "config", "waveform_rnn_z.json")) as f:
-        cfg = json.load(f)
-    cfg["system_config"]["n_samples"] = n_samples
-    cfg["net_config"]["criterion_class"] = criterion
-    if criterion.startswith("CrossEntropy"):
-        cfg["net_config"]["hparams"]["out_size"] = 2
-    if detector:
-        cfg["net_config"]["use_detector_number"] = True
-        cfg["net_config"]["num_detectors"] = 308
-    cfg["optimize_config"].pop("scheduler_class", None)
-    return cfg
-
-
-def _lit(cfg, seed=7):
-    """LitWaveform with live parameters: the RNN by the cases' recipe (the default init of a 4-unit bias-free ReLU net
-    can be dead), the head N(0, 0.5^2) scaled by its fan-in."""
-    from waveformml_amd.psd.config import DictionaryUtility
-    from waveformml_amd.psd.litwaveform import LitWaveform
-    torch.manual_seed(seed)
-    m = LitWaveform(DictionaryUtility.to_object(copy.deepcopy(cfg)))
+def _reinit(m, cfg, seed):
+    """Live parameters: the RNN by the cases' recipe (the default init of a 4-unit bias-free ReLU net can be dead), the
+    head N(0, 0.5^2) scaled by its fan-in."""
     hp = cfg["net_config"]["hparams"]
     src = make_rnn((m.model.nsamples, 1, hp["n_hidden"], hp["n_layers"], 1, "relu", False), seed=seed)
     m.model.model.rnn_block.rnn.load_state_dict(src.state_dict())
     with torch.no_grad():
         for p in m.model.model.linear.parameters():
             p.copy_(torch.randn_like(p) * (0.5 / math.sqrt(p.shape[-1]) if p.dim() > 1 else 0.5))
-    return m
 
 
-def _batch(n, L, criterion, seed, dev="cpu"):
-    g = torch.Generator().manual_seed(seed)
-    c = torch.randint(0, 616, (n, 1), generator=g, dtype=torch.int32)
-    f = torch.rand(n, L, generator=g)
-    y = torch.randint(0, 2, (n,), generator=g) if criterion.startswith("CrossEntropy") else torch.rand(n, generator=g)
-    return ([c.to(dev), f.to(dev)], y.to(dev))
+def _rnn_calls():
+    from waveformml_amd.psd import recurrent
+    return recurrent.RNN_CALLS[0]
+
+
+LIT = wc.LitCase("waveform_rnn_z.json", _rnn_calls, _reinit)
 
 
 @pytest.mark.parametrize("detector", [False, True], ids=["rows", "detector"])
 @pytest.mark.parametrize("criterion", ["L1Loss", "CrossEntropyLoss"])
 def test_lit_waveform_one_training_step_against_the_cpu_module(criterion, detector):
-    from waveformml_amd.psd import recurrent
-    cfg = _config(criterion, detector)
-    gpu = _lit(cfg)
-    cpu = _lit(cfg)
-    cpu.load_state_dict(gpu.state_dict())
-    assert gpu.model.nsamples == (62 if detector else 59) and gpu.squeeze_index == 2
-    gpu = gpu.to(DEV).train()
-    cpu.train()
-    b = _batch(500, 59, criterion, seed=3)
-    before = recurrent.RNN_CALLS[0]
-    lg = gpu.training_step(([b[0][0].to(DEV), b[0][1].to(DEV)], b[1].to(DEV)), 0)
-    assert recurrent.RNN_CALLS[0] == before + 1
-    lc = cpu.training_step(b, 0)
-    print("%s detector=%s: loss gpu %.8f cpu %.8f" % (criterion, detector, lg.item(), lc.item()))
-    assert abs(lg.item() - lc.item()) <= 1e-5 * abs(lc.item())
-    lg.backward()
-    lc.backward()
-    for (n, a), p in zip(gpu.model.named_parameters(), cpu.model.parameters()):
-        err, scale = _err(a.grad, p.grad)
-        assert scale > 0 and err <= 1e-4 * scale, (n, err, scale)
-
-
-def _module(cfg, seed=7):
-    from waveformml_amd.psd.ddp import FlatGradAllReducer
-    mod = _lit(cfg, seed).to(DEV)
-    red = FlatGradAllReducer(mod.model.parameters(), world_size=1)
-    mod.optimizer_parameters = red.optimizer_parameters()
-    opt = mod.configure_optimizers()
-    return mod, red, opt
-
-
-def _eager_step(mod, red, opt, batch):
-    red.reset()
-    loss = mod.training_step(batch, 0)
-    loss.backward()
-    red.finish()
-    opt.step()
-    return float(loss)
+    gpu, errs = wc.check_one_training_step_against_the_cpu_module(LIT, criterion, detector)
+    assert gpu.squeeze_index == 2
+    for n, _err_n, scale in errs:
+        assert scale > 0, n
 
 
 @pytest.mark.parametrize("criterion", ["L1Loss", "CrossEntropyLoss"])
 def test_captured_step_matches_the_eager_step_on_padded_batches(criterion):
-    """Batches with FEWER rows than the captured capacity: the padding rows must add nothing to the loss and nothing to
-    any gradient; the holder's parameters, re-pointed into the flat buffer, are the ones the kernels read (the flat
-    parameters move with every step)."""
-    from waveformml_amd.psd import recurrent
-    from waveformml_amd.psd.graph import GraphedTrainStep
-    cfg = _config(criterion)
-    batches = [_batch(n, 59, criterion, seed=40 + n, dev=DEV) for n in (200, 150, 233, 180)]
-    mod_g, red_g, opt_g = _module(cfg)
-    mod_e, red_e, opt_e = _module(cfg)
-    assert torch.equal(red_g.flat_param, red_e.flat_param)
-    w = mod_g.model.model.rnn_block.rnn.weight_hh_l0
-    lo, hi = red_g.flat_param.data_ptr(), red_g.flat_param.data_ptr() + 4 * red_g.flat_param.numel()
-    assert lo <= w.data_ptr() < hi                            # the holder's parameter lives in the flat buffer
-    start = red_g.flat_param.clone()
-    calls = recurrent.RNN_CALLS[0]
-    step = GraphedTrainStep(mod_g, opt_g, red_g, batches[0], warmup=2)
-    assert recurrent.RNN_CALLS[0] > calls                     # the fused path was what got captured
-    assert step.per_row and step.n_cap > 233
-    for _ in range(3):                                       # the calibration step and the two warm-up steps
-        _eager_step(mod_e, red_e, opt_e, batches[0])
-    scale = float(red_e.flat_param.abs().max())
-    assert float((red_e.flat_param - start).abs().max()) > 0
-    assert float((red_g.flat_param - red_e.flat_param).abs().max()) <= 2e-5 * scale
-    for b in batches[1:]:
-        lg = float(step(b))
-        le = _eager_step(mod_e, red_e, opt_e, b)
-        print("%s rows %d of %d: loss captured %.8f eager %.8f" % (criterion, b[1].shape[0], step.n_cap, lg, le))
-        assert abs(lg - le) <= 1e-5 * abs(le), (lg, le)
-        assert float((red_g.flat_param - red_e.flat_param).abs().max()) <= 2e-5 * scale
-    step.check()
-    step.close()
+    wc.check_captured_step_matches_the_eager_step_on_padded_batches(LIT, criterion)
 
 
 @pytest.mark.parametrize("label_index", [0, 1, 2])
 def test_trainer_captured_from_files_and_resume(label_index, tmp_path):
-    from waveformml_amd.psd.config import DictionaryUtility
-    from waveformml_amd.psd.litwaveform import LitWaveform
-    from waveformml_amd.psd.PSDDataModule import PSDDataModule
-    from waveformml_amd.psd.trainer import Trainer
-    with open(os.path.join(ROOT, "config", "waveform_rnn_z.json")) as f:
-        cfg = json.load(f)
-    cfg["system_config"]["n_samples"] = 12                  # the fixture's pulses are 12 samples long
-    dc = cfg["dataset_config"]
-    dc["base_path"] = os.path.join(ROOT, "tests", "golden", "h5", "r3")
-    dc["paths"] = ["pulses"]
-    dc["dataset_params"]["label_index"] = label_index
-    dc["n_train"] = 23
-    conf = DictionaryUtility.to_object(copy.deepcopy(cfg))
-    torch.manual_seed(2)
-    module = LitWaveform(conf)
-    loader = PSDDataModule(conf, DEV).train_dataloader()
-    trainer = Trainer(max_epochs=2, device=DEV, capture=True, default_root_dir=str(tmp_path))
-    hist = trainer.fit(module, loader, loader)
-    assert len(hist) == 2 and all(math.isfinite(h["train_loss"]) and math.isfinite(h["val_loss"]) for h in hist)
-    path = trainer.last_checkpoint
-    ck = torch.load(path, map_location="cpu", weights_only=True)
+    ck, _moms = wc.check_trainer_captured_from_files_and_resume(LIT, label_index, tmp_path)
     assert "model.model.rnn_block.rnn.weight_hh_l3" in ck["state_dict"]
-    moms = [t for st in ck["optimizer_states"][0]["state"].values() for t in st.values() if torch.is_tensor(t) and t.numel() > 1]
-    assert moms                                             # the run's own optimizer state (FlatSGD momentum)
-    # resume with no epoch left: the weights are exactly the saved ones
-    module2 = LitWaveform(DictionaryUtility.to_object(copy.deepcopy(cfg)))
-    t2 = Trainer(max_epochs=int(ck["epoch"]) + 1, device=DEV, capture=True, resume_from_checkpoint=path)
-    assert t2.fit(module2, loader) == []
-    for k, v in module2.state_dict().items():
-        assert torch.equal(v.cpu(), ck["state_dict"][k]), k
-    # ... and one more epoch trains on from them
-    module3 = LitWaveform(DictionaryUtility.to_object(copy.deepcopy(cfg)))
-    t3 = Trainer(max_epochs=int(ck["epoch"]) + 2, device=DEV, capture=True, resume_from_checkpoint=path)
-    hist3 = t3.fit(module3, loader)
-    assert [h["epoch"] for h in hist3] == [int(ck["epoch"]) + 1] and math.isfinite(hist3[0]["train_loss"])

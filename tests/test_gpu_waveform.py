@@ -2,21 +2,16 @@
 LitWaveform on the GPU: forward, dX and every parameter gradient against the torch composition in float64 on the CPU,
 dropout masks, determinism, the bounds, one LitWaveform step against the CPU module, the captured step against the
 eager one on a padded batch, and Trainer(capture=True) from the r3 pulse fixture."""
-import copy
-import json
 import math
-import os
 
 import numpy as np
 import pytest
 import torch
 
+import waveform_cases as wc
+from waveform_cases import DEV, TOL, max_err as _max_err
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEV = "cuda:0"
-# the project's bars (tests/test_gpu_parity.py): fp32 within 1e-5 of each tensor's max magnitude; 16-bit rows on the
-# same rounded inputs within 2e-2 (bf16) / 3e-3 (fp16)
-TOL = {torch.float32: 1e-5, torch.bfloat16: 2e-2, torch.float16: 3e-3}
 
 
 def _tcn_pair(c0, channels, k, dropout=0.0, seed=0):
@@ -31,11 +26,6 @@ def _tcn_pair(c0, channels, k, dropout=0.0, seed=0):
     ref = TemporalConvNet(c0, channels, kernel_size=k, dropout=dropout).double()
     ref.load_state_dict({k_: v.double() for k_, v in gpu.state_dict().items()})
     return gpu.to(DEV), ref
-
-
-def _max_err(a, ref):
-    a, ref = a.detach().double().cpu(), ref.detach().double().cpu()
-    return float((a - ref).abs().max()), float(ref.abs().max())
 
 
 CASES = [  # (c0, channels, k, L)
@@ -77,9 +67,6 @@ def test_forward_dx_and_parameter_gradients_against_float64(case, dtype):
         assert err <= tol * scale, (name, err, scale)
 
 
-_M64 = (1 << 64) - 1
-
-
 def _hash_masks(seed, p, N, C, L, conv):
     """The kernels' dropout multipliers of conv `conv` (= 2 level + {0, 1}), [N, C, L] in float64, computed here from the
     documented scheme (csrc/tcnc.hip drop_mult: splitmix64 finaliser over seed + counter * golden ratio, counter =
@@ -88,16 +75,7 @@ def _hash_masks(seed, p, N, C, L, conv):
     row = np.arange(N, dtype=np.uint64)[:, None, None]
     ch = np.arange(C, dtype=np.uint64)[None, :, None]
     t = np.arange(L, dtype=np.uint64)[None, None, :]
-    ctr = ((((row << np.uint64(4)) | np.uint64(conv)) << np.uint64(5) | ch) << np.uint64(12)) | t
-    with np.errstate(over="ignore"):
-        z = np.uint64(seed & _M64) + ctr * np.uint64(0x9E3779B97F4A7C15)
-        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
-        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
-        z = z ^ (z >> np.uint64(31))
-    th = float(np.float32(p)) * 4294967296.0
-    thr = 0xFFFFFFFF if th >= 4294967295.0 else int(th)
-    scale = float(np.float32(1.0) / (np.float32(1.0) - np.float32(p)))
-    return torch.from_numpy(np.where((z >> np.uint64(32)) < np.uint64(thr), 0.0, scale))
+    return wc.hash_masks(seed, p, ((((row << np.uint64(4)) | np.uint64(conv)) << np.uint64(5) | ch) << np.uint64(12)) | t)
 
 
 def _masked_reference(ref, x, masks):
@@ -212,143 +190,32 @@ def test_bounds_take_the_torch_composition_and_the_flag_off_never_calls_the_kern
     assert not tcn.TemporalConvNet(1, [8, 16], 3).fused
 
 
-def _config(criterion="L1Loss", detector=False, n_samples=59):
-    with open(os.path.join(ROOT, "config", "waveform_tcn_z.json")) as f:
-        cfg = json.load(f)
-    cfg["system_config"]["n_samples"] = n_samples
-    cfg["net_config"]["criterion_class"] = criterion
-    if criterion.startswith("CrossEntropy"):
-        cfg["net_config"]["hparams"]["out_size"] = 2
-    if detector:
-        cfg["net_config"]["use_detector_number"] = True
-        cfg["net_config"]["num_detectors"] = 308
-    cfg["optimize_config"].pop("scheduler_class", None)
-    return cfg
-
-
-def _lit(cfg, seed=7):
-    from waveformml_amd.psd.config import DictionaryUtility
-    from waveformml_amd.psd.litwaveform import LitWaveform
-    torch.manual_seed(seed)
-    m = LitWaveform(DictionaryUtility.to_object(copy.deepcopy(cfg)))
+def _reinit(m, _cfg, _seed):
     with torch.no_grad():
         for p in m.model.model.parameters():
             p.copy_(torch.randn_like(p) * 0.5)
-    return m
 
 
-def _batch(n, L, criterion, seed, dev="cpu"):
-    g = torch.Generator().manual_seed(seed)
-    c = torch.randint(0, 616, (n, 1), generator=g, dtype=torch.int32)
-    f = torch.rand(n, L, generator=g)
-    y = torch.randint(0, 2, (n,), generator=g) if criterion.startswith("CrossEntropy") else torch.rand(n, generator=g)
-    return ([c.to(dev), f.to(dev)], y.to(dev))
+def _tcnc_calls():
+    from waveformml_amd.psd import tcn
+    return tcn.TCNC_CALLS[0]
+
+
+LIT = wc.LitCase("waveform_tcn_z.json", _tcnc_calls, _reinit)
 
 
 @pytest.mark.parametrize("detector", [False, True], ids=["rows", "detector"])
 @pytest.mark.parametrize("criterion", ["L1Loss", "CrossEntropyLoss"])
 def test_lit_waveform_one_training_step_against_the_cpu_module(criterion, detector):
-    from waveformml_amd.psd import tcn
-    cfg = _config(criterion, detector)
-    gpu = _lit(cfg)
-    cpu = _lit(cfg)
-    cpu.load_state_dict(gpu.state_dict())
-    assert gpu.model.nsamples == (62 if detector else 59)
-    gpu = gpu.to(DEV).train()
-    cpu.train()
-    b = _batch(500, 59, criterion, seed=3)
-    before = tcn.TCNC_CALLS[0]
-    lg = gpu.training_step(([b[0][0].to(DEV), b[0][1].to(DEV)], b[1].to(DEV)), 0)
-    assert tcn.TCNC_CALLS[0] == before + 1
-    lc = cpu.training_step(b, 0)
-    print("%s detector=%s: loss gpu %.8f cpu %.8f" % (criterion, detector, lg.item(), lc.item()))
-    assert abs(lg.item() - lc.item()) <= 1e-5 * abs(lc.item())
-    lg.backward()
-    lc.backward()
-    for (n, a), p in zip(gpu.model.named_parameters(), cpu.model.parameters()):
-        err, scale = _max_err(a.grad, p.grad)
-        assert err <= 1e-4 * scale, (n, err, scale)
-
-
-def _module(cfg, seed=7):
-    from waveformml_amd.psd.ddp import FlatGradAllReducer
-    mod = _lit(cfg, seed).to(DEV)
-    red = FlatGradAllReducer(mod.model.parameters(), world_size=1)
-    mod.optimizer_parameters = red.optimizer_parameters()
-    opt = mod.configure_optimizers()
-    return mod, red, opt
-
-
-def _eager_step(mod, red, opt, batch):
-    red.reset()
-    loss = mod.training_step(batch, 0)
-    loss.backward()
-    red.finish()
-    opt.step()
-    return float(loss)
+    wc.check_one_training_step_against_the_cpu_module(LIT, criterion, detector)
 
 
 @pytest.mark.parametrize("criterion", ["L1Loss", "CrossEntropyLoss"])
 def test_captured_step_matches_the_eager_step_on_padded_batches(criterion):
-    """Batches with FEWER rows than the captured capacity: the padding rows must add nothing to the L1 mean (or the
-    cross entropy) and nothing to any gradient."""
-    from waveformml_amd.psd.graph import GraphedTrainStep
-    cfg = _config(criterion)
-    batches = [_batch(n, 59, criterion, seed=40 + n, dev=DEV) for n in (200, 150, 233, 180)]
-    mod_g, red_g, opt_g = _module(cfg)
-    mod_e, red_e, opt_e = _module(cfg)
-    assert torch.equal(red_g.flat_param, red_e.flat_param)
-    step = GraphedTrainStep(mod_g, opt_g, red_g, batches[0], warmup=2)
-    assert step.per_row and step.n_cap > 233
-    for _ in range(3):                                       # the calibration step and the two warm-up steps
-        _eager_step(mod_e, red_e, opt_e, batches[0])
-    scale = float(red_e.flat_param.abs().max())
-    assert float((red_g.flat_param - red_e.flat_param).abs().max()) <= 2e-5 * scale
-    for b in batches[1:]:
-        lg = float(step(b))
-        le = _eager_step(mod_e, red_e, opt_e, b)
-        print("%s rows %d of %d: loss captured %.8f eager %.8f" % (criterion, b[1].shape[0], step.n_cap, lg, le))
-        assert abs(lg - le) <= 1e-5 * abs(le), (lg, le)
-        assert float((red_g.flat_param - red_e.flat_param).abs().max()) <= 2e-5 * scale
-    step.check()
-    step.close()
+    wc.check_captured_step_matches_the_eager_step_on_padded_batches(LIT, criterion)
 
 
 @pytest.mark.parametrize("label_index", [0, 1, 2])
 def test_trainer_captured_from_files_and_resume(label_index, tmp_path):
-    from waveformml_amd.psd.config import DictionaryUtility
-    from waveformml_amd.psd.litwaveform import LitWaveform
-    from waveformml_amd.psd.PSDDataModule import PSDDataModule
-    from waveformml_amd.psd.trainer import Trainer
-    with open(os.path.join(ROOT, "config", "waveform_tcn_z.json")) as f:
-        cfg = json.load(f)
-    cfg["system_config"]["n_samples"] = 12                  # the fixture's pulses are 12 samples long
-    dc = cfg["dataset_config"]
-    dc["base_path"] = os.path.join(ROOT, "tests", "golden", "h5", "r3")
-    dc["paths"] = ["pulses"]
-    dc["dataset_params"]["label_index"] = label_index
-    dc["n_train"] = 23
-    conf = DictionaryUtility.to_object(copy.deepcopy(cfg))
-    torch.manual_seed(2)
-    module = LitWaveform(conf)
-    loader = PSDDataModule(conf, DEV).train_dataloader()
-    # the pulse rows validate through LitWaveform.validation_step; the best epoch's checkpoint holds the run's own
-    # optimizer state (FlatSGD momentum)
-    trainer = Trainer(max_epochs=2, device=DEV, capture=True, default_root_dir=str(tmp_path))
-    hist = trainer.fit(module, loader, loader)
-    assert len(hist) == 2 and all(math.isfinite(h["train_loss"]) and math.isfinite(h["val_loss"]) for h in hist)
-    path = trainer.last_checkpoint
-    ck = torch.load(path, map_location="cpu", weights_only=True)
-    moms = [t for st in ck["optimizer_states"][0]["state"].values() for t in st.values() if torch.is_tensor(t) and t.numel() > 1]
-    assert moms and any(float(t.abs().sum()) > 0 for t in moms)
-    # resume with no epoch left: the weights are exactly the saved ones
-    module2 = LitWaveform(DictionaryUtility.to_object(copy.deepcopy(cfg)))
-    t2 = Trainer(max_epochs=int(ck["epoch"]) + 1, device=DEV, capture=True, resume_from_checkpoint=path)
-    assert t2.fit(module2, loader) == []
-    for k, v in module2.state_dict().items():
-        assert torch.equal(v.cpu(), ck["state_dict"][k]), k
-    # ... and one more epoch trains on from them
-    module3 = LitWaveform(DictionaryUtility.to_object(copy.deepcopy(cfg)))
-    t3 = Trainer(max_epochs=int(ck["epoch"]) + 2, device=DEV, capture=True, resume_from_checkpoint=path)
-    hist3 = t3.fit(module3, loader)
-    assert [h["epoch"] for h in hist3] == [int(ck["epoch"]) + 1] and math.isfinite(hist3[0]["train_loss"])
+    _ck, moms = wc.check_trainer_captured_from_files_and_resume(LIT, label_index, tmp_path)
+    assert any(float(t.abs().sum()) > 0 for t in moms)

@@ -21,11 +21,11 @@
 // outputs (before dropout).  Only the ends torch sees are [N][T][C]: k_rnn_tin / k_rnn_tout transpose X, dY in and Y, dX
 // out through 32 x 32 LDS tiles.
 // Dropout: torch's placement (the outputs of every layer but the last, training only), this project's generator: the
-// counter hash of tcnc.hip over (row, layer, channel, t).  No mask is stored; the next layer's input projection, its
+// counter hash of wfs_rows.h over (row, layer, channel, t).  No mask is stored; the next layer's input projection, its
 // dW pass and the backward's mix rebuild it from the seed.
 // Weight gradients: each dW block sums a fixed set of position tiles in a fixed order, and the partial sums are added
 // block by block in index order -- no atomics, bit-identical reruns.
-#include "wfs_common.h"
+#include "wfs_rows.h"
 
 namespace {
 
@@ -40,44 +40,9 @@ constexpr int DW_MAXBLK = 1024;  // dW blocks (partial sums per layer and direct
 constexpr int DW_MAXCOL = MAXC + MAXH + 1;
 constexpr int TT = 32;           // transpose tile
 
-struct Drop {
-    unsigned long long seed;
-    unsigned threshold;  // drop when the hash's high 32 bits are below p * 2^32
-    float scale;         // 1 / (1 - p); 1 when dropout is off
-    bool on;
-};
-__device__ __forceinline__ Drop make_drop(float p, const long long *seed_dev) {
-    Drop d;
-    d.on = p > 0.f && seed_dev != nullptr;
-    d.seed = d.on ? (unsigned long long)*seed_dev : 0ull;
-    double th = (double)p * 4294967296.0;
-    d.threshold = th >= 4294967295.0 ? 0xFFFFFFFFu : (unsigned)th;
-    d.scale = d.on ? 1.f / (1.f - p) : 1.f;
-    return d;
-}
 // element (row, layer, channel ch of the layer's output, sample t): t < 2^12, ch < 2^6, layer < 2^3 (include/wfsparse.h)
 __device__ __forceinline__ float drop_mult(const Drop &d, long long row, int layer, int ch, int t) {
-    if (!d.on) return 1.f;
-    unsigned long long ctr = ((((unsigned long long)row << 3 | (unsigned)layer) << 6 | (unsigned)ch) << 12) | (unsigned)t;
-    unsigned long long z = d.seed + ctr * 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return (unsigned)(z >> 32) < d.threshold ? 0.f : d.scale;
-}
-
-__device__ __forceinline__ float ldt(const void *p, long long i, int dt) {
-    if (dt == WFS_F32) return ((const float *)p)[i];
-    if (dt == WFS_BF16) return wfs_ld((const wfs_bf16 *)p + i);
-    return wfs_ld((const wfs_f16 *)p + i);
-}
-__device__ __forceinline__ void stt(void *p, long long i, int dt, float v) {
-    if (dt == WFS_F32)
-        ((float *)p)[i] = v;
-    else if (dt == WFS_BF16)
-        wfs_st((wfs_bf16 *)p + i, v);
-    else
-        wfs_st((wfs_f16 *)p + i, v);
+    return wfs_drop_mult(d, ((((unsigned long long)row << 3 | (unsigned)layer) << 6 | (unsigned)ch) << 12) | (unsigned)t);
 }
 
 struct Rec {  // one (layer, direction): device addresses (0 = absent)
@@ -424,7 +389,6 @@ long long part_stride(int I, int H, int dirs, int nblk) {
     const int in_max = I > dirs * H ? I : dirs * H;
     return (long long)nblk * H * (in_max + H + 1);
 }
-int dw_blocks(long long P) { return (int)(P / DW_TP + 1 < DW_MAXBLK ? P / DW_TP + 1 : DW_MAXBLK); }
 
 int check_shape(int32_t I, int32_t H, int32_t layers, int32_t dirs, int32_t nonlin, int32_t T, int32_t dtype) {
     WFS_REQUIRE(I >= 1 && I <= MAXI, WFS_EINVAL, "RNN input size %d: 1 .. %d supported", I, MAXI);
@@ -442,8 +406,7 @@ int check_common(int64_t N, int32_t T, int32_t I, int32_t H, int32_t layers, int
     int rc = check_shape(I, H, layers, dirs, nonlin, T, dtype);
     if (rc != WFS_OK) return rc;
     WFS_REQUIRE(N >= 0 && N <= (1ll << 40) / T, WFS_EINVAL, "%lld rows of %d samples", (long long)N, T);
-    WFS_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f && (dropout_p == 0.f || seed_dev), WFS_EINVAL,
-                "dropout %g needs 0 <= p < 1 and a seed", (double)dropout_p);
+    WFS_REQUIRE_DROPOUT(dropout_p, seed_dev);
     return WFS_OK;
 }
 
@@ -489,7 +452,7 @@ extern "C" size_t wfs_rnn_saved_floats(int64_t N, int32_t T, int32_t I, int32_t 
 extern "C" size_t wfs_rnn_bwd_workspace_floats(int64_t N, int32_t T, int32_t I, int32_t H, int32_t layers, int32_t dirs) {
     if (check_shape(I, H, layers, dirs, WFS_RNN_RELU, T, WFS_F32) != WFS_OK || N < 0) return 0;
     const size_t Npad = (size_t)pad64(N), cm = (size_t)(I > dirs * H ? I : dirs * H);
-    const int nblk = dw_blocks((long long)Npad * T);
+    const int nblk = wfs_dw_blocks((long long)Npad * T, DW_TP, DW_MAXBLK);
     return 2 * cm * T * Npad + (size_t)layers * dirs * (size_t)part_stride(I, H, dirs, nblk);
 }
 
@@ -547,7 +510,7 @@ extern "C" int wfs_rnn_bwd(const void *dY, int64_t N, int32_t T, int32_t I, int3
     const long long Npad = pad64(N);
     const int C = dirs * H, cm = I > C ? I : C;
     const bool tanh_ = nonlinearity == WFS_RNN_TANH;
-    const int nblk = dw_blocks(Npad * T);
+    const int nblk = wfs_dw_blocks(Npad * T, DW_TP, DW_MAXBLK);
     float *G = workspace, *Gn = G + (long long)cm * T * Npad, *part = Gn + (long long)cm * T * Npad;
     const long long pstride = part_stride(I, H, dirs, nblk);
     k_rnn_tin<<<t_grid((long long)T * C, Npad), dim3(TT, 8), 0, stream>>>(dY, dtype, G, N, Npad, (long long)T * C);

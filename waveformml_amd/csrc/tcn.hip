@@ -13,10 +13,10 @@
 //             per-row partial sums of dW / dB are reduced by the caller in a fixed order.
 // Weight norm (w = g v / |v|) stays with the caller: the kernels take the effective taps (device memory).
 // Dropout (nn.Dropout(p) after each of the two ReLUs of a level, ConvBlocks.py:125-134, active in training) is applied
-// in place: the keep/drop decision of element (row, level, conv, t) is a counter-based hash of a 64-bit seed that the
+// in place: the keep/drop decision of element (row, level, conv, t) is a counter-based hash (wfs_rows.h) of a 64-bit seed that the
 // caller draws from torch's generator into device memory -- nothing is stored, the backward's recompute sees the same
 // masks.  (The masks are this library's own stream of random numbers, not torch's: same distribution, other bits.)
-#include "wfs_common.h"
+#include "wfs_rows.h"
 
 namespace {
 
@@ -36,36 +36,10 @@ __device__ __forceinline__ void load_taps(Taps *tp, const float *W, const float 
     for (int i = threadIdx.x; i < levels * 2; i += TB) tp->b[i] = B[i];
 }
 
-// dropout multiplier of element t of conv `ci` (= 2 * level + {0, 1}) of `row`: 0 with probability p, else 1 / (1 - p).
-// splitmix64 finaliser over a counter that is unique per element (t < 2^12, ci < 2^4).
-struct Drop {
-    unsigned long long seed;
-    unsigned threshold;      // drop when the hash's high 32 bits are below p * 2^32
-    float scale;             // 1 / (1 - p); 1 when dropout is off
-    bool on;
-};
-__device__ __forceinline__ Drop make_drop(float p, const long long *seed_dev) {
-    Drop d;
-    d.on = p > 0.f && seed_dev != nullptr;
-    d.seed = d.on ? (unsigned long long)*seed_dev : 0ull;
-    double th = (double)p * 4294967296.0;
-    d.threshold = th >= 4294967295.0 ? 0xFFFFFFFFu : (unsigned)th;
-    d.scale = d.on ? 1.f / (1.f - p) : 1.f;
-    return d;
-}
+// dropout multiplier of element t of conv `ci` (= 2 * level + {0, 1}) of `row`: the counter is unique per element
+// (t < 2^12, ci < 2^4)
 __device__ __forceinline__ float drop_mult(const Drop &d, long long row, int ci, int t) {
-    if (!d.on) return 1.f;
-    unsigned long long z = d.seed + (((unsigned long long)row << 16) | ((unsigned long long)ci << 12) | (unsigned)t) *
-                                        0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return (unsigned)(z >> 32) < d.threshold ? 0.f : d.scale;
-}
-
-template <typename T>
-__device__ __forceinline__ float ldv(const T *p) {
-    return wfs_ld(p);
+    return wfs_drop_mult(d, ((unsigned long long)row << 16) | ((unsigned long long)ci << 12) | (unsigned)t);
 }
 
 // out[t] = bias + sum_j w[j] in[t - (K-1-j) d]   (zero to the left of the row)
@@ -91,7 +65,7 @@ __global__ void __launch_bounds__(TB) k_tcn_fwd(const T *__restrict__ X, long lo
     const Drop dr = make_drop(drop_p, seed_dev);
     const T *x = X + row * L;
     load_taps<K>(&tp, Wd, Bd, levels);
-    for (int t = threadIdx.x; t < L; t += TB) A[t] = ldv(x + t);
+    for (int t = threadIdx.x; t < L; t += TB) A[t] = wfs_ld(x + t);
     __syncthreads();
     for (int lv = 0; lv < levels; ++lv) {
         const int d = 1 << lv;
@@ -135,8 +109,8 @@ __global__ void __launch_bounds__(TBW) k_tcn_bwd(const T *__restrict__ X, const 
     const Drop dr = make_drop(drop_p, seed_dev);
     load_taps<K>(&tp, Wd, Bd, levels);
     for (int t = threadIdx.x; t < L; t += nthr) {
-        Xs[t] = ldv(x + t);
-        G[t] = ldv(dY + row * L + t);
+        Xs[t] = wfs_ld(x + t);
+        G[t] = wfs_ld(dY + row * L + t);
     }
     __syncthreads();
     // ---- forward recompute, everything kept
@@ -243,83 +217,74 @@ __global__ void __launch_bounds__(TBW) k_tcn_bwd(const T *__restrict__ X, const 
     for (int t = threadIdx.x; t < L; t += nthr) wfs_st(dx + t, G[t]);
 }
 
+// f(Inst<T, K>) for the rows' dtype and the kernel size: what the two entry points instantiate their kernels through
+// (3 dtypes x k = 1 .. 8 each)
+template <typename T_, int K_>
+struct Inst {
+    using T = T_;
+    static constexpr int K = K_;
+};
+template <typename T, typename F>
+int with_k(int k, F &f) {
+    switch (k) {
+        case 1: return f(Inst<T, 1>());
+        case 2: return f(Inst<T, 2>());
+        case 3: return f(Inst<T, 3>());
+        case 4: return f(Inst<T, 4>());
+        case 5: return f(Inst<T, 5>());
+        case 6: return f(Inst<T, 6>());
+        case 7: return f(Inst<T, 7>());
+        default: return f(Inst<T, 8>());
+    }
+}
+template <typename F>
+int with_dtype_k(int dtype, int k, F f) {
+    if (dtype == WFS_F32) return with_k<float>(k, f);
+    if (dtype == WFS_BF16) return with_k<wfs_bf16>(k, f);
+    return with_k<wfs_f16>(k, f);
+}
+
+int check_common(int32_t L, int32_t levels, int32_t k, int32_t dtype, float dropout_p, const int64_t *seed_dev) {
+    WFS_REQUIRE(levels >= 1 && levels <= MAXLV && k >= 1 && k <= MAXK, WFS_EINVAL, "unsupported TCN shape: %d levels, k = %d",
+                levels, k);
+    WFS_REQUIRE(L >= 1 && L <= 16 * TB, WFS_EINVAL, "row length %d not in [1, %d]", L, 16 * TB);
+    WFS_REQUIRE(wfs_dtype_ok(dtype), WFS_EINVAL, "bad dtype %d", dtype);
+    WFS_REQUIRE_DROPOUT(dropout_p, seed_dev);
+    return WFS_OK;
+}
+
 }  // namespace
 
 extern "C" size_t wfs_tcn_lds_bytes(int32_t L, int32_t levels, int32_t backward) {
     return (size_t)L * sizeof(float) * (backward ? (3 * levels + 4) : 2);
 }
 
-#define WFS_TCN_DISPATCH_K(KERNEL, T, ...)                                  \
-    switch (k) {                                                            \
-        case 1: KERNEL<T, 1><<<grid, block, lds, stream>>>(__VA_ARGS__); break; \
-        case 2: KERNEL<T, 2><<<grid, block, lds, stream>>>(__VA_ARGS__); break; \
-        case 3: KERNEL<T, 3><<<grid, block, lds, stream>>>(__VA_ARGS__); break; \
-        case 4: KERNEL<T, 4><<<grid, block, lds, stream>>>(__VA_ARGS__); break; \
-        case 5: KERNEL<T, 5><<<grid, block, lds, stream>>>(__VA_ARGS__); break; \
-        case 6: KERNEL<T, 6><<<grid, block, lds, stream>>>(__VA_ARGS__); break; \
-        case 7: KERNEL<T, 7><<<grid, block, lds, stream>>>(__VA_ARGS__); break; \
-        default: KERNEL<T, 8><<<grid, block, lds, stream>>>(__VA_ARGS__); break; \
-    }
-
 extern "C" int wfs_tcn_fwd(const void *X, int64_t N, int32_t L, const float *taps, const float *bias, int32_t levels,
                            int32_t k, void *Y, int32_t dtype, float dropout_p, const int64_t *seed_dev_,
                            void *stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    WFS_REQUIRE(levels >= 1 && levels <= MAXLV && k >= 1 && k <= MAXK, WFS_EINVAL, "unsupported TCN shape: %d levels, k = %d",
-                levels, k);
-    WFS_REQUIRE(L >= 1 && L <= 16 * TB, WFS_EINVAL, "row length %d not in [1, %d]", L, 16 * TB);
-    WFS_REQUIRE(wfs_dtype_ok(dtype), WFS_EINVAL, "bad dtype %d", dtype);
-    WFS_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f && (dropout_p == 0.f || seed_dev_), WFS_EINVAL,
-                "dropout %g needs 0 <= p < 1 and a seed", (double)dropout_p);
+    int rc = check_common(L, levels, k, dtype, dropout_p, seed_dev_);
+    if (rc != WFS_OK) return rc;
     const long long *seed_dev = (const long long *)seed_dev_;
     if (N == 0) return WFS_OK;
     WFS_REQUIRE(X && Y && taps && bias, WFS_EINVAL, "NULL device pointer");
     const size_t lds = wfs_tcn_lds_bytes(L, levels, 0);
     const dim3 grid((unsigned)N), block(TB);
-    if (dtype == WFS_F32) {
-        WFS_TCN_DISPATCH_K(k_tcn_fwd, float, (const float *)X, N, L, taps, bias, levels, (float *)Y, dropout_p, seed_dev)
-    } else if (dtype == WFS_BF16) {
-        WFS_TCN_DISPATCH_K(k_tcn_fwd, wfs_bf16, (const wfs_bf16 *)X, N, L, taps, bias, levels, (wfs_bf16 *)Y, dropout_p, seed_dev)
-    } else {
-        WFS_TCN_DISPATCH_K(k_tcn_fwd, wfs_f16, (const wfs_f16 *)X, N, L, taps, bias, levels, (wfs_f16 *)Y, dropout_p, seed_dev)
-    }
-    WFS_LAUNCH_CHECK();
-    return WFS_OK;
-}
-
-template <typename T, int K>
-static int tcn_bwd_attr() {
-    static bool done = false;
-    if (!done) {
-        WFS_HIP_CHECK(hipFuncSetAttribute((const void *)k_tcn_bwd<T, K>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-        done = true;
-    }
-    return WFS_OK;
-}
-template <typename T>
-static int tcn_bwd_attr_k(int k) {
-    switch (k) {
-        case 1: return tcn_bwd_attr<T, 1>();
-        case 2: return tcn_bwd_attr<T, 2>();
-        case 3: return tcn_bwd_attr<T, 3>();
-        case 4: return tcn_bwd_attr<T, 4>();
-        case 5: return tcn_bwd_attr<T, 5>();
-        case 6: return tcn_bwd_attr<T, 6>();
-        case 7: return tcn_bwd_attr<T, 7>();
-        default: return tcn_bwd_attr<T, 8>();
-    }
+    return with_dtype_k(dtype, k, [&](auto inst) {
+        using T = typename decltype(inst)::T;
+        k_tcn_fwd<T, decltype(inst)::K><<<grid, block, lds, stream>>>((const T *)X, N, L, taps, bias, levels, (T *)Y, dropout_p,
+                                                                       seed_dev);
+        WFS_LAUNCH_CHECK();
+        return (int)WFS_OK;
+    });
 }
 
 extern "C" int wfs_tcn_bwd(const void *X, const void *dY, int64_t N, int32_t L, const float *taps, const float *bias,
                            int32_t levels, int32_t k, void *dX, float *partial, int32_t dtype, float dropout_p,
                            const int64_t *seed_dev_, void *stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    WFS_REQUIRE(levels >= 1 && levels <= MAXLV && k >= 1 && k <= MAXK, WFS_EINVAL, "unsupported TCN shape: %d levels, k = %d",
-                levels, k);
-    WFS_REQUIRE(L >= 1 && L <= 16 * TB, WFS_EINVAL, "row length %d not in [1, %d]", L, 16 * TB);
-    WFS_REQUIRE(wfs_dtype_ok(dtype), WFS_EINVAL, "bad dtype %d", dtype);
-    WFS_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f && (dropout_p == 0.f || seed_dev_), WFS_EINVAL,
-                "dropout %g needs 0 <= p < 1 and a seed", (double)dropout_p);
+    int rc = check_common(L, levels, k, dtype, dropout_p, seed_dev_);
+    if (rc != WFS_OK) return rc;
     const long long *seed_dev = (const long long *)seed_dev_;
     const size_t lds = wfs_tcn_lds_bytes(L, levels, 1);
     WFS_REQUIRE(lds <= 150 * 1024, WFS_EINVAL, "row of %d samples x %d levels needs %zu B of LDS", L, levels, lds);
@@ -327,24 +292,19 @@ extern "C" int wfs_tcn_bwd(const void *X, const void *dY, int64_t N, int32_t L, 
     WFS_REQUIRE(X && dY && dX && partial && taps && bias, WFS_EINVAL, "NULL device pointer");
     // rows that leave room for one or two blocks per CU get a 16-wave block, short rows keep 4 waves and more blocks
     const dim3 grid((unsigned)N), block(lds > 48 * 1024 ? TBW : TB);
-    if (dtype == WFS_F32) {
-        int rc = tcn_bwd_attr_k<float>(k);
-        if (rc != WFS_OK) return rc;
-        WFS_TCN_DISPATCH_K(k_tcn_bwd, float, (const float *)X, (const float *)dY, N, L, taps, bias, levels, (float *)dX, partial,
-                           dropout_p, seed_dev)
-    } else if (dtype == WFS_BF16) {
-        int rc = tcn_bwd_attr_k<wfs_bf16>(k);
-        if (rc != WFS_OK) return rc;
-        WFS_TCN_DISPATCH_K(k_tcn_bwd, wfs_bf16, (const wfs_bf16 *)X, (const wfs_bf16 *)dY, N, L, taps, bias, levels,
-                           (wfs_bf16 *)dX, partial, dropout_p, seed_dev)
-    } else {
-        int rc = tcn_bwd_attr_k<wfs_f16>(k);
-        if (rc != WFS_OK) return rc;
-        WFS_TCN_DISPATCH_K(k_tcn_bwd, wfs_f16, (const wfs_f16 *)X, (const wfs_f16 *)dY, N, L, taps, bias, levels,
-                           (wfs_f16 *)dX, partial, dropout_p, seed_dev)
-    }
-    WFS_LAUNCH_CHECK();
-    return WFS_OK;
+    return with_dtype_k(dtype, k, [&](auto inst) {
+        using T = typename decltype(inst)::T;
+        constexpr int K = decltype(inst)::K;
+        static bool attr_done = false;          // one per instantiation (T, K): its first launch raises the LDS limit
+        if (!attr_done) {
+            WFS_HIP_CHECK(hipFuncSetAttribute((const void *)k_tcn_bwd<T, K>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+            attr_done = true;
+        }
+        k_tcn_bwd<T, K><<<grid, block, lds, stream>>>((const T *)X, (const T *)dY, N, L, taps, bias, levels, (T *)dX, partial,
+                                                      dropout_p, seed_dev);
+        WFS_LAUNCH_CHECK();
+        return (int)WFS_OK;
+    });
 }
 
 // ------------------------------------------------------------------------------------------ weight norm of the taps
@@ -354,11 +314,6 @@ extern "C" int wfs_tcn_bwd(const void *X, const void *dY, int64_t N, int32_t L, 
 // all convolutions' (v, g, b) through a pointer table into the [n_conv][k] taps / [n_conv] biases the fused kernels take,
 // and ONE launch turns the per-row partial sums of the backward into dv, dg, db, written straight to where the caller
 // wants them (the parameters' gradient slots).
-struct TcnParamPtrs {           // one convolution: device addresses (0 = absent)
-    const float *v, *g, *b;
-    float *dv, *dg, *db;
-};
-
 __global__ void __launch_bounds__(64) k_tcn_taps(const TcnParamPtrs *__restrict__ pp, int n_conv, int k,
                                                  float *__restrict__ taps, float *__restrict__ bias) {
     const int c = blockIdx.x * 64 + threadIdx.x;

@@ -16,11 +16,11 @@
 //                        k_tcnc_bwd_x (x's gradient through conv1 plus the residual), k_tcnc_dw (all the level's weight
 //                        gradients as per-block partial sums); then ONE k_tcnc_wn_bwd for every convolution of the net.
 // The forward keeps r1 = relu(conv1), r2 = relu(conv2) -- BEFORE dropout -- and out of every level (fp32) for the
-// backward.  Dropout is a counter-based hash of a 64-bit seed in device memory (the scheme of tcn.hip, with the channel
+// backward.  Dropout is a counter-based hash of a 64-bit seed in device memory (wfs_rows.h, with the channel
 // in the counter): m(row, conv, channel, t) in {0, 1 / (1 - p)}.  No mask is stored: every pass that needs one -- conv2
 // reading h1 = r1 m1, the backward's mask passes, conv2's dW reading h1 -- rebuilds it from the seed.  Weight gradients: each dW block sums a fixed set of positions in a
 // fixed order, and the partial sums are added block by block in index order -- no atomics, bit-identical reruns.
-#include "wfs_common.h"
+#include "wfs_rows.h"
 
 namespace {
 
@@ -32,45 +32,9 @@ constexpr int DW_MAXBLK = 1024;           // dW blocks (partial sums per convolu
 constexpr int MAX_GRID = 4096;            // conv passes: grid-stride beyond this many blocks
 constexpr int MAXW = MAXC * MAXC * MAXK;  // taps of the largest convolution
 
-struct Drop {
-    unsigned long long seed;
-    unsigned threshold;  // drop when the hash's high 32 bits are below p * 2^32
-    float scale;         // 1 / (1 - p); 1 when dropout is off
-    bool on;
-};
-__device__ __forceinline__ Drop make_drop(float p, const long long *seed_dev) {
-    Drop d;
-    d.on = p > 0.f && seed_dev != nullptr;
-    d.seed = d.on ? (unsigned long long)*seed_dev : 0ull;
-    double th = (double)p * 4294967296.0;
-    d.threshold = th >= 4294967295.0 ? 0xFFFFFFFFu : (unsigned)th;
-    d.scale = d.on ? 1.f / (1.f - p) : 1.f;
-    return d;
-}
 // element (row, conv ci = 2 * level + {0, 1}, channel ch, sample t): t < 2^12, ch < 2^5, ci < 2^4
 __device__ __forceinline__ float drop_mult(const Drop &d, long long row, int ci, int ch, int t) {
-    if (!d.on) return 1.f;
-    unsigned long long ctr = ((((unsigned long long)row << 4 | (unsigned)ci) << 5 | (unsigned)ch) << 12) | (unsigned)t;
-    unsigned long long z = d.seed + ctr * 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return (unsigned)(z >> 32) < d.threshold ? 0.f : d.scale;
-}
-
-// rows of any of the three dtypes (the code is uniform across a launch: no divergence)
-__device__ __forceinline__ float ldt(const void *p, long long i, int dt) {
-    if (dt == WFS_F32) return ((const float *)p)[i];
-    if (dt == WFS_BF16) return wfs_ld((const wfs_bf16 *)p + i);
-    return wfs_ld((const wfs_f16 *)p + i);
-}
-__device__ __forceinline__ void stt(void *p, long long i, int dt, float v) {
-    if (dt == WFS_F32)
-        ((float *)p)[i] = v;
-    else if (dt == WFS_BF16)
-        wfs_st((wfs_bf16 *)p + i, v);
-    else
-        wfs_st((wfs_f16 *)p + i, v);
+    return wfs_drop_mult(d, ((((unsigned long long)row << 4 | (unsigned)ci) << 5 | (unsigned)ch) << 12) | (unsigned)t);
 }
 
 struct FwdArgs {
@@ -337,10 +301,6 @@ __global__ void __launch_bounds__(TB) k_tcnc_dw(DwJobs jobs, long long N, int L,
     }
 }
 
-struct ParamPtrs {  // one convolution: device addresses (0 = absent)
-    const float *v, *g, *b;
-    float *dv, *dg, *db;
-};
 struct ConvDesc {
     int cin, cout, kk, d;
     long long w_off, b_off, p_off;  // into the weights buffer / the partial sums
@@ -351,9 +311,9 @@ struct ConvTable {
 
 // effective taps of every convolution: w = g v / |v| per output channel (torch.nn.utils.weight_norm, dim 0); the
 // downsample has no weight norm (g == 0: w = v).  Block = convolution, thread = output channel.
-__global__ void __launch_bounds__(64) k_tcnc_taps(const ParamPtrs *__restrict__ pp, ConvTable tab, float *__restrict__ wts) {
+__global__ void __launch_bounds__(64) k_tcnc_taps(const TcnParamPtrs *__restrict__ pp, ConvTable tab, float *__restrict__ wts) {
     const ConvDesc cd = tab.c[blockIdx.x];
-    const ParamPtrs p = pp[blockIdx.x];
+    const TcnParamPtrs p = pp[blockIdx.x];
     const int co = threadIdx.x, n = cd.cin * cd.kk;
     if (co >= cd.cout) return;
     const float *v = p.v + (long long)co * n;
@@ -371,12 +331,12 @@ __global__ void __launch_bounds__(64) k_tcnc_taps(const ParamPtrs *__restrict__ 
 //   dg = (dw . v) / |v|,   dv = g / |v| (dw - v (dw . v) / |v|^2),   db = the bias column;   downsample: dv = dw.
 // In double: dw . v cancels (dg of a wide layer is a small difference of large products), and this is a few hundred
 // numbers per block.
-__global__ void __launch_bounds__(TB) k_tcnc_wn_bwd(const ParamPtrs *__restrict__ pp, ConvTable tab,
+__global__ void __launch_bounds__(TB) k_tcnc_wn_bwd(const TcnParamPtrs *__restrict__ pp, ConvTable tab,
                                                     const float *__restrict__ part, int nblk) {
     const ConvDesc cd = tab.c[blockIdx.x];
     const int co = blockIdx.y;
     if (co >= cd.cout) return;
-    const ParamPtrs p = pp[blockIdx.x];
+    const TcnParamPtrs p = pp[blockIdx.x];
     const int n = cd.cin * cd.kk, ncol = n + 1;
     __shared__ double dw[MAXC * MAXK + 1];
     __shared__ double red[2][TB];
@@ -448,8 +408,6 @@ int plan(int32_t c0, const int32_t *channels, int32_t levels, int32_t k, ConvTab
     return WFS_OK;
 }
 
-int dw_blocks(long long P) { return (int)(P / DW_TP + 1 < DW_MAXBLK ? P / DW_TP + 1 : DW_MAXBLK); }
-
 unsigned grid_for(long long threads) {
     long long b = (threads + TB - 1) / TB;
     return (unsigned)(b < 1 ? 1 : (b > MAX_GRID ? MAX_GRID : b));
@@ -468,8 +426,7 @@ int check_common(int32_t c0, const int32_t *channels, int32_t levels, int32_t k,
     WFS_REQUIRE(L >= 1 && L <= WFS_TCNC_MAX_L, WFS_EINVAL, "row length %d not in [1, %d]", L, WFS_TCNC_MAX_L);
     WFS_REQUIRE(N >= 0 && N <= (1ll << 40) / L, WFS_EINVAL, "%lld rows of %d samples", (long long)N, L);
     WFS_REQUIRE(wfs_dtype_ok(dtype), WFS_EINVAL, "bad dtype %d", dtype);
-    WFS_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f && (dropout_p == 0.f || seed_dev), WFS_EINVAL,
-                "dropout %g needs 0 <= p < 1 and a seed", (double)dropout_p);
+    WFS_REQUIRE_DROPOUT(dropout_p, seed_dev);
     return WFS_OK;
 }
 
@@ -511,7 +468,7 @@ extern "C" size_t wfs_tcnc_bwd_workspace_floats(int64_t N, int32_t L, int32_t c0
     int nc;
     if (plan(c0, channels, levels, k, &tab, &nc, nullptr) != WFS_OK) return 0;
     const size_t cm = (size_t)max_channels(c0, channels, levels), nl = (size_t)N * L;
-    const int nblk = dw_blocks((long long)nl);
+    const int nblk = wfs_dw_blocks((long long)nl, DW_TP, DW_MAXBLK);
     size_t parts = 0;
     for (int c = 0; c < nc; ++c) parts += (size_t)nblk * tab.c[c].cout * (tab.c[c].cin * tab.c[c].kk + 1);
     return 5 * cm * nl + parts;
@@ -524,7 +481,7 @@ extern "C" int wfs_tcnc_taps_fwd(const void *param_ptrs, int32_t c0, const int32
     int rc = plan(c0, channels, levels, k, &tab, &nc, nullptr);
     if (rc != WFS_OK) return rc;
     WFS_REQUIRE(param_ptrs && wts, WFS_EINVAL, "NULL device pointer");
-    k_tcnc_taps<<<dim3(nc), dim3(64), 0, (hipStream_t)stream_>>>((const ParamPtrs *)param_ptrs, tab, wts);
+    k_tcnc_taps<<<dim3(nc), dim3(64), 0, (hipStream_t)stream_>>>((const TcnParamPtrs *)param_ptrs, tab, wts);
     WFS_LAUNCH_CHECK();
     return WFS_OK;
 }
@@ -610,7 +567,7 @@ extern "C" int wfs_tcnc_bwd(const void *X, const void *dY, int64_t N, int32_t L,
     WFS_REQUIRE(N >= 1, WFS_EINVAL, "the backward needs at least one row (the gradients of an empty batch are zeros)");
     WFS_REQUIRE(X && dY && dX && wts && saved && workspace && param_ptrs, WFS_EINVAL, "NULL device pointer");
     const long long nl = N * (long long)L;
-    const int nblk = dw_blocks(nl);
+    const int nblk = wfs_dw_blocks(nl, DW_TP, DW_MAXBLK);
     const long long cm = max_channels(c0, channels, levels);
     float *GO = workspace, *GZ2 = GO + cm * nl, *GZ1 = GZ2 + cm * nl, *DXB[2] = {GZ1 + cm * nl, GZ1 + 2 * cm * nl};
     float *part = GZ1 + 3 * cm * nl;
@@ -685,7 +642,7 @@ extern "C" int wfs_tcnc_bwd(const void *X, const void *dY, int64_t N, int32_t L,
         G = dxl;
         gdt = WFS_F32;
     }
-    k_tcnc_wn_bwd<<<dim3(nc, MAXC), dim3(TB), 0, stream>>>((const ParamPtrs *)param_ptrs, tab, part, nblk);
+    k_tcnc_wn_bwd<<<dim3(nc, MAXC), dim3(TB), 0, stream>>>((const TcnParamPtrs *)param_ptrs, tab, part, nblk);
     WFS_LAUNCH_CHECK();
     return WFS_OK;
 }

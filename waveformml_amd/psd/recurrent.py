@@ -19,8 +19,8 @@ from torch import nn
 from torch.autograd import Function
 
 from .. import _lib
+from . import _fused
 from .blocks import LinearBlock
-from .tcn import _ptr_table
 
 RNN_CALLS = [0]      # forward calls that ran on the scan kernels (tests and tools read it)
 
@@ -38,10 +38,8 @@ class FusedRNNFunction(Function):
         x = x.contiguous()
         I, H, layers, dirs, nonlin = shape
         N, T, _i = x.shape
-        rows = []
-        for r in range(len(params) // 4):
-            rows.append([t.data_ptr() if t is not None else 0 for t in params[4 * r: 4 * r + 4]] + [0, 0, 0, 0])
-        tab = _ptr_table(cache, ("rfwd",) + tuple(a for r in rows for a in r[:4]), rows, x.device)
+        rows = _fused.fwd_rows(params, 4)
+        tab = _fused.ptr_table(cache, ("rfwd",) + tuple(map(tuple, rows)), rows, x.device)
         saved = torch.empty((int(lib.wfs_rnn_saved_floats(N, T, I, H, layers, dirs)),), dtype=torch.float32,
                             device=x.device)
         y = torch.empty((N, T, dirs * H), dtype=x.dtype, device=x.device)
@@ -58,30 +56,24 @@ class FusedRNNFunction(Function):
 
     @staticmethod
     def backward(ctx, grad_output, _grad_hidden):
-        from ..spconv.functional import grad_like
         lib = _lib.load()
         saved, = ctx.saved_tensors
         I, H, layers, dirs, nonlin = ctx.shape
         N, T, dtype, device = ctx.xinfo
-        params = ctx.params
-        dy = grad_output.contiguous()
-        if dy.dtype != dtype:
-            dy = dy.to(dtype)
+        first = FusedRNNFunction.first_param
+        dy = _fused.as_grad(grad_output, dtype)
         dx = torch.empty((N, T, I), dtype=dtype, device=device) if ctx.needs_input_grad[0] else None
-        grads, rows = [], []
-        for r in range(len(params) // 4):
-            ps = params[4 * r: 4 * r + 4]
-            need = ctx.needs_input_grad[5 + 4 * r: 5 + 4 * r + 4]
-            gs = [grad_like(p) if (p is not None and nd) else None for p, nd in zip(ps, need)]
-            grads += gs
-            rows.append([t.data_ptr() if t is not None else 0 for t in list(ps) + gs])
-        tab = _ptr_table(ctx.cache, ("rbwd",) + tuple(a for r in rows for a in r), rows, device)
+        rows, grads = _fused.bwd_rows(ctx, ctx.params, 4, first)
+        tab = _fused.ptr_table(ctx.cache, ("rbwd",) + tuple(map(tuple, rows)), rows, device)
         ws = torch.empty((int(lib.wfs_rnn_bwd_workspace_floats(N, T, I, H, layers, dirs)),), dtype=torch.float32,
                          device=device)
         _lib.check(lib.wfs_rnn_bwd(_lib.ptr(dy), N, T, I, H, layers, dirs, nonlin, _lib.ptr(tab), _lib.ptr(saved),
                                    _lib.ptr(dx), _lib.ptr(ws), _lib.dtype_code(dy), ctx.dropout, _lib.ptr(ctx.seed),
                                    _lib.stream_ptr()))
-        return (dx, None, None, None, None) + tuple(grads)
+        return (dx,) + (None,) * (first - 1) + tuple(grads)
+
+
+FusedRNNFunction.first_param = _fused.first_param(FusedRNNFunction)
 
 
 class RecurrentBlock(nn.Module):
@@ -98,16 +90,10 @@ class RecurrentBlock(nn.Module):
         """(weight_ih, weight_hh, bias_ih, bias_hh) per (layer, direction), read from the holder by name; None unless
         every tensor is contiguous fp32 on the GPU."""
         rnn = self.rnn
-        out = []
-        for layer in range(rnn.num_layers):
-            for sfx in ("", "_reverse") if rnn.bidirectional else ("",):
-                names = ["weight_ih_l%d%s", "weight_hh_l%d%s"] + (["bias_ih_l%d%s", "bias_hh_l%d%s"] if rnn.bias else [])
-                four = [getattr(rnn, n % (layer, sfx)) for n in names] + ([] if rnn.bias else [None, None])
-                for t in four:
-                    if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda):
-                        return None
-                out += four
-        return out
+        names = ("weight_ih", "weight_hh") + (("bias_ih", "bias_hh") if rnn.bias else ())
+        return _fused.kernel_params(
+            [getattr(rnn, "%s_l%d%s" % (n, layer, sfx)) for n in names] + ([] if rnn.bias else [None, None])
+            for layer in range(rnn.num_layers) for sfx in (("", "_reverse") if rnn.bidirectional else ("",)))
 
     def _can_fuse(self, x):
         rnn = self.rnn
@@ -127,15 +113,10 @@ class RecurrentBlock(nn.Module):
             rnn = self.rnn
             seed, p = None, 0.0
             if self.training and rnn.dropout > 0 and rnn.num_layers > 1:
-                # a fresh 64-bit seed per call from torch's generator (reproducible under torch.manual_seed, and a captured
-                # graph draws a new one per replay); the kernels derive every mask from it
-                seed = torch.randint(-2 ** 62, 2 ** 62, (1,), dtype=torch.int64, device=x.device)
-                p = rnn.dropout
-            if not hasattr(self, "_ptr_cache"):
-                self._ptr_cache = {}
+                seed, p = _fused.draw_seed(x.device), rnn.dropout
             shape = (rnn.input_size, rnn.hidden_size, rnn.num_layers, 2 if rnn.bidirectional else 1,
                      _NONLIN[rnn.nonlinearity])
-            return FusedRNNFunction.apply(x, shape, p, seed, self._ptr_cache, *self._fused_params())
+            return FusedRNNFunction.apply(x, shape, p, seed, _fused.ptr_cache(self), *self._fused_params())
         return self.rnn(x)
 
     def init_hidden(self, batch_size):

@@ -21,6 +21,7 @@ from torch.autograd import Function
 from torch.nn.utils import weight_norm
 
 from .. import _lib
+from . import _fused
 
 
 class _Chomp(nn.Module):
@@ -56,6 +57,29 @@ class TemporalBlock(nn.Module):
         return self.relu(self.net(x) + res)
 
 
+def _tcn_launch_fwd(x, taps, bias, dropout, seed):
+    """wfs_tcn_fwd on contiguous rows [N, L] and effective taps [levels, 2, k] / biases [levels, 2] -> rows [N, L]."""
+    N, L = x.shape
+    levels, _, k = taps.shape
+    y = torch.empty_like(x)
+    _lib.check(_lib.load().wfs_tcn_fwd(_lib.ptr(x), N, L, _lib.ptr(taps), _lib.ptr(bias), levels, k, _lib.ptr(y),
+                                       _lib.dtype_code(x), float(dropout), _lib.ptr(seed), _lib.stream_ptr()))
+    return y
+
+
+def _tcn_launch_bwd(x, grad_output, taps, bias, dropout, seed):
+    """wfs_tcn_bwd -> (dx [N, L], the per-row partial sums [N, levels, 2, k + 1] of d taps and d bias)."""
+    N, L = x.shape
+    levels, _, k = taps.shape
+    dy = _fused.as_grad(grad_output, x.dtype)
+    dx = torch.empty_like(x)
+    partial = torch.empty((N, levels, 2, k + 1), dtype=torch.float32, device=x.device)
+    _lib.check(_lib.load().wfs_tcn_bwd(_lib.ptr(x), _lib.ptr(dy), N, L, _lib.ptr(taps), _lib.ptr(bias), levels, k,
+                                       _lib.ptr(dx), _lib.ptr(partial), _lib.dtype_code(x), dropout, _lib.ptr(seed),
+                                       _lib.stream_ptr()))
+    return dx, partial
+
+
 class FusedTCNFunction(Function):
     """The two fused kernels on EFFECTIVE taps (what the module's FusedNormedTCNFunction wraps with the weight norm):
     rows [N, L], effective taps [levels, 2, k] and biases [levels, 2] (fp32, on the GPU) -> rows [N, L].
@@ -63,47 +87,19 @@ class FusedTCNFunction(Function):
 
     @staticmethod
     def forward(ctx, x, taps, bias, dropout=0.0, seed=None):
-        lib = _lib.load()
-        x = x.contiguous()
-        taps, bias = taps.contiguous(), bias.contiguous()
-        N, L = x.shape
-        levels, _, k = taps.shape
-        y = torch.empty_like(x)
-        _lib.check(lib.wfs_tcn_fwd(_lib.ptr(x), N, L, _lib.ptr(taps), _lib.ptr(bias), levels, k, _lib.ptr(y),
-                                   _lib.dtype_code(x), float(dropout), _lib.ptr(seed), _lib.stream_ptr()))
+        x, taps, bias = x.contiguous(), taps.contiguous(), bias.contiguous()
+        y = _tcn_launch_fwd(x, taps, bias, dropout, seed)
         ctx.save_for_backward(x, taps, bias)
         ctx.dropout, ctx.seed = float(dropout), seed
         return y
 
     @staticmethod
     def backward(ctx, grad_output):
-        lib = _lib.load()
         x, taps, bias = ctx.saved_tensors
-        N, L = x.shape
-        levels, _, k = taps.shape
-        dy = grad_output.contiguous()
-        if dy.dtype != x.dtype:
-            dy = dy.to(x.dtype)
-        dx = torch.empty_like(x)
-        partial = torch.empty((N, levels, 2, k + 1), dtype=torch.float32, device=x.device)
-        _lib.check(lib.wfs_tcn_bwd(_lib.ptr(x), _lib.ptr(dy), N, L, _lib.ptr(taps), _lib.ptr(bias), levels, k, _lib.ptr(dx),
-                                   _lib.ptr(partial), _lib.dtype_code(x), ctx.dropout, _lib.ptr(ctx.seed),
-                                   _lib.stream_ptr()))
+        k = taps.shape[2]
+        dx, partial = _tcn_launch_bwd(x, grad_output, taps, bias, ctx.dropout, ctx.seed)
         sums = partial.sum(0)
         return dx, sums[:, :, :k].contiguous(), sums[:, :, k].contiguous(), None, None
-
-
-def _ptr_table(cache, key, rows, device):
-    """Device array of pointer records for wfs_tcn_taps_* (six int64 per convolution), cached by the addresses it holds:
-    in a captured step parameters and gradient slots never move, so the table is built (one small H2D copy) during the
-    eager warm-up only."""
-    tab = cache.get(key)
-    if tab is None:
-        if len(cache) > 64:
-            cache.clear()
-        tab = torch.tensor(rows, dtype=torch.int64, device=device)
-        cache[key] = tab
-    return tab
 
 
 class FusedNormedTCNFunction(Function):
@@ -115,24 +111,17 @@ class FusedNormedTCNFunction(Function):
 
     @staticmethod
     def forward(ctx, x, k, dropout, seed, cache, *params):
-        lib = _lib.load()
         x = x.contiguous()
-        N, L = x.shape
         n_conv = len(params) // 3
         levels = n_conv // 2
-        rows = []
-        for c in range(n_conv):
-            v, g, b = params[3 * c: 3 * c + 3]
+        for v, g in zip(params[0::3], params[1::3]):
             assert v.dtype == torch.float32 and v.is_contiguous() and v.numel() == k and g.numel() == 1
-            rows.append([v.data_ptr(), g.data_ptr(), b.data_ptr() if b is not None else 0, 0, 0, 0])
-        tab = _ptr_table(cache, ("fwd",) + tuple(r[0] for r in rows) + tuple(r[1] for r in rows) + tuple(r[2] for r in rows),
-                         rows, x.device)
+        rows = _fused.fwd_rows(params, 3)
+        tab = _fused.ptr_table(cache, ("fwd",) + tuple(map(tuple, rows)), rows, x.device)
         taps = torch.empty((levels, 2, k), dtype=torch.float32, device=x.device)
         bias = torch.empty((levels, 2), dtype=torch.float32, device=x.device)
-        _lib.check(lib.wfs_tcn_taps_fwd(_lib.ptr(tab), n_conv, k, _lib.ptr(taps), _lib.ptr(bias), _lib.stream_ptr()))
-        y = torch.empty_like(x)
-        _lib.check(lib.wfs_tcn_fwd(_lib.ptr(x), N, L, _lib.ptr(taps), _lib.ptr(bias), levels, k, _lib.ptr(y),
-                                   _lib.dtype_code(x), float(dropout), _lib.ptr(seed), _lib.stream_ptr()))
+        _lib.check(_lib.load().wfs_tcn_taps_fwd(_lib.ptr(tab), n_conv, k, _lib.ptr(taps), _lib.ptr(bias), _lib.stream_ptr()))
+        y = _tcn_launch_fwd(x, taps, bias, dropout, seed)
         ctx.save_for_backward(x, taps, bias)
         ctx.params = params
         ctx.dropout, ctx.seed, ctx.k, ctx.cache = float(dropout), seed, k, cache
@@ -140,37 +129,18 @@ class FusedNormedTCNFunction(Function):
 
     @staticmethod
     def backward(ctx, grad_output):
-        from ..spconv.functional import grad_like
-        lib = _lib.load()
         x, taps, bias = ctx.saved_tensors
-        params, k = ctx.params, ctx.k
-        N, L = x.shape
-        levels = taps.shape[0]
-        n_conv = 2 * levels
-        dy = grad_output.contiguous()
-        if dy.dtype != x.dtype:
-            dy = dy.to(x.dtype)
-        dx = torch.empty_like(x)
-        partial = torch.empty((N, levels, 2, k + 1), dtype=torch.float32, device=x.device)
-        _lib.check(lib.wfs_tcn_bwd(_lib.ptr(x), _lib.ptr(dy), N, L, _lib.ptr(taps), _lib.ptr(bias), levels, k, _lib.ptr(dx),
-                                   _lib.ptr(partial), _lib.dtype_code(x), ctx.dropout, _lib.ptr(ctx.seed),
-                                   _lib.stream_ptr()))
-        grads, rows = [], []
-        for c in range(n_conv):
-            v, g, b = params[3 * c: 3 * c + 3]
-            need = ctx.needs_input_grad[5 + 3 * c: 5 + 3 * c + 3]
-            dv = grad_like(v) if need[0] else None
-            dg = grad_like(g) if need[1] else None
-            db = grad_like(b) if (b is not None and need[2]) else None
-            grads += [dv, dg, db]
-            rows.append([v.data_ptr(), g.data_ptr(), b.data_ptr() if b is not None else 0,
-                         dv.data_ptr() if dv is not None else 0, dg.data_ptr() if dg is not None else 0,
-                         db.data_ptr() if db is not None else 0])
+        first = FusedNormedTCNFunction.first_param
+        dx, partial = _tcn_launch_bwd(x, grad_output, taps, bias, ctx.dropout, ctx.seed)
+        rows, grads = _fused.bwd_rows(ctx, ctx.params, 3, first)
         if any(t is not None for t in grads):
-            tab = _ptr_table(ctx.cache, ("bwd",) + tuple(x_ for r in rows for x_ in r), rows, x.device)
-            _lib.check(lib.wfs_tcn_taps_bwd(_lib.ptr(tab), n_conv, k, _lib.ptr(partial), N, _lib.stream_ptr()))
-        return (dx, None, None, None, None) + tuple(grads)
+            tab = _fused.ptr_table(ctx.cache, ("bwd",) + tuple(map(tuple, rows)), rows, x.device)
+            _lib.check(_lib.load().wfs_tcn_taps_bwd(_lib.ptr(tab), len(rows), ctx.k, _lib.ptr(partial), x.shape[0],
+                                                    _lib.stream_ptr()))
+        return (dx,) + (None,) * (first - 1) + tuple(grads)
 
+
+FusedNormedTCNFunction.first_param = _fused.first_param(FusedNormedTCNFunction)
 
 TCNC_CALLS = [0]      # forward calls that ran on the multi-channel kernels (tests and tools read it)
 
@@ -188,11 +158,8 @@ class FusedMultiTCNFunction(Function):
         N, _c, L = x.shape
         levels = len(channels)
         ch = _lib.i32_array(channels)
-        rows = []
-        for c in range(len(params) // 3):
-            v, g, b = params[3 * c: 3 * c + 3]
-            rows.append([v.data_ptr(), g.data_ptr() if g is not None else 0, b.data_ptr() if b is not None else 0, 0, 0, 0])
-        tab = _ptr_table(cache, ("mfwd",) + tuple(x_ for r in rows for x_ in r[:3]), rows, x.device)
+        rows = _fused.fwd_rows(params, 3)
+        tab = _fused.ptr_table(cache, ("mfwd",) + tuple(map(tuple, rows)), rows, x.device)
         wts = torch.empty((int(lib.wfs_tcnc_weights_floats(c0, ch, levels, k)),), dtype=torch.float32, device=x.device)
         saved = torch.empty((int(lib.wfs_tcnc_saved_floats(N, L, c0, ch, levels)),), dtype=torch.float32, device=x.device)
         y = torch.empty((N, channels[-1], L), dtype=x.dtype, device=x.device)
@@ -207,36 +174,26 @@ class FusedMultiTCNFunction(Function):
 
     @staticmethod
     def backward(ctx, grad_output):
-        from ..spconv.functional import grad_like
         lib = _lib.load()
         x, wts, saved = ctx.saved_tensors
         c0, channels, k = ctx.plan
-        params = ctx.params
+        first = FusedMultiTCNFunction.first_param
         N, _c, L = x.shape
         levels = len(channels)
         ch = _lib.i32_array(channels)
-        dy = grad_output.contiguous()
-        if dy.dtype != x.dtype:
-            dy = dy.to(x.dtype)
+        dy = _fused.as_grad(grad_output, x.dtype)
         dx = torch.empty_like(x)
-        grads, rows = [], []
-        for c in range(len(params) // 3):
-            v, g, b = params[3 * c: 3 * c + 3]
-            need = ctx.needs_input_grad[7 + 3 * c: 7 + 3 * c + 3]
-            dv = grad_like(v) if need[0] else None
-            dg = grad_like(g) if (g is not None and need[1]) else None
-            db = grad_like(b) if (b is not None and need[2]) else None
-            grads += [dv, dg, db]
-            rows.append([v.data_ptr(), g.data_ptr() if g is not None else 0, b.data_ptr() if b is not None else 0,
-                         dv.data_ptr() if dv is not None else 0, dg.data_ptr() if dg is not None else 0,
-                         db.data_ptr() if db is not None else 0])
-        tab = _ptr_table(ctx.cache, ("mbwd",) + tuple(x_ for r in rows for x_ in r), rows, x.device)
+        rows, grads = _fused.bwd_rows(ctx, ctx.params, 3, first)
+        tab = _fused.ptr_table(ctx.cache, ("mbwd",) + tuple(map(tuple, rows)), rows, x.device)
         ws = torch.empty((int(lib.wfs_tcnc_bwd_workspace_floats(N, L, c0, ch, levels, k)),), dtype=torch.float32,
                          device=x.device)
         _lib.check(lib.wfs_tcnc_bwd(_lib.ptr(x), _lib.ptr(dy), N, L, c0, ch, levels, k, _lib.ptr(wts), _lib.ptr(saved),
                                     _lib.ptr(dx), _lib.ptr(ws), _lib.ptr(tab), _lib.dtype_code(x), ctx.dropout,
                                     _lib.ptr(ctx.seed), _lib.stream_ptr()))
-        return (dx, None, None, None, None, None, None) + tuple(grads)
+        return (dx,) + (None,) * (first - 1) + tuple(grads)
+
+
+FusedMultiTCNFunction.first_param = _fused.first_param(FusedMultiTCNFunction)
 
 
 class TemporalConvNet(nn.Module):
@@ -271,27 +228,23 @@ class TemporalConvNet(nn.Module):
     def _multi_params(self):
         """(v, g, b) per convolution in the kernels' order; the downsample as (weight, None, bias).  None unless every
         tensor is contiguous fp32 on the GPU."""
-        out = []
+        trips = []
         for blk in self.network:
-            trip = [(conv.weight_v, conv.weight_g, conv.bias) for conv in blk.convs]
+            trips += [(conv.weight_v, conv.weight_g, conv.bias) for conv in blk.convs]
             if blk.downsample is not None:
-                trip.append((blk.downsample.weight, None, blk.downsample.bias))
-            for t3 in trip:
-                for t in t3:
-                    if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda):
-                        return None
-                out += list(t3)
-        return out
+                trips.append((blk.downsample.weight, None, blk.downsample.bias))
+        return _fused.kernel_params(trips)
+
+    def _dropout_args(self, x):
+        """(p, seed) of this call: dropout runs in training mode only, on ONE draw from torch's generator."""
+        if self.training and self.dropout > 0:
+            return self.dropout, _fused.draw_seed(x.device)
+        return 0.0, None
 
     def _forward_multi(self, x):
-        seed, p = None, 0.0
-        if self.training and self.dropout > 0:
-            seed = torch.randint(-2 ** 62, 2 ** 62, (1,), dtype=torch.int64, device=x.device)
-            p = self.dropout
-        if not hasattr(self, "_ptr_cache"):
-            self._ptr_cache = {}
+        p, seed = self._dropout_args(x)
         return FusedMultiTCNFunction.apply(x, self.num_inputs, tuple(self.channels), self.kernel_size, p, seed,
-                                           self._ptr_cache, *self._multi_params())
+                                           _fused.ptr_cache(self), *self._multi_params())
 
     def _can_fuse(self, x):
         levels, k = len(self.network), self.kernel_size
@@ -318,31 +271,16 @@ class TemporalConvNet(nn.Module):
 
     def _norm_params(self):
         """(weight_v, weight_g, bias) of every convolution, level by level -- None unless they are what the fused
-        weight-norm kernels read: contiguous fp32 tensors on one device."""
-        out = []
-        for blk in self.network:
-            for conv in blk.convs:
-                v, g, b = conv.weight_v, conv.weight_g, conv.bias
-                for t in (v, g) + ((b,) if b is not None else ()):
-                    if t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda:
-                        return None
-                out += [v, g, b]
-        return out
+        weight-norm kernels read: contiguous fp32 tensors on the GPU."""
+        return _fused.kernel_params((conv.weight_v, conv.weight_g, conv.bias) for blk in self.network for conv in blk.convs)
 
     def forward(self, x):
         if self._can_fuse(x):
             params = self._norm_params()
             if params is not None:
                 rows = x.reshape(x.shape[0], x.shape[2])
-                seed, p = None, 0.0
-                if self.training and self.dropout > 0:
-                    # a fresh 64-bit seed per call from torch's CUDA generator (reproducible under torch.manual_seed, and a
-                    # captured graph draws a new one per replay); the kernels derive every mask from it
-                    seed = torch.randint(-2 ** 62, 2 ** 62, (1,), dtype=torch.int64, device=x.device)
-                    p = self.dropout
-                if not hasattr(self, "_ptr_cache"):
-                    self._ptr_cache = {}
-                return FusedNormedTCNFunction.apply(rows, self.kernel_size, p, seed, self._ptr_cache, *params).reshape(x.shape)
+                p, seed = self._dropout_args(x)
+                return FusedNormedTCNFunction.apply(rows, self.kernel_size, p, seed, _fused.ptr_cache(self), *params).reshape(x.shape)
         if self.fused and not self.single_channel and self._can_fuse_multi(x):
             return self._forward_multi(x)
         return self.network(x)
