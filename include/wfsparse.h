@@ -549,6 +549,48 @@ int wfs_tcnc_bwd(const void *X, const void *dY, int64_t N, int32_t L, int32_t c0
                  int32_t levels, int32_t k, const float *wts, const float *saved, void *dX, float *workspace,
                  const void *param_ptrs, int32_t dtype, float dropout_p, const int64_t *seed_dev, void *stream);
 
+/* dense Conv1d + BatchNorm1d + ReLU stack (csrc/conv1d.hip) -------------------------------------------------
+ * The reference's Conv1DNet (src/models/ConvBlocks.py:176-217), the front end of ConvWaveformNet: per layer i of
+ * `layers`, nn.Conv1d(c[i], channels[i], fs[i], stride = st[i], padding = pd[i]) with bias (non-causal, zero padded,
+ * dilation 1), nn.BatchNorm1d(channels[i]) with affine parameters and running statistics, nn.ReLU; c[0] = c0,
+ * c[i + 1] = channels[i]; L[i + 1] = (L[i] + 2 pd[i] - fs[i]) / st[i] + 1.  ONE call covers the whole stack:
+ * X [N][c0][L] -> Y [N][channels[layers-1]][L[layers]] in `dtype`; fp32 arithmetic, statistics in fp64.
+ * channels / fs / st / pd / momentum / eps are HOST arrays of `layers` entries.  Bounds: every channel count in
+ * 1 .. WFS_CONV1D_MAX_CHANNELS, 1 <= fs <= WFS_CONV1D_MAX_K, 1 <= st <= WFS_CONV1D_MAX_STRIDE, 0 <= pd < fs,
+ * 1 <= layers <= WFS_CONV1D_MAX_LAYERS, 1 <= L <= WFS_CONV1D_MAX_L, every L[i] >= 1; wfs_conv1d_ok says WFS_OK or
+ * WFS_EINVAL (and every entry point refuses the same shapes).
+ * param_ptrs: DEVICE array of `layers` records of fourteen device addresses: {conv.weight [cout][cin][fs], conv.bias
+ * [cout] or 0, bn.weight, bn.bias, running_mean, running_var (fp32 [cout]), num_batches_tracked (int64 [1] or 0)},
+ * then the gradient addresses of the first four and three unused words.  A gradient address 0 is not written.
+ * n_valid_dev: DEVICE count of valid rows (NULL: all N).  Rows at or beyond it are never read: they add nothing to
+ * the batch statistics or to any parameter gradient, and get Y = 0 and dX = 0.
+ * wfs_conv1d_fwd: layers + 1 launches.  training != 0: batch statistics per channel over n_valid x L[i + 1] elements
+ *   (biased variance), and running_mean / running_var (unbiased, momentum[i]) / num_batches_tracked updated on the
+ *   device; training == 0: the running statistics.  `saved` [wfs_conv1d_saved_floats] fp32 keeps every layer's pre-BN
+ *   convolution output and the statistics used, for the backward.
+ * wfs_conv1d_bwd: layers + 2 launches.  dX (dtype; NULL: not wanted) from dY (dtype) and `saved`; d conv.weight,
+ *   d conv.bias, d bn.weight, d bn.bias straight into the gradient slots; workspace [wfs_conv1d_bwd_workspace_floats]
+ *   fp32.  `training` as in the forward call.  Deterministic (fixed-order partial sums, no atomics).  N >= 1.  */
+#define WFS_CONV1D_MAX_CHANNELS 64
+#define WFS_CONV1D_MAX_K 16
+#define WFS_CONV1D_MAX_STRIDE 8
+#define WFS_CONV1D_MAX_LAYERS 8
+#define WFS_CONV1D_MAX_L 4096
+int wfs_conv1d_ok(int32_t c0, const int32_t *channels, const int32_t *fs, const int32_t *st, const int32_t *pd,
+                  int32_t layers, int32_t L, int32_t dtype);
+size_t wfs_conv1d_saved_floats(int64_t N, int32_t L, int32_t c0, const int32_t *channels, const int32_t *fs,
+                               const int32_t *st, const int32_t *pd, int32_t layers);
+size_t wfs_conv1d_bwd_workspace_floats(int64_t N, int32_t L, int32_t c0, const int32_t *channels, const int32_t *fs,
+                                       const int32_t *st, const int32_t *pd, int32_t layers);
+int wfs_conv1d_fwd(const void *X, int64_t N, int32_t L, int32_t c0, const int32_t *channels, const int32_t *fs,
+                   const int32_t *st, const int32_t *pd, int32_t layers, const void *param_ptrs, const float *momentum,
+                   const float *eps, int32_t training, float *saved, void *Y, int32_t dtype, const int64_t *n_valid_dev,
+                   void *stream);
+int wfs_conv1d_bwd(const void *X, const void *dY, int64_t N, int32_t L, int32_t c0, const int32_t *channels,
+                   const int32_t *fs, const int32_t *st, const int32_t *pd, int32_t layers, const void *param_ptrs,
+                   int32_t training, const float *saved, void *dX, float *workspace, int32_t dtype,
+                   const int64_t *n_valid_dev, void *stream);
+
 /* recurrent front end (csrc/rnn.hip) ------------------------------------------------------------------------
  * torch.nn.RNN(I, H, layers, nonlinearity, bias, dropout, bidirectional, batch_first=True) as the reference's
  * RecurrentNet builds it (src/models/RecurrentBlocks.py): per layer l and direction d (0 forward in t, 1 backward)

@@ -18,6 +18,7 @@ TIMER_GATHER_CONV, TIMER_GATHER_DW, TIMER_RULEBOOK, TIMER_CONV_BACKWARD = 0, 1, 
 
 c_i32p = ctypes.POINTER(ctypes.c_int32)
 c_i64p = ctypes.POINTER(ctypes.c_int64)
+c_f32p = ctypes.POINTER(ctypes.c_float)
 _vp, _i32, _i64, _sz = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_size_t
 
 
@@ -121,6 +122,13 @@ SIGNATURES = {
                                     _vp]),
     "wfs_tcnc_bwd": (ctypes.c_int, [_vp, _vp, _i64, _i32, _i32, c_i32p, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32,
                                     ctypes.c_float, _vp, _vp]),
+    "wfs_conv1d_ok": (ctypes.c_int, [_i32, c_i32p, c_i32p, c_i32p, c_i32p, _i32, _i32, _i32]),
+    "wfs_conv1d_saved_floats": (_sz, [_i64, _i32, _i32, c_i32p, c_i32p, c_i32p, c_i32p, _i32]),
+    "wfs_conv1d_bwd_workspace_floats": (_sz, [_i64, _i32, _i32, c_i32p, c_i32p, c_i32p, c_i32p, _i32]),
+    "wfs_conv1d_fwd": (ctypes.c_int, [_vp, _i64, _i32, _i32, c_i32p, c_i32p, c_i32p, c_i32p, _i32, _vp, c_f32p, c_f32p,
+                                      _i32, _vp, _vp, _i32, _vp, _vp]),
+    "wfs_conv1d_bwd": (ctypes.c_int, [_vp, _vp, _i64, _i32, _i32, c_i32p, c_i32p, c_i32p, c_i32p, _i32, _vp, _i32, _vp,
+                                      _vp, _vp, _i32, _vp, _vp]),
     "wfs_rnn_ok": (ctypes.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, _i32]),
     "wfs_rnn_n_params": (ctypes.c_int, [_i32, _i32]),
     "wfs_rnn_saved_floats": (_sz, [_i64, _i32, _i32, _i32, _i32, _i32]),

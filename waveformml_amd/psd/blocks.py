@@ -1,6 +1,6 @@
 """Layer-schedule generators for the PSD net: host-side mirror of the reference's builders
 (src/models/SPConvBlocks.py:411-727 ``SparseConv2DBlock`` versions 0-3, :730-948 ``SparseConv2DPreserve`` versions 0-2,
-src/models/ConvBlocks.py:82-102 ``LinearBlock``, src/utils/ModelValidation.py:119-177 output-size arithmetic).  Pure
+src/models/ConvBlocks.py:82-102 ``LinearBlock``, :49-62 ``LinearPlanes``, src/utils/ModelValidation.py:119-177 output-size arithmetic).  Pure
 Python arithmetic + constructor calls on whatever module is handed in as ``spconv``; the golden schedules in
 tests/golden/reference_callers.json and tests/golden/block_schedules.json were captured from the reference's own
 generators (tests/golden/make_reference_goldens.py, make_block_goldens.py).
@@ -258,3 +258,20 @@ class LinearBlock(object):
         self.widths = [int(round(nin * pow(factor, i))) for i in range(n + 1)]
         self.alg = [nn.Linear(self.widths[i], self.widths[i + 1]) for i in range(n)]
         self.func = nn.Sequential(*self.alg)
+
+
+class LinearPlanes(nn.Module):
+    """nn.Linear layers through the given widths, ``activation`` (one shared module) after EVERY one of them, the last
+    included (reference ConvBlocks.py:49-62)."""
+
+    def __init__(self, planes, activation=None):
+        super().__init__()
+        alg = []
+        for i in range(len(planes) - 1):
+            alg.append(nn.Linear(int(round(planes[i])), int(round(planes[i + 1]))))
+            if activation is not None:
+                alg.append(activation)
+        self.net = nn.Sequential(*alg)
+
+    def forward(self, x):
+        return self.net(x)

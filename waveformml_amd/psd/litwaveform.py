@@ -13,7 +13,8 @@ reduction='none' criterion summed under a row mask, divided by the count -- so p
 and receive a zero gradient whatever the criterion (``ignore_index`` covers CrossEntropy alone).
 
 ``net_class`` ``WaveformModels.RecurrentWaveformNet`` gets its rows as [N, n_samples, 1] (``squeeze_index`` 2), every
-other net as [N, 1, n_samples].
+other net as [N, 1, n_samples].  A net that declares ``takes_n_valid`` (ConvWaveformNet: BatchNorm statistics) is handed
+the batch's valid-row count -- a device tensor in a captured step, else None -- in its ``n_valid`` attribute for the call.
 
 Out of scope: TensorEvaluator (and the evaluator plumbing of test_step) and ``write_script`` / TorchScript export.
 """
@@ -106,8 +107,16 @@ class LitWaveform(nn.Module):
             f = torch.cat((f, coords), dim=1)
         return f
 
-    def _predict(self, f, target, phys=False):
-        predictions = self.model(f.unsqueeze(self.squeeze_index)).squeeze(1)
+    def _predict(self, f, target, phys=False, n_valid=None):
+        if getattr(self.model, "takes_n_valid", False):
+            # a net with batch statistics: the padding rows of a captured batch must stay out of them
+            self.model.n_valid = n_valid
+            try:
+                predictions = self.model(f.unsqueeze(self.squeeze_index)).squeeze(1)
+            finally:
+                self.model.n_valid = None
+        else:
+            predictions = self.model(f.unsqueeze(self.squeeze_index)).squeeze(1)
         if predictions.dim() == 2 and (target.dim() == 1 or (target.dim() == 2 and phys)):
             predictions = predictions.squeeze(1)
         if predictions.dtype != torch.float32:
@@ -137,14 +146,14 @@ class LitWaveform(nn.Module):
 
     def training_step(self, batch, batch_idx):
         c, f, n_valid, target = self._unpack(batch)
-        predictions = self._predict(self._rows(c, f), target)
+        predictions = self._predict(self._rows(c, f), target, n_valid=n_valid)
         loss = self._loss(predictions, target, n_valid)
         self.log("train_loss", loss, on_epoch=True, prog_bar=True, logger=True)
         return loss
 
     def validation_step(self, batch, batch_idx):
         c, f, n_valid, target = self._unpack(batch)
-        predictions = self._predict(self._rows(c, f), target)
+        predictions = self._predict(self._rows(c, f), target, n_valid=n_valid)
         loss = self._loss(predictions, target, n_valid)
         results = {"val_loss": loss}
         if self.use_accuracy:
