@@ -591,6 +591,69 @@ int wfs_conv1d_bwd(const void *X, const void *dY, int64_t N, int32_t L, int32_t 
                    int32_t training, const float *saved, void *dX, float *workspace, int32_t dtype,
                    const int64_t *n_valid_dev, void *stream);
 
+/* dense Conv2d + BatchNorm2d + ReLU (+ Dropout) stack on event maps (csrc/conv2d.hip) ------------------------
+ * The reference's Conv2DBlock (src/models/ConvBlocks.py:220-289) under DenseConvNet: per layer i of `layers`,
+ * nn.Conv2d(c[i], channels[i], (fs, fs), (st, st), pd, (dil, dil)) with or without bias (zero padded),
+ * nn.BatchNorm2d(channels[i]) with affine parameters and running statistics, nn.ReLU, and nn.Dropout(dropout_p[i])
+ * where dropout_p[i] > 0; c[0] = c0, H[i + 1] = (H[i] + 2 pd - dil (fs - 1) - 1) / st + 1, W alike.  ONE call covers the
+ * whole stack.  X is channels-LAST, [B][H][W][c0] (what wfs_densify_rows writes; torch's channels_last memory format of
+ * an NCHW tensor); Y and dY are channels-FIRST, [B][channels[layers-1]][H'][W'] (the order the reference flattens); dX
+ * is channels-last like X.  All in `dtype`.  fp32 accumulation on the matrix cores (16-bit rows: 16-bit MFMA; the
+ * forward keeps the filters in three and the activations between layers in two 16-bit pieces so that the ReLU masks
+ * are those of an fp32 run, the backward rounds the filters and the gradients between layers to the row type; fp32
+ * rows: v_mfma_f32_32x32x2_f32, an fp32 FMA chain); statistics in fp64.
+ * channels / fs / st / pd / dil / momentum / eps / dropout_p are HOST arrays of `layers` entries (dropout_p NULL: none).
+ * Bounds: channel counts 1 .. WFS_CONV2D_MAX_CHANNELS, 1 <= fs <= WFS_CONV2D_MAX_K, 1 <= st <= WFS_CONV2D_MAX_STRIDE,
+ * 1 <= dil <= WFS_CONV2D_MAX_DILATION, 0 <= pd <= dil (fs - 1), 1 <= layers <= WFS_CONV2D_MAX_LAYERS,
+ * 1 <= H, W <= WFS_CONV2D_MAX_HW, every layer's output >= 1 x 1, 1 <= B <= WFS_CONV2D_MAX_BATCH, and for a training
+ * call B H' W' >= 2 at every layer (torch raises below that); wfs_conv2d_ok says WFS_OK or WFS_EINVAL (and every entry
+ * point refuses the same shapes).
+ * param_ptrs: DEVICE array of `layers` records of fourteen device addresses: {conv.weight [cout][cin][fs][fs],
+ * conv.bias [cout] or 0, bn.weight, bn.bias, running_mean, running_var (fp32 [cout]), num_batches_tracked (int64 [1]
+ * or 0)}, then the gradient addresses of the first four and three unused words.  A gradient address 0 is not written.
+ * wfs_conv2d_fwd: 3 layers + 1 launches (training) or 2 layers + 1 (eval).  training != 0: batch statistics per channel
+ *   over B H' W' elements (biased variance), running_mean / running_var (unbiased, momentum[i]) / num_batches_tracked
+ *   updated on the device, dropout applied; training == 0: the running statistics, no dropout.  `saved`
+ *   [wfs_conv2d_saved_floats] fp32 keeps every layer's pre-BN convolution output (fp32), the statistics used, the
+ *   activations between the layers (row type) and the repacked filters, for the backward.
+ * wfs_conv2d_bwd: 4 layers + 1 launches, one more when dX is wanted (dX NULL: the first layer's input gradient is not
+ *   computed).  d conv.weight, d conv.bias, d bn.weight, d bn.bias straight into the gradient slots; workspace
+ *   [wfs_conv2d_bwd_workspace_floats] fp32.  `training`, dropout_p and seed_dev as in the forward call.  Deterministic
+ *   (fixed-order partial sums, no float atomics).
+ * Dropout: the dropout generator above; element (event b, channel c, y, x) of layer l's output has the counter
+ *       ctr = l << 44 | ((b C_l + c) H_l + y) W_l + x        (the element's flat index in the layer's output as NCHW)
+ *   Nothing is stored: the backward rebuilds the masks from the seed.
+ * wfs_densify_rows: rows [n_cap][C] (dtype) at coords int32 [n_cap][3] = (x, y, event) -> out [B][H][W][C], every cell
+ *   written by ONE launch (cells without a row: zeros; no memset needed).  Rows at or beyond *n_valid_dev (NULL: all
+ *   n_cap) are never read; a row whose coordinate lies outside [0, H) x [0, W) x [0, B) is skipped and never
+ *   dereferenced.  Rows with EQUAL coordinates are summed (as to_dense does), in row order, in fp32, rounded once: no
+ *   float atomics, the result does not depend on scheduling.  No backward: the rows are inputs.
+ * Nothing here allocates, synchronises or reads back: every launch goes to `stream` (capturable).  */
+#define WFS_CONV2D_MAX_CHANNELS 512
+#define WFS_CONV2D_MAX_K 5
+#define WFS_CONV2D_MAX_STRIDE 3
+#define WFS_CONV2D_MAX_DILATION 4
+#define WFS_CONV2D_MAX_LAYERS 8
+#define WFS_CONV2D_MAX_HW 32
+#define WFS_CONV2D_MAX_BATCH 2048
+int wfs_conv2d_ok(int32_t c0, const int32_t *channels, const int32_t *fs, const int32_t *st, const int32_t *pd,
+                  const int32_t *dil, int32_t layers, int64_t B, int32_t H, int32_t W, int32_t training, int32_t dtype);
+size_t wfs_conv2d_saved_floats(int64_t B, int32_t H, int32_t W, int32_t c0, const int32_t *channels, const int32_t *fs,
+                               const int32_t *st, const int32_t *pd, const int32_t *dil, int32_t layers, int32_t dtype);
+size_t wfs_conv2d_bwd_workspace_floats(int64_t B, int32_t H, int32_t W, int32_t c0, const int32_t *channels,
+                                       const int32_t *fs, const int32_t *st, const int32_t *pd, const int32_t *dil,
+                                       int32_t layers, int32_t dtype);
+int wfs_conv2d_fwd(const void *X, int64_t B, int32_t H, int32_t W, int32_t c0, const int32_t *channels, const int32_t *fs,
+                   const int32_t *st, const int32_t *pd, const int32_t *dil, int32_t layers, const void *param_ptrs,
+                   const float *momentum, const float *eps, const float *dropout_p, const int64_t *seed_dev,
+                   int32_t training, float *saved, void *Y, int32_t dtype, void *stream);
+int wfs_conv2d_bwd(const void *X, const void *dY, int64_t B, int32_t H, int32_t W, int32_t c0, const int32_t *channels,
+                   const int32_t *fs, const int32_t *st, const int32_t *pd, const int32_t *dil, int32_t layers,
+                   const void *param_ptrs, const float *dropout_p, const int64_t *seed_dev, int32_t training,
+                   const float *saved, void *dX, float *workspace, int32_t dtype, void *stream);
+int wfs_densify_rows(const void *rows, const int32_t *coords, int64_t n_cap, int32_t C, int64_t B, int32_t H, int32_t W,
+                     const int64_t *n_valid_dev, void *out, int32_t dtype, void *stream);
+
 /* recurrent front end (csrc/rnn.hip) ------------------------------------------------------------------------
  * torch.nn.RNN(I, H, layers, nonlinearity, bias, dropout, bidirectional, batch_first=True) as the reference's
  * RecurrentNet builds it (src/models/RecurrentBlocks.py): per layer l and direction d (0 forward in t, 1 backward)

@@ -129,6 +129,15 @@ SIGNATURES = {
                                       _i32, _vp, _vp, _i32, _vp, _vp]),
     "wfs_conv1d_bwd": (ctypes.c_int, [_vp, _vp, _i64, _i32, _i32, c_i32p, c_i32p, c_i32p, c_i32p, _i32, _vp, _i32, _vp,
                                       _vp, _vp, _i32, _vp, _vp]),
+    "wfs_conv2d_ok": (ctypes.c_int, [_i32, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, _i32, _i64, _i32, _i32, _i32, _i32]),
+    "wfs_conv2d_saved_floats": (_sz, [_i64, _i32, _i32, _i32, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, _i32, _i32]),
+    "wfs_conv2d_bwd_workspace_floats": (_sz, [_i64, _i32, _i32, _i32, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, _i32,
+                                              _i32]),
+    "wfs_conv2d_fwd": (ctypes.c_int, [_vp, _i64, _i32, _i32, _i32, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, _i32, _vp,
+                                      c_f32p, c_f32p, c_f32p, _vp, _i32, _vp, _vp, _i32, _vp]),
+    "wfs_conv2d_bwd": (ctypes.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, _i32, _vp,
+                                      c_f32p, _vp, _i32, _vp, _vp, _vp, _i32, _vp]),
+    "wfs_densify_rows": (ctypes.c_int, [_vp, _vp, _i64, _i32, _i64, _i32, _i32, _vp, _vp, _i32, _vp]),
     "wfs_rnn_ok": (ctypes.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, _i32]),
     "wfs_rnn_n_params": (ctypes.c_int, [_i32, _i32]),
     "wfs_rnn_saved_floats": (_sz, [_i64, _i32, _i32, _i32, _i32, _i32]),
