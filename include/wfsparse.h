@@ -771,6 +771,47 @@ int wfs_load_batch(const int32_t *coords, int64_t n, int32_t cols, const int32_t
                    const int64_t *labels, int64_t *labels_dst, int64_t B, int64_t *n_valid_dst,
                    int32_t *event_offsets, int32_t events, void *stream);
 
+/* evaluation statistics (csrc/evalstats.hip) ----------------------------------------------------------
+ * The per-batch work of the reference's PSDEvaluator.add (src/evaluation/PSDEvaluator.py:101-198) on the device.  These
+ * entry points are additions: no existing signature or struct changes, so WFS_ABI_VERSION stays.
+ *
+ * wfs_event_pulse_stats (two launches: event offsets, then one workgroup per event): what average_pulse computes
+ * (src/utils/SparseUtils.py:405-487).
+ *   coords      int32 [n_cap, 3] = (x, y, event), rows of an event contiguous, event column non-decreasing in [0, E)
+ *   rows        [n_cap, 2T] of `dtype`, left PMT first; only read.  1 <= T <= WFS_EVAL_MAX_SAMPLES
+ *   n_dev       valid rows as everywhere (NULL = n_cap); rows beyond it are never read
+ *   gains       double [nx, ny, 2]; seg_status float [nx, ny] (0.5 = single-ended)
+ *   offsets     int32 [E + 1] scratch (first row of every event), zero-initialised once by the caller
+ *   rowstats    double [n_cap, 4] scratch
+ *   outputs     avg_coo double [E, 2]; summed float [E, 2T]; stats float [6, E] = x, y, dt, E spreads, time variance,
+ *               sample variance; multiplicity, n_se int32 [E]; psdl, psdr, energy float [E] (energy = half the summed
+ *               pulse's sum); features float [9, E] in the order of the reference's metric_names.  An event without
+ *               rows gets multiplicity 0 and zeros.  n_se of event E - 1 is written as 0 unless fix_last_n_se (the
+ *               reference's loop never stores it).
+ *   flags       int32 [1], STICKY bits: 1 event column unsorted / out of range, 2 segment outside [nx, ny],
+ *               4 (set by wfs_eval_accumulate) prediction or label outside [0, n_classes)
+ * wfs_eval_accumulate (one launch): folds the batch into persistent tables.  tables int64
+ *   [wfs_eval_table_ints], in this order, count table then match-sum table for the first three:
+ *   mult [n_mult + 2] x 2, ene_psd [(n_bins + 2)^2] x 2 (every event twice: psdl and psdr), pos [(nx + 2)(ny + 2)] x 2,
+ *   confusion_energy [n_confusion + 1, C, C], confusion_SE [n_se_max + 2, C, C] (label-major), n_wfs [C + 1],
+ *   n_labelled_wfs [C].  Bin edges are the reference's: the first j with j * width + low > value in fp64.
+ *   sum_wf double [C + 1, 2T] (all, then by label), sum_labelled double [C, 2T] (by prediction): += the batch's summed
+ *   pulses, added in event order by one thread per element (deterministic). */
+#define WFS_EVAL_MAX_SAMPLES 512
+size_t wfs_eval_table_ints(int32_t n_bins, int32_t n_mult, int32_t n_confusion, int32_t n_se_max, int32_t nx,
+                           int32_t ny, int32_t n_classes);
+int wfs_event_pulse_stats(const int32_t *coords, const void *rows, int64_t n_cap, int32_t T, int32_t dtype,
+                          const int64_t *n_dev, int32_t E, const double *gains, const float *seg_status, int32_t nx,
+                          int32_t ny, int32_t fix_last_n_se, int32_t *offsets, double *rowstats, double *avg_coo,
+                          float *summed, float *stats, int32_t *multiplicity, int32_t *n_se, float *psdl, float *psdr,
+                          float *energy, float *features, int32_t *flags, void *stream);
+int wfs_eval_accumulate(int32_t E, int32_t T, int32_t n_classes, const double *avg_coo, const float *summed,
+                        const int32_t *multiplicity, const int32_t *n_se, const float *psdl, const float *psdr,
+                        const float *energy, const int64_t *predictions, const int64_t *labels, int32_t n_bins,
+                        int32_t n_mult, int32_t n_confusion, int32_t n_se_max, int32_t nx, int32_t ny, double emin,
+                        double emax, double psd_min, double psd_max, int64_t *tables, double *sum_wf,
+                        double *sum_labelled, int32_t *flags, void *stream);
+
 /* opt-in per-kernel timing (HIP events on the launch stream), used by bench.py's roofline ---- */
 #define WFS_TIMER_GATHER_CONV 0
 #define WFS_TIMER_GATHER_DW 1

@@ -157,6 +157,12 @@ SIGNATURES = {
     "wfs_adam_step": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "wfs_load_batch": (ctypes.c_int, [_vp, _i64, _i32, c_i32p, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i32,
                                       _vp]),
+    "wfs_eval_table_ints": (_sz, [_i32, _i32, _i32, _i32, _i32, _i32, _i32]),
+    "wfs_event_pulse_stats": (ctypes.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp,
+                                             _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "wfs_eval_accumulate": (ctypes.c_int, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32,
+                                           _i32, _i32, _i32, _i32, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                           ctypes.c_double, _vp, _vp, _vp, _vp, _vp]),
     "wfs_timing_enable": (ctypes.c_int, [_i32]),
     "wfs_timing_read": (ctypes.c_int, [_i32, ctypes.POINTER(ctypes.c_double), c_i64p]),
 }

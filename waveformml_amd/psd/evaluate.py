@@ -22,9 +22,12 @@ def _score(module, logits, labels):
 
 
 @torch.no_grad()
-def test_loop(module, loader, device, feature_dtype=None, capture=False):
+def test_loop(module, loader, device, feature_dtype=None, capture=False, evaluator=None):
     """``capture=True``: the forward runs as replays of one captured HIP graph (psd/graph.GraphedEvalStep); a batch that
-    does not fit the captured capacities takes the ordinary ``test_step``."""
+    does not fit the captured capacities takes the ordinary ``test_step``.
+    ``evaluator``: a psd/evaluator.PSDEvaluator; every batch is handed to its ``add`` with the logits and their argmax, as
+    the reference's ``test_step`` does (src/engineering/LitPSD.py:142-150) -- on the stream the forward ran on, without a
+    read-back -- and the returned dict gains ``"evaluation": evaluator.results()``."""
     module.to(device)
     module.eval()
     tot, acc, n = 0.0, 0.0, 0          # tot / acc become device scalars: one read-back at the end of the loop
@@ -38,10 +41,18 @@ def test_loop(module, loader, device, feature_dtype=None, capture=False):
                     from .graph import GraphedEvalStep
                     step = GraphedEvalStep(module, batch)
                 if step.fits(batch):
-                    loss, a = _score(module, step(batch, module.occlude_index), batch[1])
+                    logits = step(batch, module.occlude_index)
+                    loss, a = _score(module, logits, batch[1])
                     tot, acc, n = tot + loss * b, acc + a * b, n + b
+                    if evaluator is not None:
+                        # the static buffers hold the batch as the net saw it (occluded column included)
+                        evaluator.add(([step.coords, step.feats, step.n_valid], step.labels), logits,
+                                      torch.argmax(logits, dim=1))
                     continue
             res = module.test_step(batch, i)
+            if evaluator is not None:
+                logits = module.last_test_logits
+                evaluator.add(batch, logits, torch.argmax(logits, dim=1))
             tot = tot + res["test_loss"].detach().float() * b
             acc = acc + res["test_acc"].detach().float() * b
             n += b
@@ -58,7 +69,13 @@ def test_loop(module, loader, device, feature_dtype=None, capture=False):
                             torch.tensor(float(n), dtype=torch.float64, device=device)])
         dist.all_reduce(sums, op=dist.ReduceOp.SUM)
         tot, acc, n = float(sums[0]), float(sums[1]), int(sums[2])
-    return {"test_loss": float(tot) / max(n, 1), "test_acc": float(acc) / max(n, 1), "events": n}
+        if evaluator is not None:
+            for t in evaluator.state_tensors():          # integer tables and fp64 pulse sums: sums over batches
+                dist.all_reduce(t, op=dist.ReduceOp.SUM)
+    out = {"test_loss": float(tot) / max(n, 1), "test_acc": float(acc) / max(n, 1), "events": n}
+    if evaluator is not None:
+        out["evaluation"] = evaluator.results()
+    return out
 
 
 @torch.no_grad()

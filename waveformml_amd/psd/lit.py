@@ -32,6 +32,21 @@ class LitPSD(nn.Module):
         self.softmax = nn.LogSoftmax(dim=1)
         self.logged = {}
         self.optimizer_parameters = None      # set to [flat parameter] by ddp.FlatGradAllReducer(flatten=True)
+        self.last_test_logits = None          # test_step's logits, for evaluate.test_loop(..., evaluator=...)
+        self._evaluator = None
+
+    @property
+    def evaluator(self):
+        """The reference's ``self.evaluator = PSDEvaluator(system_config.type_names, ...)`` (src/engineering/LitPSD.py:
+        42-48), built on first use on the device the model lives on; ``None`` when the config names no types.  Nothing
+        calls it implicitly: hand it to ``evaluate.test_loop(..., evaluator=module.evaluator)``."""
+        names = getattr(self.config.system_config, "type_names", None)
+        if self._evaluator is None and names:
+            from .evaluator import PSDEvaluator
+            device = next(self.model.parameters()).device
+            self._evaluator = PSDEvaluator(list(names), device,
+                                           n_samples=getattr(self.config.system_config, "n_samples", 150))
+        return self._evaluator
 
     def forward(self, x):
         return self.model(x)
@@ -122,6 +137,7 @@ class LitPSD(nn.Module):
         if self.occlude_index:                       # falsy for index 0, exactly as the reference (:134)
             f[:, self.occlude_index] = 0
         predictions = self._predict(c, f, target, n_valid)
+        self.last_test_logits = predictions.detach()
         loss = self.criterion.forward(predictions, target)
         pred = torch.argmax(self.softmax(predictions), dim=1)
         acc = (pred == target).float().mean()
