@@ -812,6 +812,51 @@ int wfs_eval_accumulate(int32_t E, int32_t T, int32_t n_classes, const double *a
                         double emax, double psd_min, double psd_max, int64_t *tables, double *sum_wf,
                         double *sum_labelled, int32_t *flags, void *stream);
 
+/* per-segment evaluation tables (csrc/segstats.hip) ---------------------------------------------------
+ * The per-batch work of the reference's ZEvaluatorWF.add and EnergyEvaluatorWF.add without a calibration group
+ * (src/evaluation/ZEvaluator.py:528-562, EnergyEvaluator.py:132-145) on the device: the row walks z_deviation,
+ * z_deviation_with_E, z_error and E_deviation of src/utils/SparseUtils.py.  Additions only: WFS_ABI_VERSION stays.
+ *
+ * Both entry points make two launches (event offsets, then one thread per row) on `stream` and read nothing back.
+ *   coords      int32 [n_cap, 3] = (x, y, event), event column non-decreasing in [0, B); n_dev as everywhere
+ *   maps        a [B, nx, ny] plane of a [B, P, nx, ny] tensor of `dtype`: element (b, x, y) of plane `plane` is
+ *               base[b * bs + plane * ps + x * ny + y] (bs, ps in elements); only read.  energy may be NULL.
+ *   seg_status  float [nx, ny]: > 0 = the "single" tables, else the "dual" ones
+ *   sample_segs int32 [n_sample, 2] on the device (wfs_seg_z_accumulate)
+ *   offsets     int32 [B + 1] scratch, zero-initialised once by the caller
+ *   A row's multiplicity is the length of its event's run; its column is mult - 1 for 0 < mult <= nmult, else nmult.
+ *   tables      int64, persistent.  Every (count, sum) pair is a count table followed by a sum table of the same
+ *               shape; a sum cell holds the sum of round(dev * WFS_SEG_FIXED_ONE), added with integer atomics (exact,
+ *               order-independent).  wfs_seg_z_table_ints, in this order: seg_mult_mae [nx, ny, nmult + 1] pair,
+ *               z_mult_mae_single, z_mult_mae_dual, E_mult_mae_single, E_mult_mae_dual [nz + 2, nmult + 1] pairs,
+ *               seg_sample_error [n_sample, nmult + 1, n_err + 2] counts.  wfs_seg_energy_table_ints: seg_mult_Emape
+ *               [nx, ny, nmult + 1] pair, E_mult_single, E_mult_dual [nE + 2, nmult + 1] pairs.
+ *   z tables    dev = |p - t|; z bin of (t - 0.5) * zrange: the first k with k * (zrange / nz) - zrange / 2 > it, 0
+ *               below -zrange / 2, nz + 1 from zrange / 2; with an energy map the E bin of float(E * E_scale) is
+ *               get_bin_index over [E_low, E_high) in nz bins.  Histogram: (p - t) * zrange over [err_low, err_high).
+ *   energy      dev = |p - t| / t; E bin of t * E_scale over [E_low, E_high) in nE bins; a row with t == 0 is left
+ *               out (flag 4).  All of it in fp64 on the fp32 value of the element, products and sums rounded apart.
+ *   flags       int32 [1], STICKY bits: 1 event column unsorted / out of range, 2 segment outside [nx, ny], 4 zero
+ *               energy target, 8 a deviation without a fixed-point image (not finite or |dev| >= 2^30) or a sum cell
+ *               that left int64.  Rows that raise 1, 2, 4 or the first kind of 8 are left out. */
+#define WFS_SEG_FIXED_ONE 4294967296.0
+size_t wfs_seg_z_table_ints(int32_t nx, int32_t ny, int32_t nmult, int32_t nz, int32_t n_err, int32_t n_sample);
+size_t wfs_seg_energy_table_ints(int32_t nx, int32_t ny, int32_t nmult, int32_t nE);
+int wfs_seg_z_accumulate(const int32_t *coords, int64_t n_cap, const int64_t *n_dev, int32_t B, const void *pred,
+                         int32_t pred_dtype, int64_t pred_bs, int64_t pred_ps, int32_t pred_plane, const void *targ,
+                         int32_t targ_dtype, int64_t targ_bs, int64_t targ_ps, int32_t targ_plane, const void *energy,
+                         int32_t e_dtype, int64_t e_bs, int64_t e_ps, int32_t e_plane, const float *seg_status,
+                         int32_t nx, int32_t ny, const int32_t *sample_segs, int32_t n_sample, int32_t nmult,
+                         int32_t nz, double zrange, int32_t n_err, double err_low, double err_high, double E_low,
+                         double E_high, double E_scale, int32_t *offsets, int64_t *tables, int32_t *flags,
+                         void *stream);
+int wfs_seg_energy_accumulate(const int32_t *coords, int64_t n_cap, const int64_t *n_dev, int32_t B, const void *pred,
+                              int32_t pred_dtype, int64_t pred_bs, int64_t pred_ps, int32_t pred_plane,
+                              const void *targ, int32_t targ_dtype, int64_t targ_bs, int64_t targ_ps,
+                              int32_t targ_plane, const float *seg_status, int32_t nx, int32_t ny, int32_t nmult,
+                              int32_t nE, double E_low, double E_high, double E_scale, int32_t *offsets,
+                              int64_t *tables, int32_t *flags, void *stream);
+
 /* opt-in per-kernel timing (HIP events on the launch stream), used by bench.py's roofline ---- */
 #define WFS_TIMER_GATHER_CONV 0
 #define WFS_TIMER_GATHER_DW 1

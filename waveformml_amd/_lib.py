@@ -20,6 +20,7 @@ c_i32p = ctypes.POINTER(ctypes.c_int32)
 c_i64p = ctypes.POINTER(ctypes.c_int64)
 c_f32p = ctypes.POINTER(ctypes.c_float)
 _vp, _i32, _i64, _sz = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_size_t
+_dbl = ctypes.c_double
 
 
 class Geometry(ctypes.Structure):
@@ -163,6 +164,13 @@ SIGNATURES = {
     "wfs_eval_accumulate": (ctypes.c_int, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32,
                                            _i32, _i32, _i32, _i32, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                            ctypes.c_double, _vp, _vp, _vp, _vp, _vp]),
+    "wfs_seg_z_table_ints": (_sz, [_i32, _i32, _i32, _i32, _i32, _i32]),
+    "wfs_seg_energy_table_ints": (_sz, [_i32, _i32, _i32, _i32]),
+    "wfs_seg_z_accumulate": (ctypes.c_int, [_vp, _i64, _vp, _i32] + [_vp, _i32, _i64, _i64, _i32] * 3 +
+                             [_vp, _i32, _i32, _vp, _i32, _i32, _i32, _dbl, _i32, _dbl, _dbl, _dbl, _dbl, _dbl, _vp, _vp,
+                              _vp, _vp]),
+    "wfs_seg_energy_accumulate": (ctypes.c_int, [_vp, _i64, _vp, _i32] + [_vp, _i32, _i64, _i64, _i32] * 2 +
+                                  [_vp, _i32, _i32, _i32, _i32, _dbl, _dbl, _dbl, _vp, _vp, _vp, _vp]),
     "wfs_timing_enable": (ctypes.c_int, [_i32]),
     "wfs_timing_read": (ctypes.c_int, [_i32, ctypes.POINTER(ctypes.c_double), c_i64p]),
 }

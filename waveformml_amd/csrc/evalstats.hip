@@ -30,11 +30,8 @@ constexpr int EB = 256;                      // 4 waves per event
 constexpr int EW = EB / WFS_WAVE;
 constexpr int NPART = 9;
 
-__device__ __forceinline__ long long valid_rows(long long R, const long long *r_dev) {
-    long long v = r_dev ? *r_dev : R;
-    v = v < R ? v : R;
-    return v > 0 ? v : 0;
-}
+#include "wfs_evoffsets.h"                   // valid_rows, k_eval_offsets (shared with segstats.hip)
+static_assert(EB == WFS_EVOFF_THREADS, "k_eval_offsets is launched with EB threads");
 
 // butterfly sums: every lane ends with the same bits (a + b and b + a are the same number)
 __device__ __forceinline__ double wave_sum(double v) {
@@ -73,31 +70,6 @@ __device__ __forceinline__ void wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__global__ void __launch_bounds__(EB) k_eval_offsets(const int *__restrict__ coords, long long n_cap,
-                                                     const long long *__restrict__ n_dev, int E, int *__restrict__ off,
-                                                     int *__restrict__ flags) {
-    const long long nv = valid_rows(n_cap, n_dev);
-    const long long r = (long long)blockIdx.x * EB + threadIdx.x;
-    if (nv == 0) {
-        if (r == 0)
-            for (int k = 0; k <= E; ++k) off[k] = 0;
-        return;
-    }
-    if (r >= nv) return;
-    const int e = coords[r * 3 + 2];
-    const int ep = r > 0 ? coords[(r - 1) * 3 + 2] : -1;
-    const bool ok = e >= 0 && e < E && ep >= -1 && ep <= e;
-    if (!ok)
-        atomicOr(flags, 1);                  // event column not sorted / out of range
-    else
-        for (int k = ep + 1; k <= e; ++k) off[k] = (int)r;
-    if (r == nv - 1) {
-        if (ok)
-            for (int k = e + 1; k < E; ++k) off[k] = (int)nv;
-        off[E] = (int)nv;
-    }
 }
 
 // integrate_lininterp_range(v, r0, r1) over v[j] = raw[j] * g, j in [0, n); the whole wave takes part

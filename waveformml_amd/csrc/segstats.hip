@@ -1,0 +1,259 @@
+// segstats.hip -- the per-batch half of the reference's per-segment evaluators on the device: ZEvaluatorWF.add and
+// EnergyEvaluatorWF.add without a calibration group (src/evaluation/ZEvaluator.py:528-562, EnergyEvaluator.py:132-145),
+// i.e. the row walks z_deviation / z_deviation_with_E / z_error / E_deviation of src/utils/SparseUtils.py:1190-1455.
+//
+//   k_eval_offsets   (wfs_evoffsets.h, shared with evalstats.hip) first row of every event; a row's multiplicity is the
+//                    length of its event's run, which the reference finds by looking ahead.
+//   k_seg_z          one thread per row: |p - t| into seg_mult_mae, z_mult_mae_single/dual (and E_mult_mae_* when an
+//                    energy map is given), (p - t) * zrange into the sample segments' error histograms.
+//   k_seg_energy     one thread per row: |p - t| / t into seg_mult_Emape and E_mult_single/dual.
+//
+// Bin arithmetic is fp64 on the fp32 value of the element, a rounded product then a rounded sum (no fma), the
+// reference's literal edge walks (evalstats.hip has the same rule).  Counts are integer atomics on int64 cells.
+// Deviation sums are integer atomics too, on the deviation's fixed-point image round(dev * 2^32) in an int64 cell:
+// exact integer sums, hence independent of the order the rows arrive in and bit-identical from run to run, without a
+// float atomic.  A deviation that has no image (not finite, |dev| >= 2^30) or a cell whose sum leaves int64 sets flag
+// bit 8 and is left out.  The caller's tensors are only read; every index is checked before it is used.
+#include "wfs_common.h"
+
+namespace {
+
+#include "wfs_evoffsets.h"
+
+constexpr int SB = WFS_EVOFF_THREADS;
+constexpr double FIX_ONE = 4294967296.0;     // 2^32, WFS_SEG_FIXED_ONE
+
+struct Plane {                               // one [B, nx, ny] plane of a [B, P, nx, ny] tensor
+    const void *base;
+    long long batch_stride, offset;          // in elements; offset = plane * plane stride
+    int dtype;
+};
+
+__device__ __forceinline__ float ld_plane(const Plane &m, long long e, int cell) {
+    const long long i = e * m.batch_stride + m.offset + cell;
+    if (m.dtype == WFS_F32) return wfs_ld((const float *)m.base + i);
+    if (m.dtype == WFS_BF16) return wfs_ld((const wfs_bf16 *)m.base + i);
+    return wfs_ld((const wfs_f16 *)m.base + i);
+}
+
+// get_bin_index(val, low, high, width, nb): underflow in bin 0, >= high in bin nb + 1, else the first j with
+// j * width + low > val
+__device__ __forceinline__ int bin_walk(double v, double low, double high, double w, int nb) {
+    if (v < low) return 0;
+    if (v >= high) return nb + 1;
+    for (int j = 1; j <= nb; ++j)
+        if (__dadd_rn(__dmul_rn((double)j, w), low) > v) return j;
+    return 0;
+}
+// z_deviation's own walk: the first k with k * (zrange / nz) - zrange / 2 > true_z
+__device__ __forceinline__ int bin_z(double z, double zrange, int nz) {
+    const double half = zrange / 2., w = zrange / nz;
+    if (z < -half) return 0;
+    if (z >= half) return nz + 1;
+    for (int k = 1; k <= nz; ++k)
+        if (__dsub_rn(__dmul_rn((double)k, w), half) > z) return k;
+    return 0;
+}
+
+__device__ __forceinline__ void add_count(long long *p) {
+    atomicAdd(reinterpret_cast<unsigned long long *>(p), 1ull);
+}
+// the fixed-point image of dev, or false (flag 8)
+__device__ __forceinline__ bool fixed_image(double dev, long long *out, int *flags) {
+    const double s = __dmul_rn(dev, FIX_ONE);
+    if (!(fabs(s) < 4611686018427387904.0)) {                 // 2^62; also catches NaN
+        atomicOr(flags, 8);
+        return false;
+    }
+    *out = __double2ll_rn(s);
+    return true;
+}
+__device__ __forceinline__ void add_fixed(long long *p, long long v, int *flags) {
+    const long long old = (long long)atomicAdd(reinterpret_cast<unsigned long long *>(p), (unsigned long long)v);
+    const long long now = (long long)((unsigned long long)old + (unsigned long long)v);
+    if (((old ^ now) & (v ^ now)) < 0) atomicOr(flags, 8);   // the cell's sum wrapped
+}
+// increment_metric_mult_SE's single / dual pair: tab = [count | sum] of one [rows, nm1] table
+__device__ __forceinline__ void add_cell(long long *tab, int cells, int cell, long long v, int *flags) {
+    add_count(tab + cell);
+    add_fixed(tab + cells + cell, v, flags);
+}
+
+struct RowHead {
+    int x, y, e, col;
+    bool ok;
+};
+// coordinates, bounds and the multiplicity column of row r
+__device__ __forceinline__ RowHead row_head(const int *coords, long long r, const int *off, int B, int nx, int ny,
+                                            int nmult, int *flags) {
+    RowHead h;
+    h.x = coords[r * 3], h.y = coords[r * 3 + 1], h.e = coords[r * 3 + 2];
+    h.ok = false;
+    h.col = nmult;
+    if (h.e < 0 || h.e >= B) {
+        atomicOr(flags, 1);                  // k_eval_offsets has set it already
+        return h;
+    }
+    if (h.x < 0 || h.x >= nx || h.y < 0 || h.y >= ny) {
+        atomicOr(flags, 2);                  // a segment outside the detector
+        return h;
+    }
+    const int mult = off[h.e + 1] - off[h.e];
+    if (0 < mult && mult <= nmult) h.col = mult - 1;
+    h.ok = true;
+    return h;
+}
+
+struct ZBins {
+    int nx, ny, nmult, nz, n_err, n_sample;
+    double zrange, err_low, err_high, E_low, E_high, E_scale;
+};
+
+__global__ void __launch_bounds__(SB)
+k_seg_z(const int *__restrict__ coords, long long n_cap, const long long *__restrict__ n_dev, int B, Plane pred,
+        Plane targ, Plane ene, const float *__restrict__ seg, const int *__restrict__ sample_segs, ZBins Z,
+        const int *__restrict__ off, long long *__restrict__ tab, int *__restrict__ flags) {
+    const long long nv = valid_rows(n_cap, n_dev);
+    const long long r = (long long)blockIdx.x * SB + threadIdx.x;
+    if (r >= nv) return;
+    const RowHead h = row_head(coords, r, off, B, Z.nx, Z.ny, Z.nmult, flags);
+    if (!h.ok) return;
+    const int cell = h.x * Z.ny + h.y, nm1 = Z.nmult + 1;
+    const double p = (double)ld_plane(pred, h.e, cell), t = (double)ld_plane(targ, h.e, cell);
+    // table order: wfs_seg_z_table_ints
+    const int seg_cells = Z.nx * Z.ny * nm1, bin_cells = (Z.nz + 2) * nm1;
+    long long *t_seg = tab, *t_zs = t_seg + 2 * seg_cells, *t_zd = t_zs + 2 * bin_cells, *t_es = t_zd + 2 * bin_cells,
+              *t_ed = t_es + 2 * bin_cells, *t_hist = t_ed + 2 * bin_cells;
+    const bool single = seg[cell] > 0.f;
+    long long v;
+    if (fixed_image(fabs(__dsub_rn(p, t)), &v, flags)) {
+        const int zb = bin_z(__dmul_rn(__dsub_rn(t, 0.5), Z.zrange), Z.zrange, Z.nz);
+        add_cell(t_seg, seg_cells, cell * nm1 + h.col, v, flags);
+        add_cell(single ? t_zs : t_zd, bin_cells, zb * nm1 + h.col, v, flags);
+        if (ene.base) {
+            // the reference scales the energy map on the host, float32 * E_scale in float32, before the walk sees it
+            const double E = (double)__fmul_rn(ld_plane(ene, h.e, cell), (float)Z.E_scale);
+            const int eb = bin_walk(E, Z.E_low, Z.E_high, (Z.E_high - Z.E_low) / Z.nz, Z.nz);
+            add_cell(single ? t_es : t_ed, bin_cells, eb * nm1 + h.col, v, flags);
+        }
+    }
+    // z_error: only rows on a sample segment (the first that matches, as sample_index)
+    for (int s = 0; s < Z.n_sample; ++s)
+        if (sample_segs[2 * s] == h.x && sample_segs[2 * s + 1] == h.y) {
+            const double err = __dmul_rn(__dsub_rn(p, t), Z.zrange);
+            // NaN compares false everywhere: the reference's walk leaves it in bin 0, and so does this one
+            const int b = bin_walk(err, Z.err_low, Z.err_high, (Z.err_high - Z.err_low) / Z.n_err, Z.n_err);
+            add_count(t_hist + ((long long)s * nm1 + h.col) * (Z.n_err + 2) + b);
+            break;
+        }
+}
+
+struct EBins {
+    int nx, ny, nmult, nE;
+    double E_low, E_high, E_scale;
+};
+
+__global__ void __launch_bounds__(SB)
+k_seg_energy(const int *__restrict__ coords, long long n_cap, const long long *__restrict__ n_dev, int B, Plane pred,
+             Plane targ, const float *__restrict__ seg, EBins Eb, const int *__restrict__ off,
+             long long *__restrict__ tab, int *__restrict__ flags) {
+    const long long nv = valid_rows(n_cap, n_dev);
+    const long long r = (long long)blockIdx.x * SB + threadIdx.x;
+    if (r >= nv) return;
+    const RowHead h = row_head(coords, r, off, B, Eb.nx, Eb.ny, Eb.nmult, flags);
+    if (!h.ok) return;
+    const int cell = h.x * Eb.ny + h.y, nm1 = Eb.nmult + 1;
+    const double p = (double)ld_plane(pred, h.e, cell), t = (double)ld_plane(targ, h.e, cell);
+    if (t == 0.0) {
+        atomicOr(flags, 4);                  // the reference divides by it (numba raises, plain Python gives inf)
+        return;
+    }
+    long long v;
+    if (!fixed_image(fabs(__dsub_rn(p, t)) / t, &v, flags)) return;
+    const int eb = bin_walk(__dmul_rn(t, Eb.E_scale), Eb.E_low, Eb.E_high, (Eb.E_high - Eb.E_low) / Eb.nE, Eb.nE);
+    // table order: wfs_seg_energy_table_ints
+    const int seg_cells = Eb.nx * Eb.ny * nm1, bin_cells = (Eb.nE + 2) * nm1;
+    long long *t_seg = tab, *t_es = t_seg + 2 * seg_cells, *t_ed = t_es + 2 * bin_cells;
+    add_cell(t_seg, seg_cells, cell * nm1 + h.col, v, flags);
+    add_cell(seg[cell] > 0.f ? t_es : t_ed, bin_cells, eb * nm1 + h.col, v, flags);
+}
+
+bool plane_ok(const void *base, int dtype, long long bs, long long ps, int plane) {
+    return base && wfs_dtype_ok(dtype) && bs >= 0 && ps >= 0 && plane >= 0;
+}
+
+}  // namespace
+
+extern "C" size_t wfs_seg_z_table_ints(int32_t nx, int32_t ny, int32_t nmult, int32_t nz, int32_t n_err,
+                                       int32_t n_sample) {
+    const size_t nm1 = (size_t)nmult + 1;
+    return 2 * (size_t)nx * ny * nm1 + 8 * ((size_t)nz + 2) * nm1 + (size_t)n_sample * nm1 * ((size_t)n_err + 2);
+}
+
+extern "C" size_t wfs_seg_energy_table_ints(int32_t nx, int32_t ny, int32_t nmult, int32_t nE) {
+    const size_t nm1 = (size_t)nmult + 1;
+    return 2 * (size_t)nx * ny * nm1 + 4 * ((size_t)nE + 2) * nm1;
+}
+
+extern "C" int wfs_seg_z_accumulate(const int32_t *coords, int64_t n_cap, const int64_t *n_dev, int32_t B,
+                                    const void *pred, int32_t pred_dtype, int64_t pred_bs, int64_t pred_ps,
+                                    int32_t pred_plane, const void *targ, int32_t targ_dtype, int64_t targ_bs,
+                                    int64_t targ_ps, int32_t targ_plane, const void *energy, int32_t e_dtype,
+                                    int64_t e_bs, int64_t e_ps, int32_t e_plane, const float *seg_status, int32_t nx,
+                                    int32_t ny, const int32_t *sample_segs, int32_t n_sample, int32_t nmult, int32_t nz,
+                                    double zrange, int32_t n_err, double err_low, double err_high, double E_low,
+                                    double E_high, double E_scale, int32_t *offsets, int64_t *tables, int32_t *flags,
+                                    void *stream) {
+    WFS_REQUIRE(B >= 1 && n_cap >= 0 && n_cap < (1ll << 31) && nx >= 1 && ny >= 1, WFS_EINVAL,
+                "wfs_seg_z_accumulate: B = %d, n_cap = %lld, grid %d x %d", B, (long long)n_cap, nx, ny);
+    WFS_REQUIRE(nmult >= 1 && nz >= 1 && n_err >= 1 && n_sample >= 0 && err_high > err_low && zrange > 0, WFS_EINVAL,
+                "wfs_seg_z_accumulate: bad bin parameters");
+    WFS_REQUIRE(coords && seg_status && (sample_segs || n_sample == 0) && offsets && tables && flags, WFS_EINVAL,
+                "wfs_seg_z_accumulate: NULL argument");
+    WFS_REQUIRE(plane_ok(pred, pred_dtype, pred_bs, pred_ps, pred_plane) &&
+                    plane_ok(targ, targ_dtype, targ_bs, targ_ps, targ_plane) &&
+                    (!energy || (plane_ok(energy, e_dtype, e_bs, e_ps, e_plane) && E_high > E_low)),
+                WFS_EINVAL, "wfs_seg_z_accumulate: bad map (NULL, unknown dtype or negative stride / plane)");
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned rb = (unsigned)(n_cap > 0 ? wfs_cdiv(n_cap, SB) : 1);
+    k_eval_offsets<<<rb, SB, 0, s>>>(coords, n_cap, (const long long *)n_dev, B, offsets, flags);
+    WFS_LAUNCH_CHECK();
+    if (n_cap == 0) return WFS_OK;
+    const Plane P = {pred, pred_bs, pred_ps * pred_plane, pred_dtype};
+    const Plane T = {targ, targ_bs, targ_ps * targ_plane, targ_dtype};
+    const Plane En = {energy, e_bs, energy ? e_ps * e_plane : 0, energy ? e_dtype : WFS_F32};
+    const ZBins Z = {nx, ny, nmult, nz, n_err, n_sample, zrange, err_low, err_high, E_low, E_high, E_scale};
+    k_seg_z<<<rb, SB, 0, s>>>(coords, n_cap, (const long long *)n_dev, B, P, T, En, seg_status, sample_segs, Z, offsets,
+                              (long long *)tables, flags);
+    WFS_LAUNCH_CHECK();
+    return WFS_OK;
+}
+
+extern "C" int wfs_seg_energy_accumulate(const int32_t *coords, int64_t n_cap, const int64_t *n_dev, int32_t B,
+                                         const void *pred, int32_t pred_dtype, int64_t pred_bs, int64_t pred_ps,
+                                         int32_t pred_plane, const void *targ, int32_t targ_dtype, int64_t targ_bs,
+                                         int64_t targ_ps, int32_t targ_plane, const float *seg_status, int32_t nx,
+                                         int32_t ny, int32_t nmult, int32_t nE, double E_low, double E_high,
+                                         double E_scale, int32_t *offsets, int64_t *tables, int32_t *flags,
+                                         void *stream) {
+    WFS_REQUIRE(B >= 1 && n_cap >= 0 && n_cap < (1ll << 31) && nx >= 1 && ny >= 1, WFS_EINVAL,
+                "wfs_seg_energy_accumulate: B = %d, n_cap = %lld, grid %d x %d", B, (long long)n_cap, nx, ny);
+    WFS_REQUIRE(nmult >= 1 && nE >= 1 && E_high > E_low, WFS_EINVAL, "wfs_seg_energy_accumulate: bad bin parameters");
+    WFS_REQUIRE(coords && seg_status && offsets && tables && flags, WFS_EINVAL,
+                "wfs_seg_energy_accumulate: NULL argument");
+    WFS_REQUIRE(plane_ok(pred, pred_dtype, pred_bs, pred_ps, pred_plane) &&
+                    plane_ok(targ, targ_dtype, targ_bs, targ_ps, targ_plane),
+                WFS_EINVAL, "wfs_seg_energy_accumulate: bad map (NULL, unknown dtype or negative stride / plane)");
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned rb = (unsigned)(n_cap > 0 ? wfs_cdiv(n_cap, SB) : 1);
+    k_eval_offsets<<<rb, SB, 0, s>>>(coords, n_cap, (const long long *)n_dev, B, offsets, flags);
+    WFS_LAUNCH_CHECK();
+    if (n_cap == 0) return WFS_OK;
+    const Plane P = {pred, pred_bs, pred_ps * pred_plane, pred_dtype};
+    const Plane T = {targ, targ_bs, targ_ps * targ_plane, targ_dtype};
+    const EBins Eb = {nx, ny, nmult, nE, E_low, E_high, E_scale};
+    k_seg_energy<<<rb, SB, 0, s>>>(coords, n_cap, (const long long *)n_dev, B, P, T, seg_status, Eb, offsets,
+                                   (long long *)tables, flags);
+    WFS_LAUNCH_CHECK();
+    return WFS_OK;
+}

@@ -3,6 +3,8 @@
 ``test_loop``        what ``pytorch_lightning.Trainer.test(runner, datamodule)`` does for the reference's Evaluate.py
                      (Evaluate.py:69-84): eval mode, no gradients, ``LitPSD.test_step`` per batch (which zeroes feature
                      column ``occlude_index`` when it is set, src/engineering/LitPSD.py:130-151), event-weighted means.
+``segment_test_loop`` the same for the per-segment regression modules (psd/litz.LitZ, LitEZ): ``test_step`` per batch,
+                     row-weighted mean losses, the batch's dense maps handed to a psd/segment_evaluator evaluator.
 ``occlusion_sweep``  the reference's occlusion study (scripts/RunOcclusionStudy.py) runs Evaluate.py once per feature
                      index, i.e. re-reads the data and rebuilds every rulebook for each index although the geometry of a
                      batch never changes.  Here ONE batch already in HBM is run through the net for a list of indices
@@ -73,6 +75,41 @@ def test_loop(module, loader, device, feature_dtype=None, capture=False, evaluat
             for t in evaluator.state_tensors():          # integer tables and fp64 pulse sums: sums over batches
                 dist.all_reduce(t, op=dist.ReduceOp.SUM)
     out = {"test_loss": float(tot) / max(n, 1), "test_acc": float(acc) / max(n, 1), "events": n}
+    if evaluator is not None:
+        out["evaluation"] = evaluator.results()
+    return out
+
+
+@torch.no_grad()
+def segment_test_loop(module, loader, device, feature_dtype=None, evaluator=None):
+    """``test_step`` of a LitZ / LitEZ per batch in eval mode; every ``test_*`` entry it returns comes back as its mean
+    over batches weighted by the batch's rows (the segment losses are per-row means, src/engineering/LitBase.py:171).
+    ``evaluator``: a psd/segment_evaluator ZEvaluator / EZEvaluator; every batch's (predictions, dense targets,
+    coordinates, features) go to its ``add`` as in the reference's ``test_step`` (LitZ.py:134-141, LitEZ.py:86-89) -- on the
+    stream the forward ran on, without a read-back -- and the returned dict gains ``"evaluation": evaluator.results()``."""
+    module.to(device)
+    module.eval()
+    sums, n = {}, 0
+    for i, batch in enumerate(loader):
+        batch = to_device(batch, device, feature_dtype)
+        rows = int(batch[0][0].shape[0])
+        res = module.test_step(batch, i)
+        if evaluator is not None:
+            evaluator.add(*module.last_test_outputs)
+        for k, v in res.items():
+            sums[k] = sums.get(k, 0.0) + v.detach().double() * rows       # device scalars: one read-back at the end
+        n += rows
+    keys = sorted(sums)
+    import torch.distributed as dist
+    if keys and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        packed = torch.stack([sums[k].reshape(()) for k in keys] + [torch.tensor(float(n), dtype=torch.float64, device=device)])
+        dist.all_reduce(packed, op=dist.ReduceOp.SUM)
+        sums, n = {k: packed[j] for j, k in enumerate(keys)}, int(packed[-1])
+        if evaluator is not None:
+            for t in evaluator.state_tensors():          # integer tables: sums over batches
+                dist.all_reduce(t, op=dist.ReduceOp.SUM)
+    out = {k: float(sums[k]) / max(n, 1) for k in keys}
+    out["rows"] = n
     if evaluator is not None:
         out["evaluation"] = evaluator.results()
     return out

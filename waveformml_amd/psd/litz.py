@@ -4,8 +4,10 @@ predicts a dense [B, out, 14, 11] map, the loss compares it with the targets of 
 and the dense target come from ``SparseConvTensor(...).dense()`` (wfs_to_dense) -- with a sum-reduced criterion divided by
 the number of rows (``net_config.SELoss``: of the single-ended segments only, psd/segments.py).
 
-As psd/lit.LitPSD these are plain ``nn.Module``s with Lightning's step methods (Lightning is not installable offline);
-the evaluators (ZEvaluator*, EZEvaluator*, histogram / plot plumbing) are out of scope, SURVEY.md 2.
+As psd/lit.LitPSD these are plain ``nn.Module``s with Lightning's step methods (Lightning is not installable offline).
+The evaluators the reference's ``test_step`` feeds (ZEvaluatorWF, EZEvaluatorWF without a calibration group) are
+psd/segment_evaluator.py; ``test_step`` leaves what it would hand them in ``last_test_outputs`` and
+psd/evaluate.segment_test_loop does the hand-over.  Their plots and the calibration-database variants are out of scope.
 """
 import logging
 
@@ -42,6 +44,23 @@ class LitSegmentBase(nn.Module):
         if hasattr(config.net_config, "UseFFT"):
             raise NotImplementedError("UseFFT feeds complex features; not on the mirrored path")
         self.logged = {}
+        self.last_test_outputs = None         # test_step's (predictions, target_tensor, c, f), for segment_test_loop
+        self._evaluator = None
+
+    def _make_evaluator(self, device, params):
+        raise NotImplementedError
+
+    @property
+    def evaluator(self):
+        """The evaluator the reference builds in ``__init__`` (LitZ.py:43-60, LitEZ.py:24-35) for the case without a
+        calibration group, built on first use on the device the model lives on, with ``config.evaluation_config`` as
+        keyword arguments.  Nothing calls it implicitly: hand it to ``evaluate.segment_test_loop(..., evaluator=...)``."""
+        if self._evaluator is None:
+            params = {}
+            if hasattr(self.config, "evaluation_config"):
+                params = DictionaryUtility.to_dict(self.config.evaluation_config)
+            self._evaluator = self._make_evaluator(next(self.model.parameters()).device, params)
+        return self._evaluator
 
     def forward(self, x):
         return self.model(x)
@@ -119,8 +138,13 @@ class LitZ(LitSegmentBase):
         self.log("val_loss", loss, on_epoch=True, prog_bar=True, logger=True)
         return loss
 
+    def _make_evaluator(self, device, params):
+        from .segment_evaluator import ZEvaluator
+        return ZEvaluator(device, **params)
+
     def test_step(self, batch, batch_idx):
-        loss = self._process_batch(batch)[0]
+        loss, predictions, target_tensor, c, f, _ = self._process_batch(batch)
+        self.last_test_outputs = (predictions.detach(), target_tensor.detach(), c, f)
         results = {"test_loss": loss}
         self.log_dict(results, on_epoch=True, logger=True)
         return results
@@ -168,8 +192,14 @@ class LitEZ(LitSegmentBase):
         self.log_dict(results, on_epoch=True, prog_bar=True, logger=True)
         return results
 
+    def _make_evaluator(self, device, params):
+        from .segment_evaluator import EZEvaluator
+        params.setdefault("E_scale", self.e_adjust)            # the reference passes e_scale=self.e_adjust
+        return EZEvaluator(device, **params)
+
     def test_step(self, batch, batch_idx):
-        _, _, _, _, loss, ELoss, ZLoss = self._process_batch(batch)
+        c, f, predictions, target_tensor, loss, ELoss, ZLoss = self._process_batch(batch)
+        self.last_test_outputs = (predictions.detach(), target_tensor.detach(), c, f)
         results = {"test_loss": loss, "test_MAE_E": ELoss, "test_MAE_z": ZLoss}
         self.log_dict(results, on_epoch=True, logger=True)
         return results
