@@ -75,6 +75,18 @@ template <>
 __device__ __forceinline__ void widen<float>(const Piece<float> &q, float *x) {
     x[0] = q.a.x; x[1] = q.a.y; x[2] = q.a.z; x[3] = q.a.w; x[4] = q.b.x; x[5] = q.b.y; x[6] = q.b.z; x[7] = q.b.w;
 }
+// the piece, or zeros (in the registers it travels in: 4 selects for 16-bit rows)
+template <typename H>
+__device__ __forceinline__ Piece<H> blank_unless(Piece<H> q, bool keep) {
+    q.v.x = keep ? q.v.x : 0u; q.v.y = keep ? q.v.y : 0u; q.v.z = keep ? q.v.z : 0u; q.v.w = keep ? q.v.w : 0u;
+    return q;
+}
+template <>
+__device__ __forceinline__ Piece<float> blank_unless<float>(Piece<float> q, bool keep) {
+    q.a.x = keep ? q.a.x : 0.f; q.a.y = keep ? q.a.y : 0.f; q.a.z = keep ? q.a.z : 0.f; q.a.w = keep ? q.a.w : 0.f;
+    q.b.x = keep ? q.b.x : 0.f; q.b.y = keep ? q.b.y : 0.f; q.b.z = keep ? q.b.z : 0.f; q.b.w = keep ? q.b.w : 0.f;
+    return q;
+}
 // events whose row loads a thread has in flight together (fp32 rows are twice the registers)
 template <typename H> struct ShBatch { static constexpr int n = 8; };
 template <> struct ShBatch<float> { static constexpr int n = 4; };
@@ -220,10 +232,12 @@ __global__ void __launch_bounds__(512) k_shead_bwd(const H *__restrict__ X, cons
             const bool act = row[e] >= 0;
             if (part) {
                 float x[8];
-                widen<H>(q[i], x);
+                // a missing row adds 0: its registers hold row 0, which may be NaN / Inf (capacity padding when the valid
+                // count is 0, or a non-finite row 0 itself), so the DATA is selected as in the forward -- 0 * NaN is NaN
+                widen<H>(blank_unless(q[i], act), x);
 #pragma unroll
                 for (int o = 0; o < O; ++o) {
-                    const float go = act ? g[i][o] : 0.f;            // a missing row adds 0 (its registers hold row 0)
+                    const float go = g[i][o];
 #pragma unroll
                     for (int j = 0; j < 8; ++j) acc[o][j] = fmaf(go, x[j], acc[o][j]);
                 }
