@@ -398,7 +398,7 @@ def test_packed_table_products_equal_the_dense_table_products(dtype):
     dx_d = Fsp.gather_conv(rb.nbr_out, None, 27, -1, N, dY, W, True, None, nv)
     t_p, pk = rb.table_by_in(32, 32, X, 3)
     assert pk == 3
-    dw_p = Fsp.gather_dw(t_p, 27, -1, N, X, dY, False, None, nv, False, None, pk)
+    dw_p = Fsp.gather_dw(t_p, 27, -1, N, X, dY, False, None, nv, packed_kl=pk)
     dw_d = Fsp.gather_dw(rb.nbr_out, 27, -1, N, X, dY, False, None, nv)
     torch.cuda.synchronize()
     nvv = int(nv)
@@ -433,7 +433,7 @@ def test_one_launch_conv_backward_equals_the_two_products(dtype, device_counts):
     for name, table, pk, ident, rows_out in cases:
         dY = torch.randn((rows_out, 32), device=DEV, generator=g).to(dtype)
         dx1 = Fsp.gather_conv(table, None, 27, ident, N, dY, W, True, None, nv, None, pk)
-        dw1 = Fsp.gather_dw(table, 27, ident, N, X, dY, False, None, nv, False, None, pk)
+        dw1 = Fsp.gather_dw(table, 27, ident, N, X, dY, False, None, nv, packed_kl=pk)
         dx2, dw2 = Fsp.conv_backward(table, 27, ident, N, X, dY, W, nv, None, pk)
         torch.cuda.synchronize()
         nvv = int(nv) if nv is not None else N

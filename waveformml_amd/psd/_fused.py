@@ -5,6 +5,8 @@ import inspect
 
 import torch
 
+from ..spconv.functional import as_grad, grad_like          # noqa: F401  (as_grad: used by the front ends through here)
+
 
 def ptr_table(cache, key, rows, device):
     """Device array of pointer records (int64), cached by the addresses it holds: in a captured step parameters and
@@ -62,14 +64,8 @@ def bwd_rows(ctx, params, width, first):
     """The backward's records and the gradients they point to: a slot (spconv/functional.grad_like -- the flat gradient
     buffer's where there is one) for every present parameter whose entry of ctx.needs_input_grad, from ``first`` on, is
     set; None for the others."""
-    from ..spconv.functional import grad_like
     need = ctx.needs_input_grad[first: first + len(params)]
     grads = [grad_like(p) if (p is not None and nd) else None for p, nd in zip(params, need)]
     rows = [[_addr(t) for t in list(params[i: i + width]) + grads[i: i + width]] for i in range(0, len(params), width)]
     return rows, grads
 
-
-def as_grad(dy, dtype):
-    """The incoming gradient as the kernels read it: contiguous, in the rows' dtype."""
-    dy = dy.contiguous()
-    return dy if dy.dtype == dtype else dy.to(dtype)

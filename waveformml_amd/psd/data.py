@@ -4,7 +4,6 @@ of ``HDF5Dataset.__getitem__`` (src/datasets/HDF5Dataset.py:186-217: ONE item = 
 range, ``[[coords, feats], labels]`` with event ids starting at 0).
 """
 import numpy as np
-import queue as _queue
 import time as _time
 
 import torch
@@ -294,10 +293,8 @@ class DevicePrefetcher(object):
     host.  Replaces the reference's synchronous ``.to(self.device)`` inside ``_concat_range``
     (src/datasets/HDF5Dataset.py:250-300), which a forked DataLoader worker cannot do on a HIP device anyway."""
 
-    def __init__(self, loader, device, feature_dtype=None, depth=2, on_stage=None, on_exhausted=None, threaded=None):
+    def __init__(self, loader, device, feature_dtype=None, depth=2, on_stage=None, on_exhausted=None):
         self.loader, self.device, self.feature_dtype, self.depth = loader, torch.device(device), feature_dtype, depth
-        import os
-        self.threaded = (os.environ.get("WFS_PREFETCH_THREAD", "0") != "0") if threaded is None else bool(threaded)
         self.wait_seconds = 0.0
         self.copy_stream = torch.cuda.Stream(device=self.device)
         # this consumer releases ring slots itself (after each copy): the loader's reclaim-by-age must sit behind the
@@ -328,60 +325,9 @@ class DevicePrefetcher(object):
         # (host buffers kept alive until the copy has been waited on, device tensors, copy event, rows, labels)
         return (batch if ring else host), dev, done, int(c.shape[0]), int(y.shape[0])
 
-    def _producer(self, out, stop):
-        """Background thread: pulls batches off the loader and stages them (worker-message unpacking, the host -> device
-        copies and the dtype cast all happen here); hands (staged | exception | None at the end) to the consumer."""
-        try:
-            if self.device.type == "cuda":
-                torch.cuda.set_device(self.device)
-            for batch in self.loader:
-                if stop.is_set():
-                    break
-                item = self._stage(batch, notify=False)
-                while not stop.is_set():
-                    try:
-                        out.put(item, timeout=0.05)
-                        break
-                    except _queue.Full:
-                        continue
-            out.put(None)
-        except BaseException as e:          # noqa: BLE001  -- delivered to the consumer, which re-raises it
-            out.put(e)
-
-    def _staged_batches(self):
-        """Staged batches in loader order; with ``threaded`` (WFS_PREFETCH_THREAD=1; off by default) they are produced by a
-        background thread, so that the training thread's step is the hand-over launch + the graph replay and nothing
-        else.  Measured from files at the bench's density (tools/soak_from_files.py 600 85 8 16, round 4): 466-469 k
-        events/s per epoch with the thread, 462-468 k without -- the training thread then WAITS 45 us per step for the
-        next staged batch instead of staging it itself: neutral, so the simpler single-threaded form stays the default."""
-        if not self.threaded:
-            for batch in self.loader:
-                yield self._stage(batch, notify=False)
-            return
-        import threading
-        out, stop = _queue.Queue(maxsize=max(2, self.depth)), threading.Event()
-        th = threading.Thread(target=self._producer, args=(out, stop), name="wfs-prefetch", daemon=True)
-        th.start()
-        try:
-            while True:
-                item = out.get()
-                if item is None:
-                    return
-                if isinstance(item, BaseException):
-                    raise item
-                yield item
-        finally:
-            stop.set()
-            while th.is_alive():             # unblock a producer waiting on a full queue, then let it finish
-                try:
-                    out.get_nowait()
-                except _queue.Empty:
-                    pass
-                th.join(timeout=0.05)
-
     def __iter__(self):
         queue = []
-        it = self._staged_batches()
+        it = (self._stage(batch, notify=False) for batch in self.loader)       # staged batches in loader order
         more = True
         while True:
             while more and len(queue) < self.depth:

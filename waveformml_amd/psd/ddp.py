@@ -122,8 +122,7 @@ class FlatGradAllReducer(object):
 
     def _pack(self, b):
         from ..spconv import functional as _fsp
-        _fsp.join_side_streams()          # weight gradients may still be in flight on the dW side stream
-        _fsp.flush_deferred_dw()          # ... or wait for their (deferred) second stage
+        _fsp.flush_deferred_dw()          # weight gradients may still wait for their (deferred) second stage
         s, e, idxs = self.buckets[b]
         base = self.flat_grad.data_ptr()
         placed = []                       # gradients that already sit in their slot (written there by the kernels)

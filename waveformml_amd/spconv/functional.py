@@ -41,6 +41,12 @@ def _features_ok(t):
     return t.contiguous()
 
 
+def as_grad(dy, dtype):
+    """The incoming gradient as the kernels read it: contiguous, in the rows' dtype."""
+    dy = dy.contiguous()
+    return dy if dy.dtype == dtype else dy.to(dtype)
+
+
 def _rows(shape, like, r_dev):
     """Row-dimensioned output.  In device-count mode rows beyond the valid count are never written NOR read
     by the kernels, so they can stay uninitialised (the conv bias gradient's column sum honours the count too)."""
@@ -159,9 +165,6 @@ def scatter_conv(table, K, identity_k, R, X, W, transpose_w, n_out, bias):
     return Y.to(X.dtype)
 
 
-_PENDING_SIDE = []          # (event, tensors kept alive until the join) of launches made on a side stream
-
-
 # ---- parameter gradients written where the optimizer reads them ---------------------------------------------------
 # A runner that keeps all parameters / gradients in ONE flat buffer each (psd/ddp.FlatGradAllReducer) registers the
 # pair here.  Backward passes then allocate a parameter's gradient as a VIEW of its slot in the flat gradient buffer
@@ -253,59 +256,41 @@ def flush_deferred_dw():
     del _DEFERRED_DW[:]
 
 
-def join_side_streams():
-    """Make the current stream wait for everything launched on side streams (OVERLAP_DW) and release the
-    tensors that were kept alive for them."""
-    if _PENDING_SIDE:
-        cur = torch.cuda.current_stream()
-        for ev, _keep in _PENDING_SIDE:
-            cur.wait_event(ev)
-        del _PENDING_SIDE[:]
+def _dw_job(grad):
+    """A DwJob for the kernel to fill when the slab reduction of ``grad`` can join the pass's deferred ones: deferral is
+    on and ``grad`` sits in a slot of a registered flat gradient buffer.  Else None (the kernel reduces at once)."""
+    if _DEFERRED_DW is not None and grad is not None and grad._base is not None:
+        return _lib.DwJob()
+    return None
 
 
-def gather_dw(table, K, identity_k, R, S, G, swap, kmap=None, r_dev=None, overlap=False, like=None, packed_kl=0):
+def _queue_dw_job(job, ws):
+    """After the call that was handed ``job`` (ctypes passes a DwJob by reference, None as NULL): if it left a second stage
+    pending, flush_deferred_dw() runs it; ``ws`` holds its slabs until then."""
+    if job is not None and job.nslabs > 0:
+        _DEFERRED_DW.append((job, ws))
+
+
+def gather_dw(table, K, identity_k, R, S, G, swap, kmap=None, r_dev=None, like=None, packed_kl=0):
     """dW[k,a,b] = sum_r S[r,a] G[table[kmap[k],r], b]  (swap: dW[k,b,a]).
-    overlap=True launches on the side stream (see ops.OVERLAP_DW): memory is allocated on the calling stream
-    and every operand is kept alive until join_side_streams().  ``like``: the parameter this is the gradient of
-    (grad_like: written straight into its slot of a registered flat gradient buffer)."""
+    ``like``: the parameter this is the gradient of (grad_like: written straight into its slot of a registered flat
+    gradient buffer)."""
     lib = _lib.load()
     Cs, Cg = int(S.shape[1]), int(G.shape[1])
     shape = (K, Cg, Cs) if swap else (K, Cs, Cg)
-    in_slot = False
     if like is not None and like.numel() == K * Cs * Cg:
         dW = grad_like(like, shape)
-        in_slot = dW._base is not None
     else:
         dW = torch.empty(shape, dtype=torch.float32, device=S.device)
     assert S.dtype == G.dtype and S.shape[0] == R
     assert table is None or (table.dtype == torch.int32 and table.shape == ((K // packed_kl if packed_kl else K), R))
     nbytes = lib.wfs_gather_dw_workspace_bytes(K, R, Cs, Cg)
     ws = torch.empty((max(int(nbytes), 1),), dtype=torch.uint8, device=S.device)
-
-    def launch():
-        defer = _DEFERRED_DW is not None and in_slot and not overlap
-        job = _lib.DwJob() if defer else None
-        _lib.check(lib.wfs_gather_dw(_lib.ptr(table), kmap, K, identity_k, R, _lib.ptr(S), Cs, _lib.ptr(G), G.shape[0],
-                                     Cg, 1 if swap else 0, _lib.ptr(dW), _lib.dtype_code(S), _lib.ptr(ws), ws.numel(),
-                                     _lib.ptr(r_dev), ctypes.byref(job) if defer else None, packed_kl, _lib.stream_ptr()))
-        if defer and job.nslabs > 0:
-            _DEFERRED_DW.append((job, ws))          # second stage pending: flush_deferred_dw()
-
-    if overlap and ACCOUNT is None:
-        from . import ops
-        main = torch.cuda.current_stream()
-        side = ops.side_stream(S.device, 1)
-        side.wait_stream(main)
-        with torch.cuda.stream(side):
-            launch()
-            ev = torch.cuda.Event()
-            ev.record(side)
-        if not _PENDING_SIDE:
-            # fallback join at the end of this backward pass (the reducer normally joins earlier, before packing)
-            torch.autograd.Variable._execution_engine.queue_callback(join_side_streams)
-        _PENDING_SIDE.append((ev, (table, S, G, dW, ws, r_dev)))
-    else:
-        launch()
+    job = _dw_job(dW)
+    _lib.check(lib.wfs_gather_dw(_lib.ptr(table), kmap, K, identity_k, R, _lib.ptr(S), Cs, _lib.ptr(G), G.shape[0],
+                                 Cg, 1 if swap else 0, _lib.ptr(dW), _lib.dtype_code(S), _lib.ptr(ws), ws.numel(),
+                                 _lib.ptr(r_dev), job, packed_kl, _lib.stream_ptr()))
+    _queue_dw_job(job, ws)
     if ACCOUNT is not None:
         _account("gather_dw", (table >> 3).clamp_(min=-1) if packed_kl else table, R, R, Cs, G.shape[0], Cg, K, Cs, Cg,
                  S.element_size())
@@ -320,18 +305,15 @@ def conv_backward(table, K, identity_k, R, X, dY, W, r_dev=None, like=None, pack
     Cin, Cout = int(X.shape[1]), int(dY.shape[1])
     if like is not None and like.numel() == K * Cin * Cout:
         dW = grad_like(like, (K, Cin, Cout))
-        in_slot = dW._base is not None
     else:
-        dW, in_slot = torch.empty((K, Cin, Cout), dtype=torch.float32, device=X.device), False
+        dW = torch.empty((K, Cin, Cout), dtype=torch.float32, device=X.device)
     dX = _rows((R, Cin), dY, r_dev)
     ws = torch.empty((max(int(lib.wfs_gather_dw_workspace_bytes(K, R, Cin, Cout)), 1),), dtype=torch.uint8, device=X.device)
-    defer = _DEFERRED_DW is not None and in_slot
-    job = _lib.DwJob() if defer else None
+    job = _dw_job(dW)
     _lib.check(lib.wfs_conv_backward(_lib.ptr(table), K, identity_k, R, _lib.ptr(X), _lib.ptr(dY), dY.shape[0], Cin, Cout,
                                      _lib.ptr(W), _lib.ptr(dX), _lib.ptr(dW), _lib.dtype_code(X), _lib.ptr(ws), ws.numel(),
-                                     _lib.ptr(r_dev), ctypes.byref(job) if defer else None, packed_kl, _lib.stream_ptr()))
-    if defer and job.nslabs > 0:
-        _DEFERRED_DW.append((job, ws))
+                                     _lib.ptr(r_dev), job, packed_kl, _lib.stream_ptr()))
+    _queue_dw_job(job, ws)
     if ACCOUNT is not None:
         # SURVEY.md 8d "backward": X, dY and dX once each, the rulebook twice (8 B per pair), the filters twice
         dense = (table >> 3).clamp_(min=-1) if packed_kl else table
@@ -348,15 +330,14 @@ def conv_backward(table, K, identity_k, R, X, dY, W, r_dev=None, like=None, pack
     return dX, dW
 
 
-# dW and dX of a 32 -> 32 layer in one launch (WFS_FUSED_CONV_BACKWARD=0: two launches): 16-bit rows, and fp32 rows on the
-# three-piece kernels (the library's WFS_SPLIT_BF16, default on; WFS_FUSED_CONV_BACKWARD_F32=0 keeps fp32 on two launches)
-FUSED_CONV_BACKWARD = __import__("os").environ.get("WFS_FUSED_CONV_BACKWARD", "1") != "0"
-FUSED_CONV_BACKWARD_F32 = (__import__("os").environ.get("WFS_SPLIT_BF16", "1") != "0"
-                           and __import__("os").environ.get("WFS_FUSED_CONV_BACKWARD_F32", "1") != "0")
+# Mirrors csrc/conv_mfma.hip's wfs_split_bf16(): fp32 rows run on the three-piece (split-bf16) kernels unless the library's
+# WFS_SPLIT_BF16 is "0".  Only those kernels have the one-launch backward for fp32 rows.
+SPLIT_BF16 = __import__("os").environ.get("WFS_SPLIT_BF16", "1") != "0"
 
 
 def _one_launch_rows(dtype):
-    return dtype in (torch.bfloat16, torch.float16) or (dtype == torch.float32 and FUSED_CONV_BACKWARD_F32)
+    """Row types whose 32 -> 32 dW and dX run in one launch (wfs_conv_backward; else it issues two)."""
+    return dtype in (torch.bfloat16, torch.float16) or (dtype == torch.float32 and SPLIT_BF16)
 
 
 class SparseConvFunction(Function):
@@ -392,14 +373,10 @@ class SparseConvFunction(Function):
         features, filters, bias = ctx.saved_tensors
         rb, mode = ctx.rb, ctx.mode
         K = rb.K
-        dY = grad_output.contiguous()
-        if dY.dtype != features.dtype:
-            dY = dY.to(features.dtype)
+        dY = as_grad(grad_output, features.dtype)
         W = filters.detach().reshape(K, filters.shape[-2], filters.shape[-1]).float().contiguous()
         ident = rb.centre_k if rb.subm else -1
         dX = dW = db = None
-        from . import ops as _ops
-        ov = _ops.OVERLAP_DW
         if mode == INVERSE:
             if ctx.needs_input_grad[0]:
                 if rb.has_dup:
@@ -407,24 +384,22 @@ class SparseConvFunction(Function):
                 else:
                     dX = gather_conv(rb.nbr_in, None, K, ident, rb.M, dY, W, True, None, rb.m_dev, ctx.w16)
             if ctx.needs_input_grad[1]:
-                dW = gather_dw(rb.nbr_out, K, ident, rb.N, dY, features, True, None, rb.n_dev, ov, filters)
-        elif (FUSED_CONV_BACKWARD and ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and not ov and not rb.has_dup
-              and features.shape[1] == 32 and dY.shape[1] == 32 and _one_launch_rows(features.dtype)
-              and features.is_cuda):
+                dW = gather_dw(rb.nbr_out, K, ident, rb.N, dY, features, True, None, rb.n_dev, filters)
+        elif (ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and not rb.has_dup and features.shape[1] == 32
+              and dY.shape[1] == 32 and features.is_cuda and _one_launch_rows(features.dtype)):
             table, pk = rb.table_by_in(32, 32, features, 3)
             if pk and rb.table_by_in(32, 32, dY, 1)[1] != pk:
                 table, pk = rb.nbr_out, 0
             dX, dW = conv_backward(table, K, ident, rb.N, features, dY, W, rb.n_dev, filters, pk)
         else:
-            # dW first: with OVERLAP_DW it goes to the side stream and runs beside the dX launched next
             if ctx.needs_input_grad[1]:
                 if features.shape[1] == 2 and dY.shape[1] == 32 and K <= 27 and not rb.has_dup:
                     # narrow input, wide output (first layer): keep the wide dY rows stationary
                     table, kmap = rb.table_by_out()
-                    dW = gather_dw(table, K, ident, rb.M, dY, features, True, kmap, rb.m_dev, ov, filters)
+                    dW = gather_dw(table, K, ident, rb.M, dY, features, True, kmap, rb.m_dev, filters)
                 else:
                     table, pk = rb.table_by_in(features.shape[1], dY.shape[1], features, 3)
-                    dW = gather_dw(table, K, ident, rb.N, features, dY, False, None, rb.n_dev, ov, filters, pk)
+                    dW = gather_dw(table, K, ident, rb.N, features, dY, False, None, rb.n_dev, filters, pk)
             if ctx.needs_input_grad[0]:
                 table, pk = rb.table_by_in(dY.shape[1], W.shape[1], dY, 1)
                 dX = gather_conv(table, None, K, ident, rb.N, dY, W, True, None, rb.n_dev, ctx.w16, pk)
@@ -488,9 +463,7 @@ class SparseMaxPoolFunction(Function):
         rb = ctx.rb
         if not ctx.needs_input_grad[0]:
             return None, None
-        dY = grad_output.contiguous()
-        if dY.dtype != features.dtype:
-            dY = dY.to(features.dtype)
+        dY = as_grad(grad_output, features.dtype)
         table, pk = rb.nbr_out_packed, rb.packed_kl
         if table is None or not _lib.load().wfs_maxpool_packed_ok(pk, rb.K, int(features.shape[1]), _lib.dtype_code(features)):
             table, pk = rb.nbr_out, 0
@@ -524,13 +497,11 @@ class PointwiseConvFunction(Function):
         features, filters, bias = ctx.saved_tensors
         n_dev = ctx.n_dev
         R = int(features.shape[0])
-        dY = grad_output.contiguous()
-        if dY.dtype != features.dtype:
-            dY = dY.to(features.dtype)
+        dY = as_grad(grad_output, features.dtype)
         W = filters.detach().reshape(1, filters.shape[-2], filters.shape[-1]).float().contiguous()
         dX = dW = db = None
         if ctx.needs_input_grad[1]:
-            dW = gather_dw(None, 1, 0, R, features, dY, False, None, n_dev, False, filters)
+            dW = gather_dw(None, 1, 0, R, features, dY, False, None, n_dev, filters)
             dW = dW.reshape(filters.shape).to(filters.dtype)
         if ctx.needs_input_grad[0]:
             dX = gather_conv(None, None, 1, 0, R, dY, W, True, None, n_dev, ctx.w16)
@@ -598,9 +569,7 @@ class ToDenseFunction(Function):
         if ctx.cell_map is not None:
             ticket, slot, _keep, V = ctx.cell_map
             dtype, device = ctx.like
-            dY = grad_output.contiguous()
-            if dY.dtype != dtype:
-                dY = dY.to(dtype)
+            dY = as_grad(grad_output, dtype)
             dX = torch.empty((M, C), dtype=dtype, device=device)     # every valid row has exactly one cell
             _lib.check(lib.wfs_to_dense_bwd_mapped(_lib.ptr(dY), ticket, slot, M, _lib.ptr(ctx.m_dev), batch_size, V, C,
                                                    _lib.ptr(dX), _lib.dtype_code(dX), _lib.stream_ptr()))
@@ -654,9 +623,7 @@ def bn_relu_backward(x, grad_output, weight, bias, save_mean, save_invstd, train
     sum(g), sum(g * xhat) with the ReLU mask recomputed from x, then the elementwise pass)."""
     lib = _lib.load()
     N, C = x.shape
-    dy = grad_output.contiguous()
-    if dy.dtype != x.dtype:
-        dy = dy.to(x.dtype)
+    dy = as_grad(grad_output, x.dtype)
     dx = _rows(tuple(x.shape), x, n_dev)
     dgamma = grad_like(weight) if weight is not None else None
     dbeta = grad_like(bias) if bias is not None else None
@@ -721,13 +688,10 @@ class SkinnyLinearFunction(Function):
         ws = torch.empty((max(int(lib.wfs_head_workspace_bytes(B, I, O)), 1),), dtype=torch.uint8, device=x.device)
         want_db = bias is not None and ctx.needs_input_grad[2]
         db = grad_like(bias, (O,)) if (want_db and dw is not None) else None
-        defer = _DEFERRED_DW is not None and dw is not None and dw._base is not None and dx is not None
-        job = _lib.DwJob() if defer else None
+        job = _dw_job(dw) if dx is not None else None           # deferred only when dx is wanted too
         _lib.check(lib.wfs_head_bwd(_lib.ptr(x), _lib.ptr(g), B, I, _lib.ptr(w), O, _lib.ptr(dx), _lib.ptr(dw), _lib.ptr(db),
-                                    _lib.dtype_code(x), _lib.ptr(ws), ws.numel(), ctypes.byref(job) if defer else None,
-                                    _lib.stream_ptr()))
-        if defer and job.nslabs > 0:
-            _DEFERRED_DW.append((job, ws))          # the sum over the dW partials joins the pass's deferred reductions
+                                    _lib.dtype_code(x), _lib.ptr(ws), ws.numel(), job, _lib.stream_ptr()))
+        _queue_dw_job(job, ws)          # the sum over the dW partials joins the pass's deferred reductions
         if want_db and db is None:
             db = g.sum(0)
         return dx, (dw.to(weight.dtype) if dw is not None else None), (db.to(bias.dtype) if db is not None else None)
@@ -773,14 +737,11 @@ class SparseHeadFunction(Function):
         db = grad_like(bias, (O,)) if (want_db and dw is not None) else None
         ws = torch.empty((int(lib.wfs_sparse_head_workspace_bytes(ctx.batch_size, V, C, O)),), dtype=torch.uint8,
                          device=features.device)
-        defer = _DEFERRED_DW is not None and dw is not None and dw._base is not None
-        job = _lib.DwJob() if defer else None
+        job = _dw_job(dw)
         _lib.check(lib.wfs_sparse_head_bwd(_lib.ptr(features), _lib.ptr(g), ticket, slot, M, _lib.ptr(ctx.m_dev),
                                            ctx.batch_size, V, C, _lib.ptr(w), O, _lib.ptr(dx), _lib.ptr(dw), _lib.ptr(db),
-                                           _lib.dtype_code(features), _lib.ptr(ws), ws.numel(),
-                                           ctypes.byref(job) if defer else None, _lib.stream_ptr()))
-        if defer and job.nslabs > 0:
-            _DEFERRED_DW.append((job, ws))          # the sum over the per-slice dW partials joins the deferred reductions
+                                           _lib.dtype_code(features), _lib.ptr(ws), ws.numel(), job, _lib.stream_ptr()))
+        _queue_dw_job(job, ws)          # the sum over the per-slice dW partials joins the deferred reductions
         if want_db and db is None:
             db = g.sum(0)
         return (dx, (dw.to(weight.dtype) if dw is not None else None), (db.to(bias.dtype) if db is not None else None),

@@ -80,12 +80,10 @@ class SparseSequential(SparseModule):
         return False
 
     @staticmethod
-    def _prefetch_rulebooks(mods, x, owner=None):
+    def _prefetch_rulebooks(mods, x):
         """Build every layer's rulebook on a side stream now (device-count mode: nothing synchronises with the
         host).  Rulebooks depend on indices only, so the strided layers' builds run while the first layers
-        compute; each conv waits for its own rulebook's event.  ``owner``: a submanifold layer about to run on the
-        calling stream -- it and the layers sharing its indice_key keep building / finding their rulebook there, the
-        branch forks BEFORE it (its output has the input's rows, so nothing on the branch depends on it)."""
+        compute; each conv waits for its own rulebook's event."""
         from . import ops
         from .conv import SparseConvolution
         from .pool import SparseMaxPool
@@ -93,7 +91,6 @@ class SparseSequential(SparseModule):
         side = ops.side_stream(x.features.device)
         side.wait_stream(main)
         plan = {}
-        built = []
         keyed = {k: v.rulebook for k, v in x.indice_dict.items() if hasattr(v, "rulebook")}      # already built
         indices, spatial, n_dev = x.indices, x.spatial_shape, x.n_valid
         events = getattr(x, "events", None)
@@ -104,9 +101,6 @@ class SparseSequential(SparseModule):
                         continue
                     if m.inverse or m.transposed:
                         break                       # geometry comes from a coupled layer: leave the rest to the layers
-                    if owner is not None and (m is owner or (m.subm and m.indice_key is not None
-                                                             and m.indice_key == owner.indice_key)):
-                        continue
                     if m.indice_key is not None and m.indice_key in keyed:
                         rb = keyed[m.indice_key]
                     else:
@@ -115,9 +109,7 @@ class SparseSequential(SparseModule):
                                                 out_capacity=getattr(m, "out_capacity", None), events=events,
                                                 flags=m._sticky_flags(),
                                                 want_cell_map=SparseSequential._dense_follows(mods, at))
-                        built.append(rb)
-                        if ops.JOIN_PER_BUILD:
-                            rb.ready = _SideJoin(side)      # its own edge: the layer waits for THIS build only
+                        rb.ready = _SideJoin(side)      # its own edge: the layer waits for THIS build only
                         if m.indice_key is not None:
                             keyed[m.indice_key] = rb
                     plan[id(m)] = rb
@@ -131,20 +123,12 @@ class SparseSequential(SparseModule):
                                             out_capacity=getattr(m, "out_capacity", None), events=events,
                                             flags=m._sticky_flags(),
                                             want_cell_map=SparseSequential._dense_follows(mods, at))
-                    built.append(rb)
-                    if ops.JOIN_PER_BUILD:
-                        rb.ready = _SideJoin(side)
+                    rb.ready = _SideJoin(side)
                     plan[id(m)] = rb
                     indices, spatial, n_dev = rb.out_indices, rb.out_spatial_shape, rb.m_dev
                     events = getattr(rb, "events_out", None)
                 elif isinstance(m, SparseModule):
                     break                           # ToDense or an unknown sparse module ends the sparse stack
-            if built and not ops.JOIN_PER_BUILD:
-                # ONE join for the whole branch: the first layer that needs any of these rulebooks waits for all of them
-                # (every further cross-stream edge costs a captured step 5 - 10 us)
-                join = _SideJoin(side)
-                for rb in built:
-                    rb.ready = join
         x.prefetched = plan
 
     def forward(self, input):
@@ -166,13 +150,6 @@ class SparseSequential(SparseModule):
             if isinstance(module, SparseModule):
                 if _is_sparse_tensor(input):
                     input.dense_follows = self._dense_follows(mods, i)
-                if (want_prefetch and ops.PREFETCH_BEFORE_FIRST and getattr(input, "events", None) is not None
-                        and getattr(module, "subm", False) and not getattr(module, "conv1x1", False)
-                        and input.find_indice_pair(module.indice_key) is None):
-                    # the event offsets came with the batch: the strided layers' builds need nothing the first layer
-                    # makes, so the branch forks before its build and its conv rather than after them
-                    want_prefetch = False
-                    self._prefetch_rulebooks(mods[i:], input, owner=module)
                 input = module(input)
                 if want_prefetch and _is_sparse_tensor(input):
                     # the first layer has built its own rulebook and launched its conv on this stream; the

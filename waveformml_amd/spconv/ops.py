@@ -21,27 +21,11 @@ from .. import _lib
 ASSUME_VALID_UNIQUE_INDICES = False
 
 
-# Concurrency switches (both need a caller that follows the stated contract, so both default to off):
-#   PREFETCH_RULEBOOKS  in device-count mode SparseSequential builds the rulebooks of ALL its layers on a side
-#                       stream at the start of forward, so the strided layers' builds overlap the first layers'
-#                       compute (the builds depend on indices only).
-#   OVERLAP_DW          conv backward launches dW on a side stream while dX and the previous layers' backward
-#                       continue on the main stream.  Contract: parameter .grad is None when backward starts
-#                       (autograd then just stores the tensor) and whoever reads the gradients first calls
-#                       functional.join_side_streams() (psd/ddp.FlatGradAllReducer does; a fallback join also runs
-#                       when the backward pass ends).
+# PREFETCH_RULEBOOKS: in device-count mode SparseSequential builds the rulebooks of the layers behind its first one on
+# a side stream, so the strided layers' builds overlap the first layers' compute (the builds depend on indices only).
+# Every prefetched rulebook has its own edge back to the main chain: the first strided layer does not wait for the second
+# one's build.  Off by default; a runner that replays captured steps switches it on.
 PREFETCH_RULEBOOKS = False
-OVERLAP_DW = False
-# WFS_PREFETCH_BEFORE_FIRST=1: the branch of the prefetched builds forks BEFORE the first layer when the batch came with its
-# event offsets (a captured step's hand-over launch writes them) instead of behind the first layer's conv.  Off: same-box
-# A/B 0.4813 / 0.4806 ms against 0.4716 / 0.4704 -- the builds then end 23 us earlier, but the main chain's first kernel
-# (the SubM build) starts 18 us after the hand-over launch on the replay's second queue and shares the chip with the
-# first strided build (27 us instead of 18)
-PREFETCH_BEFORE_FIRST = os.environ.get("WFS_PREFETCH_BEFORE_FIRST", "0") == "1"
-# every prefetched rulebook has its own edge back to the main chain: the first strided layer does not wait for the second
-# one's build.  WFS_JOIN_PER_BUILD=0: one join for the whole branch (each cross-stream edge of a replayed graph costs
-# 6 - 10 us; with the 512-thread builds the per-build edges win: 0.4642 / 0.4659 vs 0.4695 / 0.4699 ms per step)
-JOIN_PER_BUILD = os.environ.get("WFS_JOIN_PER_BUILD", "1") != "0"
 
 # Event-local SubM rulebook build (round 3; csrc/evrulebook.hip): in device-count mode -- captured steps, where the index
 # rows come from the reference's collate_fn, i.e. grouped by event -- a SubM rulebook is built by a pair of workgroups
@@ -64,8 +48,9 @@ PACKED_TABLES = os.environ.get("WFS_PACKED_TABLES", "1") != "0"
 _SIDE_STREAMS = {}
 
 
-def side_stream(device, which=0):
-    key = (torch.device(device).index if torch.device(device).index is not None else torch.cuda.current_device(), which)
+def side_stream(device):
+    """The stream the prefetched rulebook builds run on (one per device)."""
+    key = torch.device(device).index if torch.device(device).index is not None else torch.cuda.current_device()
     if key not in _SIDE_STREAMS:
         _SIDE_STREAMS[key] = torch.cuda.Stream(device)
     return _SIDE_STREAMS[key]
