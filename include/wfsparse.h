@@ -857,6 +857,58 @@ int wfs_seg_energy_accumulate(const int32_t *coords, int64_t n_cap, const int64_
                               int32_t nE, double E_low, double E_high, double E_scale, int32_t *offsets,
                               int64_t *tables, int32_t *flags, void *stream);
 
+/* pairwise metric tables and the PID evaluator's rows (csrc/metricpairs.hip) -----------------------------
+ * The reference's MetricPairAggregator (src/evaluation/MetricAggregator.py:339-366) and the per-row half of
+ * PIDEvaluator.add (src/evaluation/PIDEvaluator.py:93-135) on the device.  Additions only: WFS_ABI_VERSION stays.
+ *
+ * wfs_metric_pairs_accumulate (one launch on `stream`, no read-back): bins a 0/1 result of M elements by each of P
+ * parameters and by every pair of them, per category.
+ *   params      float [P, M], row-major; 1 <= P <= WFS_METRIC_PAIRS_MAX; only read
+ *   result      int32 [M], 0 or 1 (anything else: flag 8, element left out)
+ *   category    int32 [M] in [0, n_classes); -1 = the element is skipped; anything else: flag 4, element left out
+ *   n_dev       valid elements as everywhere (NULL = M); elements beyond it are never read
+ *   lo, hi      double [P] on the HOST, hi > lo; nbins int32 [P] on the host, >= 1
+ *   tables      int64 [wfs_metric_pairs_table_ints], persistent, in this order: for each metric i a count table
+ *               [n_classes, nbins[i] + 2], then its match-sum table of the same shape; then for each pair i < j in the
+ *               order 0_1, 0_2, .., 0_P-1, 1_2, .. a count table [n_classes, nbins[i] + 2, nbins[j] + 2], then its
+ *               match-sum table.  Integer atomics only: exact, order-independent.
+ *   bins        get_bin_index in fp64 on the fp32 value: 0 below lo, nbins + 1 from hi, else the first j in 1 .. nbins
+ *               with j * ((hi - lo) / nbins) + lo > value (rounded product, rounded sum); 0 if there is none (NaN, or
+ *               a value just below hi that no rounded edge exceeds).  Computed without walking the bins.
+ *   flags       int32 [1], STICKY bits: 4 category outside [-1, n_classes), 8 result not 0 / 1
+ * wfs_match_categories (one launch): result[m] = (predictions[m] == labels[m]), category[m] = labels[m] (a label
+ *   outside int32 becomes -2, which the accumulate flags), for a caller that holds int64 class indices [M].
+ * wfs_pid_row_stats (two launches: event offsets, then one thread per row):
+ *   coords      int32 [n_cap, 3] = (x, y, event), event column non-decreasing in [0, E); n_dev as everywhere
+ *   predictions, targets  int64 [n_cap] in [0, WFS_PID_CLASSES)
+ *   phys        [n_cap, n_phys] of `dtype`; columns e_index, psd_index, z_index are read
+ *   seg_status  float [nx, ny] (0.5 = single-ended); offsets int32 [E + 1] scratch, zero-initialised once
+ *   outputs     per row, int32 [n_cap]: accuracy (prediction == target), multiplicity (rows of the row's event, the
+ *               lookahead ends with the valid rows), se (seg_status == 0.5), n_se (single-ended rows of the row's
+ *               event), category (target if se else -1); params float [4, n_cap] = E, PSD, multiplicity, z.  Rows
+ *               beyond the valid count and flagged rows get zeros and category -1.
+ *   tables      int64 [wfs_pid_table_ints], persistent, label-major [.., target, prediction]: SE_confusion [5, 5] over
+ *               single-ended rows, confusion_SE [n_se_max + 2, 5, 5] by n_se over [-0.5, n_se_max + 0.5] in
+ *               n_se_max + 1 bins, confusion_energy [n_confusion + 1, 5, 5] by E over [0, e_high] in n_confusion bins;
+ *               both with confusion_accumulate_1d's edges (a value above the range is dropped, one at it is bin 0).
+ *   flags       int32 [1], STICKY bits: 1 event column unsorted / out of range, 2 segment outside [nx, ny],
+ *               4 prediction or target outside [0, WFS_PID_CLASSES).  Flagged rows are left out. */
+#define WFS_METRIC_PAIRS_MAX 16
+#define WFS_PID_CLASSES 5
+size_t wfs_metric_pairs_table_ints(int32_t P, const int32_t *nbins, int32_t n_classes);
+int wfs_metric_pairs_accumulate(const float *params, const int32_t *result, const int32_t *category, int64_t M,
+                                const int64_t *n_dev, int32_t P, const double *lo, const double *hi,
+                                const int32_t *nbins, int32_t n_classes, int64_t *tables, int32_t *flags, void *stream);
+int wfs_match_categories(const int64_t *predictions, const int64_t *labels, int64_t M, int32_t *result,
+                         int32_t *category, void *stream);
+size_t wfs_pid_table_ints(int32_t n_confusion, int32_t n_se_max);
+int wfs_pid_row_stats(const int32_t *coords, const int64_t *predictions, const int64_t *targets, const void *phys,
+                      int32_t n_phys, int32_t dtype, int64_t n_cap, const int64_t *n_dev, int32_t E,
+                      const float *seg_status, int32_t nx, int32_t ny, int32_t e_index, int32_t psd_index,
+                      int32_t z_index, int32_t n_confusion, int32_t n_se_max, double e_high, int32_t *offsets,
+                      int32_t *accuracy, int32_t *multiplicity, int32_t *se, int32_t *n_se, float *params,
+                      int32_t *category, int64_t *tables, int32_t *flags, void *stream);
+
 /* opt-in per-kernel timing (HIP events on the launch stream), used by bench.py's roofline ---- */
 #define WFS_TIMER_GATHER_CONV 0
 #define WFS_TIMER_GATHER_DW 1

@@ -171,6 +171,13 @@ SIGNATURES = {
                               _vp, _vp]),
     "wfs_seg_energy_accumulate": (ctypes.c_int, [_vp, _i64, _vp, _i32] + [_vp, _i32, _i64, _i64, _i32] * 2 +
                                   [_vp, _i32, _i32, _i32, _i32, _dbl, _dbl, _dbl, _vp, _vp, _vp, _vp]),
+    "wfs_metric_pairs_table_ints": (_sz, [_i32, c_i32p, _i32]),
+    "wfs_metric_pairs_accumulate": (ctypes.c_int, [_vp, _vp, _vp, _i64, _vp, _i32, ctypes.POINTER(_dbl),
+                                                   ctypes.POINTER(_dbl), c_i32p, _i32, _vp, _vp, _vp]),
+    "wfs_match_categories": (ctypes.c_int, [_vp, _vp, _i64, _vp, _vp, _vp]),
+    "wfs_pid_table_ints": (_sz, [_i32, _i32]),
+    "wfs_pid_row_stats": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i64, _vp, _i32, _vp, _i32, _i32, _i32, _i32,
+                                         _i32, _i32, _i32, _dbl] + [_vp] * 10),
     "wfs_timing_enable": (ctypes.c_int, [_i32]),
     "wfs_timing_read": (ctypes.c_int, [_i32, ctypes.POINTER(ctypes.c_double), c_i64p]),
 }

@@ -32,6 +32,7 @@ constexpr int NPART = 9;
 
 #include "wfs_evoffsets.h"                   // valid_rows, k_eval_offsets (shared with segstats.hip)
 static_assert(EB == WFS_EVOFF_THREADS, "k_eval_offsets is launched with EB threads");
+#include "wfs_evalbins.h"                   // bin_metric, bin_confusion, add64 (shared with metricpairs.hip)
 
 // butterfly sums: every lane ends with the same bits (a + b and b + a are the same number)
 __device__ __forceinline__ double wave_sum(double v) {
@@ -317,29 +318,6 @@ struct EvalBins {
     int n_bins, n_mult, n_conf, n_se_max, nx, ny, C;
     double emin, emax, pmin, pmax;
 };
-
-// get_bin_index / metric_accumulate_2d: underflow in bin 0, >= high in bin nbins + 1
-__device__ __forceinline__ int bin_metric(double v, double low, double high, int nb) {
-    const double w = (high - low) / nb;
-    if (v < low) return 0;
-    if (v >= high) return nb + 1;
-    for (int j = 1; j <= nb; ++j)
-        if (__dadd_rn(__dmul_rn((double)j, w), low) > v) return j;
-    return 0;
-}
-// confusion_accumulate_1d: no underflow bin, and although it names bin nbins for values > high, its increment sits
-// inside `if find_bin:` -- values below low AND above high are dropped (-1); a value exactly at high finds no edge above
-// it and lands in bin 0, as in the reference
-__device__ __forceinline__ int bin_confusion(double v, double low, double high, int nb) {
-    const double w = (high - low) / nb;
-    if (v < low || v > high) return -1;
-    for (int j = 1; j <= nb; ++j)
-        if (__dadd_rn(__dmul_rn((double)j, w), low) > v) return j - 1;
-    return 0;
-}
-__device__ __forceinline__ void add64(long long *p, long long v) {
-    atomicAdd(reinterpret_cast<unsigned long long *>(p), (unsigned long long)v);
-}
 
 __global__ void __launch_bounds__(EB)
 k_eval_accumulate(int E, int Ts, EvalBins B, int event_blocks, const double *__restrict__ avg_coo,

@@ -1,0 +1,325 @@
+// metricpairs.hip -- the reference's MetricPairAggregator and the per-row half of its PIDEvaluator on the device.
+//
+// MetricPairAggregator.add / add_normalized (src/evaluation/MetricAggregator.py:339-366) bins a 0/1 result of every
+// element by each of P parameters (metric_accumulate_1d) and by every pair i < j (metric_accumulate_2d), per class.  Both
+// reference callers feed it a 0/1 result (find_matches, calculate_class_accuracy), so every table here is an int64 count
+// -- a count table and a match-sum table -- exact, independent of the order the elements arrive in and bit-identical from
+// run to run; the running mean / M2 of metric_accumulate_1d follow from the two counts on the host.
+//
+//   k_metric_pairs   one thread per element, grid-stride over slices of MP_SLICE elements per workgroup.  The 1-D tables
+//                    (few cells, every element hits P of them: the contended ones) go through an int32 image of them in
+//                    LDS that the workgroup flushes sparsely with int64 atomics; the pair tables (many cells, P(P-1)/2
+//                    hits spread over them) take int64 global atomics directly.  A miss adds nothing to a match-sum.
+//   k_pid_rows       one thread per row of a LitSegClassifier batch: accuracy, multiplicity (the length of the row's event
+//                    run from the offsets of wfs_evoffsets.h), single-ended flag, single-ended rows of its event, the
+//                    [4, N] parameter matrix and the category of PIDEvaluator.add (src/evaluation/PIDEvaluator.py:93-135);
+//                    the three confusion tables are folded in the same launch.
+//
+// Bins: get_bin_index in fp64 on the fp32 value of the element, without walking the bins: the candidate
+// floor((v - low) / width) + 1 is corrected by the reference's own predicate j * width + low > v (a rounded product and
+// a rounded sum, no fma) at the candidate and its neighbours, so every value lands where the walk would put it --
+// including the value just below `high` for which no edge is above it (bin 0) and NaN (bin 0).
+#include "wfs_common.h"
+
+namespace {
+
+#include "wfs_evoffsets.h"
+#include "wfs_evalbins.h"
+
+constexpr int MB = WFS_EVOFF_THREADS;
+constexpr int MP_MAX = 16;                    // WFS_METRIC_PAIRS_MAX
+constexpr int MP_SLICE = 4 * MB;              // elements per workgroup pass
+constexpr int MP_LDS_CELLS = 4096;            // cells of the 1-D image (2 x 16 KB of int32); above it the 1-D tables go direct
+constexpr int PID_CLASSES = 5;                // WFS_PID_CLASSES
+
+#ifndef MP_LDS_1D
+#define MP_LDS_1D 1                           // 0: timing variant, every table by direct global atomics
+#endif
+
+struct PairPlan {
+    int P, C, cells1;                         // cells1: sum over i of C * (nb[i] + 2)
+    int nb[MP_MAX];
+    double lo[MP_MAX], hi[MP_MAX];
+    long long off1[MP_MAX];                   // metric i: count table, then the match-sum table C * (nb[i] + 2) further
+    long long off2[MP_MAX];                   // first pair of row i (i_i+1); the pairs i_j follow in j
+    int img[MP_MAX];                          // metric i's offset in the LDS image
+};
+
+// get_bin_index(v, low, high, (high - low) / nb, nb) without the walk
+__device__ __forceinline__ int bin_direct(double v, double low, double high, int nb) {
+    if (v < low) return 0;
+    if (v >= high) return nb + 1;
+    if (!(v == v)) return 0;                  // NaN: no edge compares above it
+    const double w = (high - low) / nb;
+    double c = floor((v - low) / w) + 1.0;
+    c = c < 1.0 ? 1.0 : (c > (double)nb ? (double)nb : c);
+    int k = (int)c;
+    // edges are non-decreasing in j, so "j * w + low > v" is false up to some j and true from there on
+    while (k > 1 && __dadd_rn(__dmul_rn((double)(k - 1), w), low) > v) --k;
+    while (k <= nb && !(__dadd_rn(__dmul_rn((double)k, w), low) > v)) ++k;
+    return k <= nb ? k : 0;                   // no edge above v: the reference's bin_index stays 0
+}
+
+template <bool LDS1D>
+__global__ void __launch_bounds__(MB)
+k_metric_pairs(const float *__restrict__ params, const int *__restrict__ result, const int *__restrict__ category,
+               long long M, const long long *__restrict__ n_dev, PairPlan pl, long long *__restrict__ tab,
+               int *__restrict__ flags) {
+    extern __shared__ int image[];            // [2][cells1]: counts, then match sums
+    const long long nv = valid_rows(M, n_dev);
+    const int P = pl.P, C = pl.C;
+    for (long long base = (long long)blockIdx.x * MP_SLICE; base < nv; base += (long long)gridDim.x * MP_SLICE) {
+        if (LDS1D) {
+            for (int k = threadIdx.x; k < 2 * pl.cells1; k += MB) image[k] = 0;
+            __syncthreads();
+        }
+        for (int s = 0; s < MP_SLICE / MB; ++s) {
+            const long long m = base + s * MB + threadIdx.x;
+            if (m >= nv) break;
+            const int cat = category[m];
+            if (cat == -1) continue;
+            const int res = result[m];
+            if (cat < -1 || cat >= C) {
+                atomicOr(flags, 4);           // a class outside class_names
+                continue;
+            }
+            if (res != 0 && res != 1) {
+                atomicOr(flags, 8);           // not a 0/1 result
+                continue;
+            }
+            int b[MP_MAX];
+#pragma unroll
+            for (int i = 0; i < MP_MAX; ++i)
+                b[i] = i < P ? bin_direct((double)params[(long long)i * M + m], pl.lo[i], pl.hi[i], pl.nb[i]) : 0;
+            for (int i = 0; i < P; ++i) {
+                const int ni = pl.nb[i] + 2;
+                if (LDS1D) {
+                    const int cell = pl.img[i] + cat * ni + b[i];
+                    atomicAdd(image + cell, 1);
+                    if (res) atomicAdd(image + pl.cells1 + cell, 1);
+                } else {
+                    long long *t = tab + pl.off1[i] + (long long)cat * ni + b[i];
+                    add64(t, 1);
+                    if (res) add64(t + (long long)C * ni, 1);
+                }
+                long long *t2 = tab + pl.off2[i];
+                for (int j = i + 1; j < P; ++j) {
+                    const int nj = pl.nb[j] + 2;
+                    const long long cells = (long long)C * ni * nj;
+                    long long *t = t2 + ((long long)cat * ni + b[i]) * nj + b[j];
+                    add64(t, 1);
+                    if (res) add64(t + cells, 1);
+                    t2 += 2 * cells;
+                }
+            }
+        }
+        if (LDS1D) {
+            __syncthreads();
+            // the image's cells in table order: metric i's count cells, then its match-sum cells
+            for (int k = threadIdx.x; k < 2 * pl.cells1; k += MB) {
+                const int v = image[k];
+                if (v == 0) continue;
+                const int half = k >= pl.cells1 ? 1 : 0, cell = k - half * pl.cells1;
+                int i = 0;
+                while (i + 1 < P && pl.img[i + 1] <= cell) ++i;
+                const long long sz = (long long)C * (pl.nb[i] + 2);
+                add64(tab + pl.off1[i] + half * sz + (cell - pl.img[i]), v);
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// result = (prediction == label), category = label, for a caller that holds int64 class indices
+__global__ void __launch_bounds__(MB)
+k_match_categories(const long long *__restrict__ pred, const long long *__restrict__ labels, long long M,
+                   int *__restrict__ result, int *__restrict__ category) {
+    const long long m = (long long)blockIdx.x * MB + threadIdx.x;
+    if (m >= M) return;
+    const long long l = labels[m];
+    result[m] = pred[m] == l ? 1 : 0;
+    category[m] = l >= 0 && l < (1ll << 30) ? (int)l : -2;       // outside any class count: flagged by the accumulate
+}
+
+struct PidPlan {
+    int nx, ny, n_phys, e_index, psd_index, z_index, n_conf, n_se_max;
+    double e_high;                            // n_confusion / E_scale
+};
+
+template <typename T>
+__global__ void __launch_bounds__(MB)
+k_pid_rows(const int *__restrict__ coords, const long long *__restrict__ pred, const long long *__restrict__ targ,
+           const T *__restrict__ phys, long long n_cap, const long long *__restrict__ n_dev, int E,
+           const float *__restrict__ seg, PidPlan pp, const int *__restrict__ off, int *__restrict__ accuracy,
+           int *__restrict__ mult, int *__restrict__ se, int *__restrict__ n_se, float *__restrict__ params,
+           int *__restrict__ category, long long *__restrict__ tab, int *__restrict__ flags) {
+    const long long nv = valid_rows(n_cap, n_dev);
+    const long long r = (long long)blockIdx.x * MB + threadIdx.x;
+    if (r >= n_cap) return;
+    // a row that is not scored (beyond the valid count or flagged) still gets defined outputs; category -1 keeps it out
+    // of the pair tables
+    int o_acc = 0, o_mult = 0, o_se = 0, o_nse = 0, o_cat = -1;
+    float o_par[4] = {0.f, 0.f, 0.f, 0.f};
+    if (r < nv) {
+        const int x = coords[r * 3], y = coords[r * 3 + 1], e = coords[r * 3 + 2];
+        const long long p = pred[r], t = targ[r];
+        if (e < 0 || e >= E) {
+            atomicOr(flags, 1);               // k_eval_offsets has set it already
+        } else if (x < 0 || x >= pp.nx || y < 0 || y >= pp.ny) {
+            atomicOr(flags, 2);               // a segment outside the detector
+        } else if (p < 0 || p >= PID_CLASSES || t < 0 || t >= PID_CLASSES) {
+            atomicOr(flags, 4);               // a class outside PID_MAPPED_NAMES
+        } else {
+            long long b = off[e], en = off[e + 1];
+            b = b < 0 ? 0 : (b > nv ? nv : b);
+            en = en < 0 ? 0 : (en > nv ? nv : en);
+            if (en < b) en = b;               // only with a flagged (unsorted) event column
+            o_mult = (int)(en - b);
+            for (long long q = b; q < en; ++q) {
+                const int qx = coords[q * 3], qy = coords[q * 3 + 1];
+                // a row outside the grid raises flag 2 itself
+                if (qx >= 0 && qx < pp.nx && qy >= 0 && qy < pp.ny && seg[qx * pp.ny + qy] == 0.5f) ++o_nse;
+            }
+            o_acc = p == t ? 1 : 0;
+            o_se = seg[x * pp.ny + y] == 0.5f ? 1 : 0;
+            const T *row = phys + r * pp.n_phys;
+            o_par[0] = wfs_ld(row + pp.e_index);
+            o_par[1] = wfs_ld(row + pp.psd_index);
+            o_par[2] = (float)o_mult;
+            o_par[3] = wfs_ld(row + pp.z_index);
+            o_cat = o_se ? (int)t : -1;
+            // table order: wfs_pid_table_ints
+            constexpr int CC = PID_CLASSES * PID_CLASSES;
+            const long long cell = t * PID_CLASSES + p;
+            long long *t_se = tab, *t_nse = t_se + CC, *t_ene = t_nse + (long long)(pp.n_se_max + 2) * CC;
+            if (o_se) add64(t_se + cell, 1);
+            int k = bin_confusion((double)o_nse, -0.5, pp.n_se_max + 0.5, pp.n_se_max + 1);
+            if (k >= 0) add64(t_nse + (long long)k * CC + cell, 1);
+            k = bin_confusion((double)o_par[0], 0.0, pp.e_high, pp.n_conf);
+            if (k >= 0) add64(t_ene + (long long)k * CC + cell, 1);
+        }
+    }
+    accuracy[r] = o_acc;
+    mult[r] = o_mult;
+    se[r] = o_se;
+    n_se[r] = o_nse;
+    category[r] = o_cat;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) params[(long long)k * n_cap + r] = o_par[k];
+}
+
+bool make_plan(int P, const int32_t *nbins, const double *lo, const double *hi, int C, PairPlan *pl, size_t *total) {
+    if (P < 1 || P > MP_MAX || C < 1 || !nbins) return false;
+    pl->P = P, pl->C = C;
+    size_t at = 0;
+    int img = 0;
+    for (int i = 0; i < P; ++i) {
+        if (nbins[i] < 1 || nbins[i] > (1 << 20)) return false;
+        if (lo && hi && !(hi[i] > lo[i])) return false;
+        pl->nb[i] = nbins[i];
+        pl->lo[i] = lo ? lo[i] : 0.0;
+        pl->hi[i] = hi ? hi[i] : 1.0;
+        pl->off1[i] = (long long)at;
+        pl->img[i] = img;
+        at += 2 * (size_t)C * ((size_t)nbins[i] + 2);
+        if ((size_t)img + (size_t)C * ((size_t)nbins[i] + 2) > (size_t)1 << 30) return false;
+        img += C * (nbins[i] + 2);
+    }
+    pl->cells1 = img;
+    for (int i = 0; i < P; ++i) {
+        pl->off2[i] = (long long)at;
+        for (int j = i + 1; j < P; ++j) at += 2 * (size_t)C * ((size_t)nbins[i] + 2) * ((size_t)nbins[j] + 2);
+    }
+    for (int i = P; i < MP_MAX; ++i) pl->nb[i] = 1, pl->lo[i] = 0, pl->hi[i] = 1, pl->off1[i] = pl->off2[i] = 0, pl->img[i] = 0;
+    *total = at;
+    return true;
+}
+
+}  // namespace
+
+extern "C" size_t wfs_metric_pairs_table_ints(int32_t P, const int32_t *nbins, int32_t n_classes) {
+    PairPlan pl;
+    size_t total = 0;
+    return make_plan(P, nbins, nullptr, nullptr, n_classes, &pl, &total) ? total : 0;
+}
+
+extern "C" int wfs_metric_pairs_accumulate(const float *params, const int32_t *result, const int32_t *category,
+                                           int64_t M, const int64_t *n_dev, int32_t P, const double *lo,
+                                           const double *hi, const int32_t *nbins, int32_t n_classes, int64_t *tables,
+                                           int32_t *flags, void *stream) {
+    PairPlan pl;
+    size_t total = 0;
+    WFS_REQUIRE(lo && hi && make_plan(P, nbins, lo, hi, n_classes, &pl, &total), WFS_EINVAL,
+                "wfs_metric_pairs_accumulate: P = %d (1 .. %d), classes = %d, or a bad bin count / range (high > low)", P,
+                MP_MAX, n_classes);
+    WFS_REQUIRE(M >= 0 && M < (1ll << 31), WFS_EINVAL, "wfs_metric_pairs_accumulate: M = %lld", (long long)M);
+    WFS_REQUIRE(tables && flags && (M == 0 || (params && result && category)), WFS_EINVAL,
+                "wfs_metric_pairs_accumulate: NULL argument");
+    if (M == 0) return WFS_OK;
+    long long blocks = wfs_cdiv(M, MP_SLICE);
+    if (blocks > 1024) blocks = 1024;
+    hipStream_t s = (hipStream_t)stream;
+    if (MP_LDS_1D && pl.cells1 <= MP_LDS_CELLS)
+        k_metric_pairs<true><<<(unsigned)blocks, MB, 2 * (size_t)pl.cells1 * sizeof(int), s>>>(
+            params, result, category, M, (const long long *)n_dev, pl, (long long *)tables, flags);
+    else
+        k_metric_pairs<false><<<(unsigned)blocks, MB, 0, s>>>(params, result, category, M, (const long long *)n_dev, pl,
+                                                              (long long *)tables, flags);
+    WFS_LAUNCH_CHECK();
+    return WFS_OK;
+}
+
+extern "C" int wfs_match_categories(const int64_t *predictions, const int64_t *labels, int64_t M, int32_t *result,
+                                    int32_t *category, void *stream) {
+    WFS_REQUIRE(M >= 0 && M < (1ll << 31), WFS_EINVAL, "wfs_match_categories: M = %lld", (long long)M);
+    WFS_REQUIRE(M == 0 || (predictions && labels && result && category), WFS_EINVAL, "wfs_match_categories: NULL argument");
+    if (M == 0) return WFS_OK;
+    k_match_categories<<<(unsigned)wfs_cdiv(M, MB), MB, 0, (hipStream_t)stream>>>(
+        (const long long *)predictions, (const long long *)labels, M, result, category);
+    WFS_LAUNCH_CHECK();
+    return WFS_OK;
+}
+
+extern "C" size_t wfs_pid_table_ints(int32_t n_confusion, int32_t n_se_max) {
+    return (size_t)PID_CLASSES * PID_CLASSES * (1 + ((size_t)n_se_max + 2) + ((size_t)n_confusion + 1));
+}
+
+extern "C" int wfs_pid_row_stats(const int32_t *coords, const int64_t *predictions, const int64_t *targets,
+                                 const void *phys, int32_t n_phys, int32_t dtype, int64_t n_cap, const int64_t *n_dev,
+                                 int32_t E, const float *seg_status, int32_t nx, int32_t ny, int32_t e_index,
+                                 int32_t psd_index, int32_t z_index, int32_t n_confusion, int32_t n_se_max,
+                                 double e_high, int32_t *offsets, int32_t *accuracy, int32_t *multiplicity, int32_t *se,
+                                 int32_t *n_se, float *params, int32_t *category, int64_t *tables, int32_t *flags,
+                                 void *stream) {
+    WFS_REQUIRE(wfs_dtype_ok(dtype), WFS_EINVAL, "wfs_pid_row_stats: unknown dtype %d", dtype);
+    WFS_REQUIRE(E >= 1 && n_cap >= 0 && n_cap < (1ll << 31) && nx >= 1 && ny >= 1, WFS_EINVAL,
+                "wfs_pid_row_stats: E = %d, n_cap = %lld, grid %d x %d", E, (long long)n_cap, nx, ny);
+    WFS_REQUIRE(n_phys >= 1 && e_index >= 0 && e_index < n_phys && psd_index >= 0 && psd_index < n_phys && z_index >= 0 &&
+                    z_index < n_phys,
+                WFS_EINVAL, "wfs_pid_row_stats: column indices %d, %d, %d outside [0, %d)", e_index, psd_index, z_index,
+                n_phys);
+    WFS_REQUIRE(n_confusion >= 1 && n_se_max >= 0 && e_high > 0, WFS_EINVAL, "wfs_pid_row_stats: bad bin parameters");
+    WFS_REQUIRE(seg_status && offsets && tables && flags &&
+                    (n_cap == 0 || (coords && predictions && targets && phys && accuracy && multiplicity && se && n_se &&
+                                    params && category)),
+                WFS_EINVAL, "wfs_pid_row_stats: NULL argument");
+    hipStream_t s = (hipStream_t)stream;
+    if (n_cap == 0) return WFS_OK;
+    const unsigned rb = (unsigned)wfs_cdiv(n_cap, MB);
+    k_eval_offsets<<<rb, MB, 0, s>>>(coords, n_cap, (const long long *)n_dev, E, offsets, flags);
+    WFS_LAUNCH_CHECK();
+    const PidPlan pp = {nx, ny, n_phys, e_index, psd_index, z_index, n_confusion, n_se_max, e_high};
+#define WFS_PIDROWS(TYPE)                                                                                              \
+    k_pid_rows<TYPE><<<rb, MB, 0, s>>>(coords, (const long long *)predictions, (const long long *)targets,            \
+                                       (const TYPE *)phys, n_cap, (const long long *)n_dev, E, seg_status, pp, offsets, \
+                                       accuracy, multiplicity, se, n_se, params, category, (long long *)tables, flags)
+    if (dtype == WFS_F32)
+        WFS_PIDROWS(float);
+    else if (dtype == WFS_BF16)
+        WFS_PIDROWS(wfs_bf16);
+    else
+        WFS_PIDROWS(wfs_f16);
+#undef WFS_PIDROWS
+    WFS_LAUNCH_CHECK();
+    return WFS_OK;
+}

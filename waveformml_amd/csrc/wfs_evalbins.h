@@ -1,0 +1,28 @@
+// wfs_evalbins.h -- the bin walks and the int64 add of the evaluation tables (evalstats.hip, metricpairs.hip).  Included
+// into each file's anonymous namespace.  Edges follow the reference literally: the first j with j * width + low > value,
+// a rounded product and a rounded sum (no fma).
+#pragma once
+#include "wfs_common.h"
+
+// get_bin_index / metric_accumulate_2d: underflow in bin 0, >= high in bin nbins + 1
+__device__ __forceinline__ int bin_metric(double v, double low, double high, int nb) {
+    const double w = (high - low) / nb;
+    if (v < low) return 0;
+    if (v >= high) return nb + 1;
+    for (int j = 1; j <= nb; ++j)
+        if (__dadd_rn(__dmul_rn((double)j, w), low) > v) return j;
+    return 0;
+}
+// confusion_accumulate_1d: no underflow bin, and although it names bin nbins for values > high, its increment sits
+// inside `if find_bin:` -- values below low AND above high are dropped (-1); a value exactly at high finds no edge above
+// it and lands in bin 0, as in the reference
+__device__ __forceinline__ int bin_confusion(double v, double low, double high, int nb) {
+    const double w = (high - low) / nb;
+    if (v < low || v > high) return -1;
+    for (int j = 1; j <= nb; ++j)
+        if (__dadd_rn(__dmul_rn((double)j, w), low) > v) return j - 1;
+    return 0;
+}
+__device__ __forceinline__ void add64(long long *p, long long v) {
+    atomicAdd(reinterpret_cast<unsigned long long *>(p), (unsigned long long)v);
+}

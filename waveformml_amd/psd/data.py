@@ -281,6 +281,12 @@ def make_loader(dataset, items_per_batch, num_workers=0, shuffle=False, pin_memo
 def to_device(batch, device, feature_dtype=None, non_blocking=True):
     (c, f), y = batch
     c = c.to(device, non_blocking=non_blocking)
+    if isinstance(f, (list, tuple)):
+        # [feats, *additional_fields] (HDF5Dataset's ``additional_fields``): the fields keep their dtype
+        f = [t.to(device, non_blocking=non_blocking) for t in f]
+        if feature_dtype is not None:
+            f[0] = f[0].to(feature_dtype)
+        return [c, f], y.to(device, non_blocking=non_blocking)
     f = f.to(device, non_blocking=non_blocking)
     if feature_dtype is not None:
         f = f.to(feature_dtype)

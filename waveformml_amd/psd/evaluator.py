@@ -6,9 +6,11 @@ launches on the current stream (csrc/evalstats.hip: event offsets, per-event pul
 is read back until ``results()``.
 
 What is mirrored: the constructor defaults, the accumulators of ``add`` (``mult_acc``, ``ene_psd_acc``, ``pos_acc``,
-``confusion_energy``, ``confusion_SE``, the summed pulses and their counts) and ``finalize()``.  What is not: TensorBoard
-histograms, plots, ``MetricPairAggregator`` (its input, the ``[9, E]`` feature matrix of the last batch, is
-``self.features``), ``PhysEvaluator`` and the calibration database -- a caller that has gains passes them as an array.
+``confusion_energy``, ``confusion_SE``, the summed pulses and their counts) and ``finalize()``; with ``metric_pairs=True``
+also ``MetricPairAggregator``'s per-class tables over the nine metrics of ``_init_results`` (psd/metric_pairs.py, two more
+launches per ``add``; their input is ``self.features``, the ``[9, E]`` feature matrix of the batch).  What is not:
+TensorBoard histograms, plots, ``PhysEvaluator`` and the calibration database -- a caller that has gains passes them as
+an array.
 
 Two things of the reference that matter for comparing numbers:
 
@@ -21,6 +23,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from .metric_pairs import MetricPairTables, split_results, triple_1d
 
 FLAG_TEXT = {1: "the event column of a batch was not sorted or held an event outside the batch",
              2: "a segment coordinate lay outside the detector grid",
@@ -43,7 +46,7 @@ def result_shapes(class_names, n_bins=100, n_mult=10, n_confusion=10, n_SE_max=4
 class PSDEvaluator:
     def __init__(self, class_names, device, gains=None, seg_status=None, n_samples=150, n_bins=100, n_mult=10,
                  n_confusion=10, n_SE_max=4, emin=0.0, emax=5.0, psd_min=0.0, psd_max=0.6, nx=14, ny=11,
-                 fix_last_event_n_SE=False):
+                 fix_last_event_n_SE=False, metric_pairs=False):
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("waveformml_amd: PSDEvaluator runs on the GPU (there is no CPU path); got %s" % self.device)
@@ -74,6 +77,14 @@ class PSDEvaluator:
         self.sum_labelled = torch.zeros((C, W), dtype=torch.float64, device=self.device)
         self.flags = torch.zeros(1, dtype=torch.int32, device=self.device)
         self._rows_cap, self._events_cap = 0, 0
+        # MetricPairAggregator over _init_results' nine metrics; energy, psd and multiplicity follow this evaluator's ranges
+        self.metric_pairs = None
+        if metric_pairs:
+            self.metric_pairs = MetricPairTables(self.device, [
+                ("energy", self.emin, self.emax, self.n_bins), ("psd", self.psd_min, self.psd_max, self.n_bins),
+                ("multiplicity", 0.5, self.n_mult + 0.5, self.n_mult), ("x_dev", 0., 4., 20), ("y_dev", 0., 3., 20),
+                ("$\\Delta$t_dev", 0., 10., 20), ("E_dev", 0., 2., 40), ("t_variance", 0., 1000.0, 40),
+                ("n_variance", 0.0, 0.25, 40)], self.class_names)
 
     def _reserve(self, rows, events):
         """Per-batch buffers; allocated on the first call and again only when a batch exceeds them."""
@@ -93,6 +104,9 @@ class PSDEvaluator:
             self.psdr = torch.zeros(E, dtype=torch.float32, device=dev)
             self.energy = torch.zeros(E, dtype=torch.float32, device=dev)
             self.features = torch.zeros((9, E), dtype=torch.float32, device=dev)
+            if self.metric_pairs is not None:
+                self._match = torch.zeros(E, dtype=torch.int32, device=dev)
+                self._category = torch.zeros(E, dtype=torch.int32, device=dev)
             self._events_cap = E
 
     def add(self, batch, output, predictions):
@@ -129,20 +143,30 @@ class PSDEvaluator:
             p(self.psdl), p(self.psdr), p(self.energy), p(predictions), p(labels), self.n_bins, self.n_mult,
             self.n_confusion, self.n_SE_max, self.nx, self.ny, self.emin, self.emax, self.psd_min, self.psd_max,
             p(self.tables), p(self.sum_wf), p(self.sum_labelled), p(self.flags), st))
+        if self.metric_pairs is not None:
+            # the reference's class loop (results[label_class_inds], skipping empty classes) is category = label; the
+            # rows of self.features are in its concatenate order: energy, psdl, multiplicity, the six output_stats
+            _lib.check(lib.wfs_match_categories(p(predictions), p(labels), E, p(self._match), p(self._category), st))
+            self.metric_pairs.add(self.features, self._match, self._category)
 
     def reset(self):
         self.tables.zero_()
         self.sum_wf.zero_()
         self.sum_labelled.zero_()
         self.flags.zero_()
+        if self.metric_pairs is not None:
+            self.metric_pairs.reset()
 
     def state_tensors(self):
         """The persistent accumulators; all are sums over batches, so N ranks combine them with one SUM all-reduce each
         (psd/evaluate.test_loop)."""
-        return [self.tables, self.sum_wf, self.sum_labelled]
+        own = [self.tables, self.sum_wf, self.sum_labelled]
+        return own if self.metric_pairs is None else own + self.metric_pairs.state_tensors()
 
     def _check_flags(self):
         f = int(self.flags.item())
+        if self.metric_pairs is not None:
+            f |= int(self.metric_pairs.flags.item()) & 4
         if f:
             raise RuntimeError("PSDEvaluator: " + "; ".join(t for b, t in FLAG_TEXT.items() if f & b))
 
@@ -158,15 +182,6 @@ class PSDEvaluator:
             t[name] = host[at:at + size].reshape(shape).copy()
             at += size
         nb, nm = self.n_bins + 2, self.n_mult + 2
-
-        def triple_1d(matches, n):
-            # the sequential Welford update of metric_accumulate_1d over 0/1 results, in closed form, then finalize()
-            m, c = matches.astype(np.float64), n.astype(np.float64)
-            safe = np.where(n > 0, c, 1.0)
-            mean = np.where(n > 0, m / safe, 0.0)
-            M2 = np.where(n > 0, m * (c - m) / safe, 0.0)
-            dev = np.where(n > 2, np.sqrt(M2 / np.where(n > 2, c - 1.0, 1.0)), 0.0)
-            return mean, n.copy(), dev
 
         def empty_1d(k):
             return np.zeros(k), np.zeros(k, np.int64), np.zeros(k)
@@ -188,4 +203,7 @@ class PSDEvaluator:
         res["n_wfs"] = t["n_wfs"]
         res["summed_labelled_waveforms"] = self.sum_labelled.cpu().numpy().astype(np.float32)
         res["n_labelled_wfs"] = t["n_labelled_wfs"]
+        if self.metric_pairs is not None:
+            mp = self.metric_pairs
+            res["metric_pairs"] = split_results(mp.tables.cpu().numpy(), mp._layout, mp.names)
         return res

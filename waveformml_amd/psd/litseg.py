@@ -1,11 +1,15 @@
 """``LitSegClassifier``: host-side mirror of the reference's per-SEGMENT classifier (src/engineering/LitSegClassifier.py:15-100
 on src/engineering/LitBase.py:13-55): the net -- ``SPConvNet.SPConvPreserveNet`` in config/examples/IoniClassifierCNN.json --
 returns one logit row per ACTIVE segment [N, n_type], the target holds one label per row, the criterion is mean-reduced
-(``net_config.SELoss``: over the rows of single-ended segments only).  The torch_geometric ``Data`` batch form, the
-torchmetrics objects and the PIDEvaluator / ROC plumbing are out of scope.
+(``net_config.SELoss``: over the rows of single-ended segments only).  ``evaluator`` is the reference's ``PIDEvaluator`` on
+the GPU (psd/pid_evaluator.py); ``test_step`` keeps what its ``add`` takes in ``last_test_outputs``, so
+``evaluate.segment_test_loop(module, loader, device, evaluator=module.evaluator)`` fills the PID tables without a read-back
+per batch.  The torch_geometric ``Data`` batch form, the torchmetrics objects and the ROC plumbing are out of scope
+(SURVEY.md 2).
 """
 import torch
 
+from .config import DictionaryUtility
 from .lit import LitPSD
 from .segments import SE_DEAD_PMTS, segment_status, single_ended_mask
 
@@ -20,6 +24,27 @@ class LitSegClassifier(LitPSD):
         if self.SE_only:
             dead = getattr(config.net_config, "SE_dead_pmts", SE_DEAD_PMTS)
             self.register_buffer("SE_mask", single_ended_mask(segment_status(dead)))
+        self.last_test_outputs = None     # test_step's (pred, target, c, additional_fields), for segment_test_loop
+        self._evaluator = None
+
+    @property
+    def evaluator(self):
+        """The ``PIDEvaluator`` the reference builds in ``__init__`` (LitSegClassifier.py:26-33), built on first use on
+        the device the model lives on: ``additional_field_names`` from ``dataset_config.test_dataset_params
+        .additional_fields``, then ``config.evaluation_config`` as keyword arguments (``excludes``, the reference's name
+        for the dead PMTs, included).  Nothing calls it implicitly: hand it to ``evaluate.segment_test_loop``."""
+        if self._evaluator is None:
+            from .pid_evaluator import PIDEvaluator
+            params = {}
+            test_params = getattr(getattr(self.config, "dataset_config", None), "test_dataset_params", None)
+            if hasattr(test_params, "additional_fields"):
+                params["additional_field_names"] = list(test_params.additional_fields)
+            if hasattr(self.config, "evaluation_config"):
+                params.update(DictionaryUtility.to_dict(self.config.evaluation_config))
+            if "excludes" in params:
+                params["dead_pmts"] = params.pop("excludes")
+            self._evaluator = PIDEvaluator(next(self.model.parameters()).device, **params)
+        return self._evaluator
 
     # reference LitSegClassifier._process_batch, :36-63
     def _process_batch(self, batch):
@@ -56,8 +81,9 @@ class LitSegClassifier(LitPSD):
         return results
 
     def test_step(self, batch, batch_idx):
-        loss, predictions, target = self._process_batch(batch)[:3]
+        loss, predictions, target, c, _f, additional_fields = self._process_batch(batch)
         pred = torch.argmax(self.softmax(predictions), dim=1)
+        self.last_test_outputs = (pred, target, c, additional_fields)
         results = {"test_loss": loss, "test_acc": (pred == target).float().mean()}
         self.log_dict(results, on_epoch=True, logger=True)
         return results

@@ -1,0 +1,138 @@
+"""``MetricPairTables``: the reference's ``MetricPairAggregator`` (src/evaluation/MetricAggregator.py:339-366, over its
+``MetricAggregator`` / ``Metric2DAggregator``) on the GPU: a 0/1 result of every element binned by each of P parameters
+and by every pair of them, per class.
+
+``add`` is one HIP launch on the current stream (csrc/metricpairs.hip); nothing is read back until ``results()``.  Both
+reference callers feed the aggregator a 0/1 result (``find_matches``, ``calculate_class_accuracy``), so every table is an
+exact int64 count -- a count table and a match-sum table -- bit-identical from run to run, and N ranks combine them with
+one integer SUM.  The running mean / M2 that ``metric_accumulate_1d`` keeps follow from the two counts in closed form
+(``triple_1d``).  Results that are not 0/1 (``WaveformEvaluator``'s deviations) are not supported and are rejected.
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from .. import _lib
+
+MAX_METRICS = 16                # WFS_METRIC_PAIRS_MAX, include/wfsparse.h
+FLAG_TEXT = {4: "a category lay outside class_names",
+             8: "a result was neither 0 nor 1"}
+
+
+def triple_1d(matches, n):
+    """(mean, n, dev) of ``metric_accumulate_1d``'s sequential Welford update over 0/1 results, in closed form from the
+    sum of matches and the count, after ``finalize`` / ``finalize2d`` (dev = sqrt(M2 / (n - 1)) when n > 2, else 0)."""
+    m, c = matches.astype(np.float64), n.astype(np.float64)
+    safe = np.where(n > 0, c, 1.0)
+    mean = np.where(n > 0, m / safe, 0.0)
+    M2 = np.where(n > 0, m * (c - m) / safe, 0.0)
+    dev = np.where(n > 2, np.sqrt(M2 / np.where(n > 2, c - 1.0, 1.0)), 0.0)
+    return mean, n.copy(), dev
+
+
+def bin_edge_range(low, high, n_bins):
+    """First and last entry of the reference's ``get_bins(low, high, n_bins)`` (src/utils/util.py): what
+    ``MetricAggregator`` keeps as ``bin_edges[0]`` / ``bin_edges[-1]`` and bins by."""
+    width = (high - low) / n_bins
+    edges = np.arange(low, high + width / 2, width)
+    return float(edges[0]), float(edges[-1])
+
+
+def normalized_range(low, high, norm_factor):
+    """The range ``MetricAggregator.add_normalized`` bins a parameter normalised to [0, 1] by."""
+    if norm_factor is None:
+        return 0.0, 1.0
+    if low < 0:
+        return low / norm_factor + 0.5, high / norm_factor + 0.5
+    return low / norm_factor, high / norm_factor
+
+
+def table_layout(n_bins, n_classes):
+    """(key, shape) of every table in the order of include/wfsparse.h; each stands for a count table followed by a
+    match-sum table of that shape.  Keys: the metric's index, or ``"i_j"`` for a pair."""
+    P, C = len(n_bins), int(n_classes)
+    layout = [(i, (C, n_bins[i] + 2)) for i in range(P)]
+    for i in range(P - 1):
+        for j in range(i + 1, P):
+            layout.append(("%d_%d" % (i, j), (C, n_bins[i] + 2, n_bins[j] + 2)))
+    return layout
+
+
+class MetricPairTables:
+    def __init__(self, device, metrics, class_names):
+        """``metrics``: a list of ``(name, low, high, n_bins)``, ``MetricAggregator``'s leading arguments."""
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("waveformml_amd: MetricPairTables runs on the GPU (there is no CPU path); got %s" % self.device)
+        self.class_names = list(class_names)
+        self.n_classes = len(self.class_names)
+        self.names = [str(m[0]) for m in metrics]
+        self.n_bins = [int(m[3]) for m in metrics]
+        self.P = len(self.names)
+        if not 1 <= self.P <= MAX_METRICS or self.n_classes < 1 or min(self.n_bins) < 1:
+            raise ValueError("MetricPairTables: 1 to %d metrics with at least one bin each and at least one class" % MAX_METRICS)
+        self.ranges = [bin_edge_range(float(m[1]), float(m[2]), int(m[3])) for m in metrics]
+        self._nb = _lib.i32_array(self.n_bins)
+        self._layout = table_layout(self.n_bins, self.n_classes)
+        n = int(_lib.load().wfs_metric_pairs_table_ints(self.P, self._nb, self.n_classes))
+        assert n == sum(2 * int(np.prod(s)) for _k, s in self._layout)
+        self.tables = torch.zeros(n, dtype=torch.int64, device=self.device)
+        self.flags = torch.zeros(1, dtype=torch.int32, device=self.device)
+
+    def add(self, params, result, category, n_valid=None, ranges=None):
+        """``params`` float32 [P, M]; ``result`` int32 [M] of 0 / 1; ``category`` int32 [M], the class index of every
+        element or -1 to leave it out; ``n_valid`` a device int64 count of the valid elements.  ``ranges``: one
+        ``(low, high)`` per metric; the default bins by the metrics' own edges (the reference's ``add``), a caller
+        passes ``add_normalized``'s ranges.  Launches on the current stream; no read-back."""
+        M = int(result.shape[0])
+        if params.dtype != torch.float32 or tuple(params.shape) != (self.P, M):
+            raise RuntimeError("MetricPairTables.add: params must be float32 [%d, %d], got %s %s"
+                               % (self.P, M, params.dtype, tuple(params.shape)))
+        if result.dtype != torch.int32 or category.dtype != torch.int32 or category.shape[0] != M:
+            raise RuntimeError("MetricPairTables.add: result (0 / 1) and category must be int32 [%d]; real-valued "
+                               "results are not supported" % M)
+        if n_valid is not None and (n_valid.dtype != torch.int64 or not n_valid.is_cuda):
+            raise RuntimeError("MetricPairTables.add: n_valid must be a device int64")
+        ranges = self.ranges if ranges is None else ranges
+        if len(ranges) != self.P:
+            raise ValueError("MetricPairTables.add: one (low, high) per metric")
+        lo = (ctypes.c_double * self.P)(*[float(r[0]) for r in ranges])
+        hi = (ctypes.c_double * self.P)(*[float(r[1]) for r in ranges])
+        p = _lib.ptr
+        _lib.check(_lib.load().wfs_metric_pairs_accumulate(
+            p(params), p(result), p(category), M, p(n_valid), self.P, lo, hi, self._nb, self.n_classes, p(self.tables),
+            p(self.flags), _lib.stream_ptr()))
+
+    def reset(self):
+        self.tables.zero_()
+        self.flags.zero_()
+
+    def state_tensors(self):
+        """The persistent accumulator: integer sums over batches, so N ranks combine it with one SUM all-reduce."""
+        return [self.tables]
+
+    def _check_flags(self):
+        f = int(self.flags.item())
+        if f:
+            raise RuntimeError("MetricPairTables: " + "; ".join(t for b, t in FLAG_TEXT.items() if f & b))
+
+    def results(self):
+        """One read-back: ``{"metrics": {name: (mean, n, dev)}, "pairs": {"i_j": (sum of matches, n)}}`` with the
+        reference's shapes [C, nb + 2] and [C, nb_i + 2, nb_j + 2]."""
+        self._check_flags()
+        return split_results(self.tables.cpu().numpy(), self._layout, self.names)
+
+
+def split_results(host, layout, names):
+    out, at = {"metrics": {}, "pairs": {}}, 0
+    for key, shape in layout:
+        size = int(np.prod(shape))
+        n = host[at:at + size].reshape(shape).copy()
+        m = host[at + size:at + 2 * size].reshape(shape)
+        at += 2 * size
+        if isinstance(key, int):
+            out["metrics"][names[key]] = triple_1d(m, n)
+        else:
+            out["pairs"][key] = (m.astype(np.float64), n)
+    return out
