@@ -909,6 +909,45 @@ int wfs_pid_row_stats(const int32_t *coords, const int64_t *predictions, const i
                       int32_t *accuracy, int32_t *multiplicity, int32_t *se, int32_t *n_se, float *params,
                       int32_t *category, int64_t *tables, int32_t *flags, void *stream);
 
+/* real-valued metric tables and the TensorEvaluator's rows (csrc/metricpairs.hip) ------------------------
+ * The reference's TensorEvaluator.add (src/evaluation/TensorEvaluator.py:70-91) on the device: a per-row LOSS binned by
+ * each of P parameters and by every pair of them, and summed per PMT.  Additions only: WFS_ABI_VERSION stays.
+ *
+ * wfs_metric_pairs_accumulate_real (one launch on `stream`, no read-back): as wfs_metric_pairs_accumulate, for a result
+ * that is a real number.
+ *   result      float [M]; its fixed-point image is v = round(result * 2^32).  A result without an image (not finite, or
+ *               |result| >= 2^15): flag 8, element left out
+ *   params, category, n_dev, lo, hi, nbins, bins   as wfs_metric_pairs_accumulate
+ *   tables      int64 [wfs_metric_pairs_real_table_ints], persistent, in this order: for each metric i FIVE tables
+ *               [n_classes, nbins[i] + 2]: the count n, S = sum v, and Q0, Q1, Q2 with sum v^2 = Q0 + Q1 2^32 + Q2 2^64
+ *               (the sums of the three 32-bit pieces of every v^2 < 2^94: each fits an int64 for 2^31 elements per
+ *               cell); then for each pair i < j in the order 0_1, 0_2, .., 1_2, .. a count table
+ *               [n_classes, nbins[i] + 2, nbins[j] + 2], then its S table.  Integer atomics only: exact, independent of
+ *               the order of the elements and of the launch shape, N ranks combine them with one integer SUM.  The host
+ *               forms mean = S / (n 2^32) and M2 = (n Q - S^2) / (n 2^64) from the integers.
+ *   flags       int32 [1], STICKY bits: 4 category outside [-1, n_classes), 8 result without a fixed-point image,
+ *               16 a cell's S left int64
+ * wfs_tensor_rows (one launch, one thread per row):
+ *   c           detector numbers [N] (c_cols = 1) or (x, y, side) rows [N, 3] (c_cols = 3); int32, or int64 with c_int64
+ *   target      [N, P] of target_dtype (WFS_F32 / WFS_BF16 / WFS_F16, or WFS_TENSOR_TARGET_I64 for class indices);
+ *               1 <= P <= WFS_METRIC_PAIRS_MAX, P = 1 for a target [N]
+ *   results     float [N], the per-row loss; n_dev as everywhere, rows beyond it are never read
+ *   outputs     params float [P, N] (the transposed target), category int32 [N]: 0, or -1 beyond the valid rows (whose
+ *               params are 0)
+ *   det_tables  int64 [2 * nx * ny * 2], persistent: the count table [nx, ny, 2], then the table of sum v.  A detector
+ *               number decodes as the reference compares it, det == 2 * (14 * y + x) + side (nx <= 14); a row whose PMT
+ *               lies outside the grid is left out of these tables only.
+ *   flags       int32 [1], STICKY bits 8 and 16 as above (such a row is left out of det_tables) */
+#define WFS_TENSOR_TARGET_I64 3
+size_t wfs_metric_pairs_real_table_ints(int32_t P, const int32_t *nbins, int32_t n_classes);
+int wfs_metric_pairs_accumulate_real(const float *params, const float *result, const int32_t *category, int64_t M,
+                                     const int64_t *n_dev, int32_t P, const double *lo, const double *hi,
+                                     const int32_t *nbins, int32_t n_classes, int64_t *tables, int32_t *flags,
+                                     void *stream);
+int wfs_tensor_rows(const void *c, int32_t c_int64, int32_t c_cols, const void *target, int32_t target_dtype, int32_t P,
+                    const float *results, int64_t N, const int64_t *n_dev, int32_t nx, int32_t ny, float *params,
+                    int32_t *category, int64_t *det_tables, int32_t *flags, void *stream);
+
 /* opt-in per-kernel timing (HIP events on the launch stream), used by bench.py's roofline ---- */
 #define WFS_TIMER_GATHER_CONV 0
 #define WFS_TIMER_GATHER_DW 1

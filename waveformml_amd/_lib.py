@@ -11,6 +11,7 @@ LIB_PATH = os.environ.get("WFS_LIB") or os.path.join(_HERE, "lib", "libwfsparse.
 
 WFS_OK, WFS_EINVAL, WFS_EOVERFLOW, WFS_EHIP, WFS_EWORKSPACE = 0, 1, 2, 3, 4
 WFS_F32, WFS_BF16, WFS_F16 = 0, 1, 2
+WFS_TENSOR_TARGET_I64 = 3   # wfs_tensor_rows: a target of int64 class indices
 WFS_MAX_DIM = 4
 WFS_RNN_RELU, WFS_RNN_TANH = 0, 1
 WFS_ABI_VERSION = 6         # include/wfsparse.h: this binding's struct layouts and signatures
@@ -178,6 +179,11 @@ SIGNATURES = {
     "wfs_pid_table_ints": (_sz, [_i32, _i32]),
     "wfs_pid_row_stats": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i64, _vp, _i32, _vp, _i32, _i32, _i32, _i32,
                                          _i32, _i32, _i32, _dbl] + [_vp] * 10),
+    "wfs_metric_pairs_real_table_ints": (_sz, [_i32, c_i32p, _i32]),
+    "wfs_metric_pairs_accumulate_real": (ctypes.c_int, [_vp, _vp, _vp, _i64, _vp, _i32, ctypes.POINTER(_dbl),
+                                                        ctypes.POINTER(_dbl), c_i32p, _i32, _vp, _vp, _vp]),
+    "wfs_tensor_rows": (ctypes.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _vp, _i64, _vp, _i32, _i32, _vp, _vp, _vp, _vp,
+                                       _vp]),
     "wfs_timing_enable": (ctypes.c_int, [_i32]),
     "wfs_timing_read": (ctypes.c_int, [_i32, ctypes.POINTER(ctypes.c_double), c_i64p]),
 }

@@ -1,4 +1,5 @@
-// metricpairs.hip -- the reference's MetricPairAggregator and the per-row half of its PIDEvaluator on the device.
+// metricpairs.hip -- the reference's MetricPairAggregator and the per-row half of its PIDEvaluator on the device; in the
+// second half of the file the same for a real-valued result, with the per-row half of its TensorEvaluator.
 //
 // MetricPairAggregator.add / add_normalized (src/evaluation/MetricAggregator.py:339-366) bins a 0/1 result of every
 // element by each of P parameters (metric_accumulate_1d) and by every pair i < j (metric_accumulate_2d), per class.  Both
@@ -41,6 +42,7 @@ struct PairPlan {
     int nb[MP_MAX];
     double lo[MP_MAX], hi[MP_MAX];
     long long off1[MP_MAX];                   // metric i: count table, then the match-sum table C * (nb[i] + 2) further
+                                              // (k_metric_pairs_real: count, S and the three limbs of Q)
     long long off2[MP_MAX];                   // first pair of row i (i_i+1); the pairs i_j follow in j
     int img[MP_MAX];                          // metric i's offset in the LDS image
 };
@@ -208,7 +210,9 @@ k_pid_rows(const int *__restrict__ coords, const long long *__restrict__ pred, c
     for (int k = 0; k < 4; ++k) params[(long long)k * n_cap + r] = o_par[k];
 }
 
-bool make_plan(int P, const int32_t *nbins, const double *lo, const double *hi, int C, PairPlan *pl, size_t *total) {
+// k1: int64 tables per metric (2: count + match sum; the real-valued accumulate keeps MPR_TABS)
+bool make_plan(int P, const int32_t *nbins, const double *lo, const double *hi, int C, PairPlan *pl, size_t *total,
+               int k1 = 2) {
     if (P < 1 || P > MP_MAX || C < 1 || !nbins) return false;
     pl->P = P, pl->C = C;
     size_t at = 0;
@@ -221,7 +225,7 @@ bool make_plan(int P, const int32_t *nbins, const double *lo, const double *hi, 
         pl->hi[i] = hi ? hi[i] : 1.0;
         pl->off1[i] = (long long)at;
         pl->img[i] = img;
-        at += 2 * (size_t)C * ((size_t)nbins[i] + 2);
+        at += (size_t)k1 * (size_t)C * ((size_t)nbins[i] + 2);
         if ((size_t)img + (size_t)C * ((size_t)nbins[i] + 2) > (size_t)1 << 30) return false;
         img += C * (nbins[i] + 2);
     }
@@ -320,6 +324,268 @@ extern "C" int wfs_pid_row_stats(const int32_t *coords, const int64_t *predictio
     else
         WFS_PIDROWS(wfs_f16);
 #undef WFS_PIDROWS
+    WFS_LAUNCH_CHECK();
+    return WFS_OK;
+}
+
+// ---- real-valued results: the reference's TensorEvaluator (src/evaluation/TensorEvaluator.py:70-91) -------------------
+//
+// A result that is a loss value, not 0/1: the mean and M2 of metric_accumulate_1d no longer follow from two counts.  Per
+// 1-D cell the tables keep n, S = sum v and Q = sum v^2 of the fixed-point image v = round(r * 2^32) of the result, Q as
+// three int64 limbs holding the 32-bit pieces of v^2 (|r| < 2^15, so v^2 < 2^94 and every limb sum fits an int64 for up
+// to 2^31 elements per cell); per pair cell n and S.  Integer atomics only, so the tables do not depend on the order of
+// the rows or on the launch shape; the host forms mean = S / (n 2^32) and M2 = (n Q - S^2) / (n 2^64) from integers.
+//
+//   k_tensor_rows          one thread per row of a LitWaveform batch: the [P, N] parameter matrix (the transposed target,
+//                          or the single target), the category (0, or -1 beyond the valid rows) and the per-PMT count /
+//                          loss-sum tables of TensorEvaluator.add's loop over (x, y, side).
+//   k_metric_pairs_real    k_metric_pairs's shape and bin_direct; the 1-D cells through an int64 image in LDS where they
+//                          fit (MPR_LDS_CELLS), by direct global atomics above that; the pair cells direct.
+namespace {
+
+constexpr int MPR_TABS = 5;                   // per 1-D cell: n, S, and the limbs Q0, Q1, Q2
+constexpr int MPR_LDS_CELLS = 1024;           // cells of the 1-D image (5 x 8 KB of int64)
+#ifndef MPR_SLICE_ROWS
+#define MPR_SLICE_ROWS 1                      // elements per thread and workgroup pass
+#endif
+#ifndef MPR_BINS_LDS
+#define MPR_BINS_LDS 1                        // 0: timing variant, the element's bin indices in a private array
+#endif
+constexpr int MPR_SLICE = MPR_SLICE_ROWS * MB;
+constexpr int TENSOR_DET_ROW = 14;            // det == 2 * (14 * j + i) + k
+constexpr double FIX_ONE = 4294967296.0;      // 2^32
+
+// the fixed-point image of a result; false (flag 8) for a result that has none: not finite, or |r| >= 2^15
+__device__ __forceinline__ bool real_image(float r, long long *v, int *flags) {
+    if (!(fabsf(r) < 32768.f)) {              // also catches NaN
+        atomicOr(flags, 8);
+        return false;
+    }
+    *v = __double2ll_rn(__dmul_rn((double)r, FIX_ONE));
+    return true;
+}
+// a cell's S: flag 16 when the sum leaves int64
+__device__ __forceinline__ void add_fixed(long long *p, long long v, int *flags) {
+    const long long old = (long long)atomicAdd(reinterpret_cast<unsigned long long *>(p), (unsigned long long)v);
+    const long long now = (long long)((unsigned long long)old + (unsigned long long)v);
+    if (((old ^ now) & (v ^ now)) < 0) atomicOr(flags, 16);
+}
+
+template <bool LDS1D>
+__global__ void __launch_bounds__(MB)
+k_metric_pairs_real(const float *__restrict__ params, const float *__restrict__ result,
+                    const int *__restrict__ category, long long M, const long long *__restrict__ n_dev, PairPlan pl,
+                    long long *__restrict__ tab, int *__restrict__ flags) {
+    extern __shared__ long long image64[];    // [MPR_TABS][cells1]
+#if MPR_BINS_LDS
+    // the element's bin indices: the loops over metrics are not unrolled, and a private array indexed by them would live
+    // in scratch memory
+    __shared__ int bins[MP_MAX][MB];
+#endif
+    const long long nv = valid_rows(M, n_dev);
+    const int P = pl.P, C = pl.C, cells1 = pl.cells1;
+    for (long long base = (long long)blockIdx.x * MPR_SLICE; base < nv; base += (long long)gridDim.x * MPR_SLICE) {
+        if (LDS1D) {
+            for (int k = threadIdx.x; k < MPR_TABS * cells1; k += MB) image64[k] = 0;
+            __syncthreads();
+        }
+        for (int s = 0; s < MPR_SLICE / MB; ++s) {
+            const long long m = base + s * MB + threadIdx.x;
+            if (m >= nv) break;
+            const int cat = category[m];
+            if (cat == -1) continue;
+            if (cat < -1 || cat >= C) {
+                atomicOr(flags, 4);           // a class outside class_names
+                continue;
+            }
+            long long v;
+            if (!real_image(result[m], &v, flags)) continue;
+            // v^2 < 2^94 in 32-bit pieces
+            const unsigned long long a = (unsigned long long)(v < 0 ? -v : v);
+            const unsigned long long lo = a * a;
+            const long long q[3] = {(long long)(lo & 0xffffffffull), (long long)(lo >> 32), (long long)__umul64hi(a, a)};
+#if MPR_BINS_LDS
+            for (int i = 0; i < P; ++i)
+                bins[i][threadIdx.x] = bin_direct((double)params[(long long)i * M + m], pl.lo[i], pl.hi[i], pl.nb[i]);
+#define MPR_BIN(i) bins[i][threadIdx.x]
+#else
+            int b[MP_MAX];
+#pragma unroll
+            for (int i = 0; i < MP_MAX; ++i)
+                b[i] = i < P ? bin_direct((double)params[(long long)i * M + m], pl.lo[i], pl.hi[i], pl.nb[i]) : 0;
+#define MPR_BIN(i) b[i]
+#endif
+            for (int i = 0; i < P; ++i) {
+                const int ni = pl.nb[i] + 2, bi = MPR_BIN(i);
+                if (LDS1D) {
+                    unsigned long long *c = reinterpret_cast<unsigned long long *>(image64) + pl.img[i] + cat * ni + bi;
+                    atomicAdd(c, 1ull);
+                    if (v != 0) {             // a slice's S stays below 2^10 * 2^47
+                        atomicAdd(c + cells1, (unsigned long long)v);
+#pragma unroll
+                        for (int k = 0; k < 3; ++k)
+                            if (q[k] != 0) atomicAdd(c + (2 + k) * cells1, (unsigned long long)q[k]);
+                    }
+                } else {
+                    const long long sz = (long long)C * ni;
+                    long long *t = tab + pl.off1[i] + (long long)cat * ni + bi;
+                    add64(t, 1);
+                    if (v != 0) {
+                        add_fixed(t + sz, v, flags);
+#pragma unroll
+                        for (int k = 0; k < 3; ++k)
+                            if (q[k] != 0) add64(t + (2 + k) * sz, q[k]);
+                    }
+                }
+                long long *t2 = tab + pl.off2[i];
+                for (int j = i + 1; j < P; ++j) {
+                    const int nj = pl.nb[j] + 2;
+                    const long long cells = (long long)C * ni * nj;
+                    long long *t = t2 + ((long long)cat * ni + bi) * nj + MPR_BIN(j);
+                    add64(t, 1);
+                    if (v != 0) add_fixed(t + cells, v, flags);
+                    t2 += 2 * cells;
+                }
+            }
+#undef MPR_BIN
+        }
+        if (LDS1D) {
+            __syncthreads();
+            // the image's cells in table order: metric i's n cells, then its S cells, then the limbs
+            for (int k = threadIdx.x; k < MPR_TABS * cells1; k += MB) {
+                const long long v = image64[k];
+                if (v == 0) continue;
+                const int which = k / cells1, cell = k - which * cells1;
+                int i = 0;
+                while (i + 1 < P && pl.img[i + 1] <= cell) ++i;
+                const long long sz = (long long)C * (pl.nb[i] + 2);
+                long long *t = tab + pl.off1[i] + which * sz + (cell - pl.img[i]);
+                if (which == 1)
+                    add_fixed(t, v, flags);
+                else
+                    add64(t, v);
+            }
+            __syncthreads();
+        }
+    }
+}
+
+template <typename T>
+__device__ __forceinline__ float target_f32(const T *p) {
+    return wfs_ld(p);
+}
+template <>
+__device__ __forceinline__ float target_f32<long long>(const long long *p) {
+    return (float)*p;                         // a class index
+}
+
+// CT: int or long long coordinates; T: the target's element type
+template <typename CT, typename T>
+__global__ void __launch_bounds__(MB)
+k_tensor_rows(const CT *__restrict__ c, int c_cols, const T *__restrict__ target, int P,
+              const float *__restrict__ results, long long N, const long long *__restrict__ n_dev, int nx, int ny,
+              float *__restrict__ params, int *__restrict__ category, long long *__restrict__ det,
+              int *__restrict__ flags) {
+    const long long nv = valid_rows(N, n_dev);
+    const long long r = (long long)blockIdx.x * MB + threadIdx.x;
+    if (r >= N) return;
+    if (r >= nv) {                            // beyond the valid count: defined outputs, category -1, nothing read
+        category[r] = -1;
+        for (int k = 0; k < P; ++k) params[(long long)k * N + r] = 0.f;
+        return;
+    }
+    for (int k = 0; k < P; ++k) params[(long long)k * N + r] = target_f32(target + r * P + k);
+    category[r] = 0;
+    long long x, y, side;
+    if (c_cols == 1) {
+        const long long d = (long long)c[r];
+        if (d < 0) return;                    // no (i, j, k) gives a negative number
+        side = d & 1;
+        x = (d >> 1) % TENSOR_DET_ROW;
+        y = (d >> 1) / TENSOR_DET_ROW;
+    } else {
+        x = (long long)c[r * 3], y = (long long)c[r * 3 + 1], side = (long long)c[r * 3 + 2];
+    }
+    // a PMT outside the grid: the reference's loop over (i, j, k) never selects the row
+    if (x < 0 || x >= nx || y < 0 || y >= ny || side < 0 || side > 1) return;
+    long long v;
+    if (!real_image(results[r], &v, flags)) return;
+    const long long cells = (long long)nx * ny * 2, cell = (x * ny + y) * 2 + side;
+    add64(det + cell, 1);
+    if (v != 0) add_fixed(det + cells + cell, v, flags);
+}
+
+}  // namespace
+
+extern "C" size_t wfs_metric_pairs_real_table_ints(int32_t P, const int32_t *nbins, int32_t n_classes) {
+    PairPlan pl;
+    size_t total = 0;
+    return make_plan(P, nbins, nullptr, nullptr, n_classes, &pl, &total, MPR_TABS) ? total : 0;
+}
+
+extern "C" int wfs_metric_pairs_accumulate_real(const float *params, const float *result, const int32_t *category,
+                                                int64_t M, const int64_t *n_dev, int32_t P, const double *lo,
+                                                const double *hi, const int32_t *nbins, int32_t n_classes,
+                                                int64_t *tables, int32_t *flags, void *stream) {
+    PairPlan pl;
+    size_t total = 0;
+    WFS_REQUIRE(lo && hi && make_plan(P, nbins, lo, hi, n_classes, &pl, &total, MPR_TABS), WFS_EINVAL,
+                "wfs_metric_pairs_accumulate_real: P = %d (1 .. %d), classes = %d, or a bad bin count / range (high > low)",
+                P, MP_MAX, n_classes);
+    WFS_REQUIRE(M >= 0 && M < (1ll << 31), WFS_EINVAL, "wfs_metric_pairs_accumulate_real: M = %lld", (long long)M);
+    WFS_REQUIRE(tables && flags && (M == 0 || (params && result && category)), WFS_EINVAL,
+                "wfs_metric_pairs_accumulate_real: NULL argument");
+    if (M == 0) return WFS_OK;
+    long long blocks = wfs_cdiv(M, MPR_SLICE);
+    if (blocks > 1024) blocks = 1024;
+    hipStream_t s = (hipStream_t)stream;
+    if (MP_LDS_1D && pl.cells1 <= MPR_LDS_CELLS)
+        k_metric_pairs_real<true><<<(unsigned)blocks, MB, (size_t)MPR_TABS * pl.cells1 * sizeof(long long), s>>>(
+            params, result, category, M, (const long long *)n_dev, pl, (long long *)tables, flags);
+    else
+        k_metric_pairs_real<false><<<(unsigned)blocks, MB, 0, s>>>(params, result, category, M, (const long long *)n_dev,
+                                                                   pl, (long long *)tables, flags);
+    WFS_LAUNCH_CHECK();
+    return WFS_OK;
+}
+
+extern "C" int wfs_tensor_rows(const void *c, int32_t c_int64, int32_t c_cols, const void *target,
+                               int32_t target_dtype, int32_t P, const float *results, int64_t N, const int64_t *n_dev,
+                               int32_t nx, int32_t ny, float *params, int32_t *category, int64_t *det_tables,
+                               int32_t *flags, void *stream) {
+    WFS_REQUIRE(wfs_dtype_ok(target_dtype) || target_dtype == WFS_TENSOR_TARGET_I64, WFS_EINVAL,
+                "wfs_tensor_rows: unknown target dtype %d", target_dtype);
+    WFS_REQUIRE((c_cols == 1 || c_cols == 3) && (c_int64 == 0 || c_int64 == 1), WFS_EINVAL,
+                "wfs_tensor_rows: c must be detector numbers [N] or (x, y, side) rows [N, 3] of int32 / int64");
+    WFS_REQUIRE(P >= 1 && P <= MP_MAX && N >= 0 && N < (1ll << 31) && nx >= 1 && nx <= TENSOR_DET_ROW && ny >= 1 &&
+                    ny <= (1 << 15),
+                WFS_EINVAL, "wfs_tensor_rows: P = %d (1 .. %d), N = %lld, grid %d x %d", P, MP_MAX, (long long)N, nx, ny);
+    WFS_REQUIRE(det_tables && flags && (N == 0 || (c && target && results && params && category)), WFS_EINVAL,
+                "wfs_tensor_rows: NULL argument");
+    if (N == 0) return WFS_OK;
+    const unsigned rb = (unsigned)wfs_cdiv(N, MB);
+    hipStream_t s = (hipStream_t)stream;
+#define WFS_TROWS(CT, TYPE)                                                                                            \
+    k_tensor_rows<CT, TYPE><<<rb, MB, 0, s>>>((const CT *)c, c_cols, (const TYPE *)target, P, results, N,              \
+                                              (const long long *)n_dev, nx, ny, params, category,                     \
+                                              (long long *)det_tables, flags)
+#define WFS_TROWS_C(TYPE)                                                                                              \
+    do {                                                                                                               \
+        if (c_int64)                                                                                                   \
+            WFS_TROWS(long long, TYPE);                                                                                \
+        else                                                                                                           \
+            WFS_TROWS(int, TYPE);                                                                                      \
+    } while (0)
+    if (target_dtype == WFS_F32)
+        WFS_TROWS_C(float);
+    else if (target_dtype == WFS_BF16)
+        WFS_TROWS_C(wfs_bf16);
+    else if (target_dtype == WFS_F16)
+        WFS_TROWS_C(wfs_f16);
+    else
+        WFS_TROWS_C(long long);
+#undef WFS_TROWS_C
+#undef WFS_TROWS
     WFS_LAUNCH_CHECK();
     return WFS_OK;
 }

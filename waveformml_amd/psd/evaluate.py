@@ -4,7 +4,8 @@
                      (Evaluate.py:69-84): eval mode, no gradients, ``LitPSD.test_step`` per batch (which zeroes feature
                      column ``occlude_index`` when it is set, src/engineering/LitPSD.py:130-151), event-weighted means.
 ``segment_test_loop`` the same for the per-segment regression modules (psd/litz.LitZ, LitEZ): ``test_step`` per batch,
-                     row-weighted mean losses, the batch's dense maps handed to a psd/segment_evaluator evaluator.
+                     row-weighted mean losses, the batch's dense maps handed to a psd/segment_evaluator evaluator.  Also
+                     the loop of LitSegClassifier (PIDEvaluator) and of LitWaveform (TensorEvaluator).
 ``occlusion_sweep``  the reference's occlusion study (scripts/RunOcclusionStudy.py) runs Evaluate.py once per feature
                      index, i.e. re-reads the data and rebuilds every rulebook for each index although the geometry of a
                      batch never changes.  Here ONE batch already in HBM is run through the net for a list of indices
@@ -86,7 +87,10 @@ def segment_test_loop(module, loader, device, feature_dtype=None, evaluator=None
     over batches weighted by the batch's rows (the segment losses are per-row means, src/engineering/LitBase.py:171).
     ``evaluator``: a psd/segment_evaluator ZEvaluator / EZEvaluator; every batch's (predictions, dense targets,
     coordinates, features) go to its ``add`` as in the reference's ``test_step`` (LitZ.py:134-141, LitEZ.py:86-89) -- on the
-    stream the forward ran on, without a read-back -- and the returned dict gains ``"evaluation": evaluator.results()``."""
+    stream the forward ran on, without a read-back -- and the returned dict gains ``"evaluation": evaluator.results()``.
+    The loop only needs ``module.last_test_outputs`` to hold ``evaluator.add``'s arguments, so it serves
+    psd/litseg.LitSegClassifier (PIDEvaluator) and psd/litwaveform.LitWaveform (psd/tensor_evaluator.TensorEvaluator:
+    ``(c, f, target, per-row loss)``) as it stands."""
     module.to(device)
     module.eval()
     sums, n = {}, 0

@@ -16,14 +16,18 @@ and receive a zero gradient whatever the criterion (``ignore_index`` covers Cros
 other net as [N, 1, n_samples].  A net that declares ``takes_n_valid`` (ConvWaveformNet: BatchNorm statistics) is handed
 the batch's valid-row count -- a device tensor in a captured step, else None -- in its ``n_valid`` attribute for the call.
 
-Out of scope: TensorEvaluator (and the evaluator plumbing of test_step) and ``write_script`` / TorchScript export.
+``evaluator`` is the reference's ``TensorEvaluator`` on the GPU (psd/tensor_evaluator.py); ``test_step`` keeps what its
+``add`` takes in ``last_test_outputs``, so ``evaluate.segment_test_loop(module, loader, device,
+evaluator=module.evaluator)`` fills the per-PMT and the binned loss tables without a read-back per batch.
+
+Out of scope: ``write_script`` / TorchScript export.
 """
 import logging
 
 import torch
 from torch import nn
 
-from .config import ModuleUtility
+from .config import DictionaryUtility, ModuleUtility
 from .lit import LitPSD
 
 
@@ -83,6 +87,25 @@ class LitWaveform(nn.Module):
         self.loss_no_reduce = self.criterion_class(*nc.criterion_params, reduction="none")
         if self.use_accuracy:
             self.softmax = nn.Softmax(dim=1)
+        self.last_test_outputs = None     # test_step's (c, f, target, results), for segment_test_loop
+        self._evaluator = None
+
+    @property
+    def evaluator(self):
+        """The ``TensorEvaluator`` the reference builds in ``__init__`` (LitWaveform.py:39-63), built on first use on the
+        device the model lives on (it raises on the CPU): ``calgroup`` from ``dataset_config``, ``target_has_phys``,
+        ``target_index`` and ``metric_name`` as the constructor derives them, then ``config.evaluation_config`` as
+        keyword arguments.  Nothing calls it implicitly: hand it to ``evaluate.segment_test_loop``."""
+        if self._evaluator is None:
+            from .tensor_evaluator import TensorEvaluator
+            params = {}
+            if hasattr(self.config, "evaluation_config"):
+                params = DictionaryUtility.to_dict(self.config.evaluation_config)
+            self._evaluator = TensorEvaluator(next(self.model.parameters()).device,
+                                              calgroup=getattr(self.config.dataset_config, "calgroup", None),
+                                              target_has_phys=self.test_has_phys, target_index=self.target_index,
+                                              metric_name=self.metric_name, **params)
+        return self._evaluator
 
     configure_optimizers = LitPSD.configure_optimizers
     log = LitPSD.log
@@ -168,10 +191,10 @@ class LitWaveform(nn.Module):
         if self.occlude_index:                       # falsy for index 0, exactly as the reference
             f[:, self.occlude_index] = 0
         predictions = self._predict(f, target, phys=self.test_has_phys)
-        if self.test_has_phys:
-            loss = self.criterion.forward(predictions, target[:, self.target_index])
-        else:
-            loss = self.criterion.forward(predictions, target)
+        scored = target[:, self.target_index] if self.test_has_phys else target
+        loss = self.criterion.forward(predictions, scored)
+        # what the reference hands its evaluator (LitWaveform.py:139-146)
+        self.last_test_outputs = (c, f, target, self.loss_no_reduce(predictions, scored).detach())
         results = {"test_loss": loss}
         if self.use_accuracy:
             pred = torch.argmax(self.softmax(predictions), dim=1)

@@ -6,9 +6,11 @@ and by every pair of them, per class.
 reference callers feed the aggregator a 0/1 result (``find_matches``, ``calculate_class_accuracy``), so every table is an
 exact int64 count -- a count table and a match-sum table -- bit-identical from run to run, and N ranks combine them with
 one integer SUM.  The running mean / M2 that ``metric_accumulate_1d`` keeps follow from the two counts in closed form
-(``triple_1d``).  Results that are not 0/1 (``WaveformEvaluator``'s deviations) are not supported and are rejected.
+(``triple_1d``).  Results that are not 0/1 are rejected here; ``RealMetricPairTables`` below takes them (a per-element
+loss, the reference's ``TensorEvaluator``).
 """
 import ctypes
+import math
 
 import numpy as np
 import torch
@@ -136,3 +138,107 @@ def split_results(host, layout, names):
         else:
             out["pairs"][key] = (m.astype(np.float64), n)
     return out
+
+
+# ---- real-valued results ---------------------------------------------------------------------------------------------
+REAL_TABS = 5                   # per 1-D cell: n, S, Q0, Q1, Q2 (include/wfsparse.h)
+FIX_BITS = 32                   # the fixed-point image of a result: v = round(result * 2^32)
+REAL_LIMIT = float(1 << 15)     # |result| < 2^15
+REAL_FLAG_TEXT = {4: "a category lay outside class_names",
+                  8: "a result had no fixed-point image (not finite, or |result| >= 2^15)",
+                  16: "the fixed-point sum of a cell left int64"}
+
+
+def real_triple_1d(n, S, Q0, Q1, Q2):
+    """(mean, n, dev) of ``metric_accumulate_1d``'s Welford update after ``finalize2d``, from the integer tables of the
+    real-valued accumulate: mean = S / (n 2^32), M2 = (n Q - S^2) / (n 2^64) with Q = Q0 + Q1 2^32 + Q2 2^64, dev =
+    sqrt(M2 / (n - 1)) when n > 2, else 0.  Python integers: n Q - S^2 is exact, so a loss that is nearly constant within
+    a bin keeps its spread; every quotient is rounded once."""
+    mean, dev = np.zeros(n.shape, np.float64), np.zeros(n.shape, np.float64)
+    for idx in zip(*np.nonzero(n)):
+        k, s = int(n[idx]), int(S[idx])
+        mean[idx] = s / (k << FIX_BITS)
+        if k > 2:
+            q = int(Q0[idx]) + (int(Q1[idx]) << 32) + (int(Q2[idx]) << 64)
+            dev[idx] = math.sqrt((k * q - s * s) / ((k * (k - 1)) << (2 * FIX_BITS)))
+    return mean, n.copy(), dev
+
+
+def real_table_layout(n_bins, n_classes):
+    """(key, shape, tables) of every group of tables in the order of include/wfsparse.h: five per metric, two per pair."""
+    return [(key, shape, REAL_TABS if isinstance(key, int) else 2) for key, shape in table_layout(n_bins, n_classes)]
+
+
+def split_real_results(host, layout, names):
+    out, at = {"metrics": {}, "pairs": {}}, 0
+    for key, shape, tabs in layout:
+        size = int(np.prod(shape))
+        t = [host[at + k * size:at + (k + 1) * size].reshape(shape) for k in range(tabs)]
+        at += tabs * size
+        if isinstance(key, int):
+            out["metrics"][names[key]] = real_triple_1d(*t)
+        else:
+            out["pairs"][key] = (t[1].astype(np.float64) / float(1 << FIX_BITS), t[0].copy())
+    return out
+
+
+class RealMetricPairTables(MetricPairTables):
+    """``MetricPairTables`` for a result that is a real number (a per-element loss): ``MetricPairAggregator`` as the
+    reference's ``TensorEvaluator`` feeds it.  Per 1-D cell the count, S = sum v and Q = sum v^2 of the fixed-point images
+    v = round(result * 2^32), per pair cell the count and S -- all int64, changed by integer atomics only, so the tables
+    are independent of the order of the elements, bit-identical from run to run, and N ranks combine them with one
+    integer SUM.  The ranges, ``reset()`` and ``state_tensors()`` are the base class's."""
+
+    def __init__(self, device, metrics, class_names):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("waveformml_amd: RealMetricPairTables runs on the GPU (there is no CPU path); got %s"
+                               % self.device)
+        self.class_names = list(class_names)
+        self.n_classes = len(self.class_names)
+        self.names = [str(m[0]) for m in metrics]
+        self.n_bins = [int(m[3]) for m in metrics]
+        self.P = len(self.names)
+        if not 1 <= self.P <= MAX_METRICS or self.n_classes < 1 or min(self.n_bins) < 1:
+            raise ValueError("RealMetricPairTables: 1 to %d metrics with at least one bin each and at least one class"
+                             % MAX_METRICS)
+        self.ranges = [bin_edge_range(float(m[1]), float(m[2]), int(m[3])) for m in metrics]
+        self._nb = _lib.i32_array(self.n_bins)
+        self._layout = real_table_layout(self.n_bins, self.n_classes)
+        n = int(_lib.load().wfs_metric_pairs_real_table_ints(self.P, self._nb, self.n_classes))
+        assert n == sum(tabs * int(np.prod(s)) for _k, s, tabs in self._layout)
+        self.tables = torch.zeros(n, dtype=torch.int64, device=self.device)
+        self.flags = torch.zeros(1, dtype=torch.int32, device=self.device)
+
+    def add(self, params, result, category, n_valid=None, ranges=None):
+        """``params`` float32 [P, M]; ``result`` float32 [M]; ``category``, ``n_valid`` and ``ranges`` as in
+        ``MetricPairTables.add``.  One launch on the current stream; no read-back."""
+        M = int(result.shape[0])
+        if params.dtype != torch.float32 or tuple(params.shape) != (self.P, M):
+            raise RuntimeError("RealMetricPairTables.add: params must be float32 [%d, %d], got %s %s"
+                               % (self.P, M, params.dtype, tuple(params.shape)))
+        if result.dtype != torch.float32 or result.dim() != 1 or category.dtype != torch.int32 or \
+                tuple(category.shape) != (M,):
+            raise RuntimeError("RealMetricPairTables.add: result must be float32 [%d] and category int32 [%d]" % (M, M))
+        if n_valid is not None and (n_valid.dtype != torch.int64 or not n_valid.is_cuda):
+            raise RuntimeError("RealMetricPairTables.add: n_valid must be a device int64")
+        ranges = self.ranges if ranges is None else ranges
+        if len(ranges) != self.P:
+            raise ValueError("RealMetricPairTables.add: one (low, high) per metric")
+        lo = (ctypes.c_double * self.P)(*[float(r[0]) for r in ranges])
+        hi = (ctypes.c_double * self.P)(*[float(r[1]) for r in ranges])
+        p = _lib.ptr
+        _lib.check(_lib.load().wfs_metric_pairs_accumulate_real(
+            p(params), p(result), p(category), M, p(n_valid), self.P, lo, hi, self._nb, self.n_classes, p(self.tables),
+            p(self.flags), _lib.stream_ptr()))
+
+    def _check_flags(self):
+        f = int(self.flags.item())
+        if f:
+            raise RuntimeError("RealMetricPairTables: " + "; ".join(t for b, t in REAL_FLAG_TEXT.items() if f & b))
+
+    def results(self):
+        """One read-back: ``{"metrics": {name: (mean, n, dev)}, "pairs": {"i_j": (sum of results, n)}}`` with the
+        reference's shapes [C, nb + 2] and [C, nb_i + 2, nb_j + 2]."""
+        self._check_flags()
+        return split_real_results(self.tables.cpu().numpy(), self._layout, self.names)
