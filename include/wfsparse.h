@@ -948,6 +948,65 @@ int wfs_tensor_rows(const void *c, int32_t c_int64, int32_t c_cols, const void *
                     const float *results, int64_t N, const int64_t *n_dev, int32_t nx, int32_t ny, float *params,
                     int32_t *category, int64_t *det_tables, int32_t *flags, void *stream);
 
+/* the per-segment regression module: masked loss and the SegEvaluator's rows (csrc/segquant.hip) -----------
+ * Additions only: WFS_ABI_VERSION stays.
+ *
+ * wfs_masked_regression_loss (ONE launch on `stream`): the mean of |d| (WFS_LOSS_L1) or d^2 (WFS_LOSS_MSE),
+ * d = pred - target[:, col], over the COUNTED rows: those below the valid count and, with a mask, on a segment whose mask
+ * entry is 1.0.  A row that is not counted is selected out: nothing in it (NaN, Inf, padding) reaches a result.
+ *   pred        [n_cap] of pred_dtype; target [n_cap, n_cols] of target_dtype (n_cols = 1, col = 0 for a target [n_cap])
+ *   coords      int32 [n_cap, 3] = (x, y, event), read only with a mask; se_mask float [nx, ny] or NULL
+ *   n_dev       as everywhere; max_blocks 0 = the default grid (the result does not depend on it)
+ *   workspace   wfs_masked_regression_loss_workspace_bytes(n_cap) bytes whose first 4 are ZERO before the first use; the
+ *               launch leaves them zero, so a buffer is zeroed once.  One launch at a time per workspace.
+ *   out         float [2]: the loss and the mean of d^2 over the same rows; count int64 [1].  d and all sums are fp64,
+ *               chunk sums are folded in a fixed order, no floating-point atomics: bit-identical from run to run and
+ *               independent of the grid.  No row counted: NaN, NaN, 0.
+ * wfs_masked_regression_loss_backward (ONE launch): dpred [n_cap] of pred_dtype = grad[0] * s / count[0] with
+ *   s = sign(d) (sign(0) = 0) for L1, 2 d for MSE; exactly 0 in a row that is not counted, and everywhere when count is 0.
+ *
+ * wfs_error_edges (host only): first_last[0 .. 1] = the first and last entry of the reference's
+ *   get_bins(-1.1 max_abs, 1.1 max_abs, n_bins) = np.arange(low, high + w / 2, w), bit for bit; WFS_EINVAL for a
+ *   max_abs that is 0, negative or not finite.  The device fixes the ErrorAggregator's ranges with the same function.
+ * wfs_segq_row_stats (two launches: event offsets, then one thread per row), SegEvaluator.add's row walks:
+ *   results     [n_cap] of results_dtype; target [n_cap, n_phys] of target_dtype; pid int32 / int64 [n_cap] or NULL
+ *   outputs     per row: mae float = |error|, error double = results - target[:, target_index] in fp64, multiplicity,
+ *               se (seg_status == 0.5), category, slot (int32), params float [4, n_cap] = E, PSD, multiplicity, z.
+ *               With pid: slot = the PID's place in 1 | 4 | 6, 258 | 256 | 512 and category = its class 0 .. 4 on a
+ *               valid single-ended row whose PID is in that list, else both -1.  Without: slot = category = 0 for every
+ *               valid row.  Rows beyond the valid count and flagged rows get zeros and -1.
+ *   slot_scratch int64 [2 * 6], zero before the first use: per slot max |error| (the bits of the double) and the row
+ *               count of this batch; wfs_segq_error_accumulate consumes and clears them.
+ *   flags       int32 [1], STICKY bits: 1 event column unsorted / out of range, 2 segment outside [nx, ny]
+ * wfs_segq_error_accumulate (two launches: one workgroup fixing edges, then one thread per row), ErrorAggregator.add_norm:
+ *   n_classes is 5 with has_pid, 1 without.  edges double [n_classes, 2], edges_set int32 [n_classes], persistent: a class that is not set takes the first slot
+ *   with rows in this batch; error_flags int32 [1], STICKY bit c: class c's first subset had a max |error| of 0 or not
+ *   finite (its edges stay unset and its rows are not binned).  error_hist int64 [n_classes, n_bins + 2] by the class's
+ *   edges, error_2d int64 [n_classes, n_bins + 2, n_bins + 2] by (actual, predicted) over [0, 1]. */
+#define WFS_LOSS_L1 0
+#define WFS_LOSS_MSE 1
+size_t wfs_masked_regression_loss_workspace_bytes(int64_t n_cap);
+int wfs_masked_regression_loss(const void *pred, int32_t pred_dtype, const void *target, int32_t target_dtype,
+                               int32_t n_cols, int32_t col, const int32_t *coords, const float *se_mask, int32_t nx,
+                               int32_t ny, int64_t n_cap, const int64_t *n_dev, int32_t kind, int32_t max_blocks,
+                               void *workspace, size_t workspace_bytes, float *out, int64_t *count, void *stream);
+int wfs_masked_regression_loss_backward(const void *pred, int32_t pred_dtype, const void *target, int32_t target_dtype,
+                                        int32_t n_cols, int32_t col, const int32_t *coords, const float *se_mask,
+                                        int32_t nx, int32_t ny, int64_t n_cap, const int64_t *n_dev, int32_t kind,
+                                        const int64_t *count, const float *grad, void *dpred, void *stream);
+int wfs_error_edges(double max_abs, int32_t n_bins, double *first_last);
+int wfs_segq_row_stats(const int32_t *coords, const void *results, int32_t results_dtype, const void *target,
+                       int32_t target_dtype, int32_t n_phys, const void *pid, int32_t pid_int64, int64_t n_cap,
+                       const int64_t *n_dev, int32_t E, const float *seg_status, int32_t nx, int32_t ny, int32_t e_index,
+                       int32_t psd_index, int32_t z_index, int32_t target_index, int32_t *offsets, float *mae,
+                       double *error, int32_t *multiplicity, int32_t *se, float *params, int32_t *category,
+                       int32_t *slot, int64_t *slot_scratch, int32_t *flags, void *stream);
+int wfs_segq_error_accumulate(const void *results, int32_t results_dtype, const void *target, int32_t target_dtype,
+                              int32_t n_phys, int32_t target_index, const double *error, const int32_t *category,
+                              int64_t n_cap, const int64_t *n_dev, int32_t n_classes, int32_t has_pid, int32_t n_bins,
+                              int64_t *slot_scratch, double *edges, int32_t *edges_set, int32_t *error_flags,
+                              int64_t *error_hist, int64_t *error_2d, void *stream);
+
 /* opt-in per-kernel timing (HIP events on the launch stream), used by bench.py's roofline ---- */
 #define WFS_TIMER_GATHER_CONV 0
 #define WFS_TIMER_GATHER_DW 1

@@ -14,6 +14,7 @@ WFS_F32, WFS_BF16, WFS_F16 = 0, 1, 2
 WFS_TENSOR_TARGET_I64 = 3   # wfs_tensor_rows: a target of int64 class indices
 WFS_MAX_DIM = 4
 WFS_RNN_RELU, WFS_RNN_TANH = 0, 1
+WFS_LOSS_L1, WFS_LOSS_MSE = 0, 1
 WFS_ABI_VERSION = 6         # include/wfsparse.h: this binding's struct layouts and signatures
 TIMER_GATHER_CONV, TIMER_GATHER_DW, TIMER_RULEBOOK, TIMER_CONV_BACKWARD = 0, 1, 2, 3
 
@@ -184,6 +185,16 @@ SIGNATURES = {
                                                         ctypes.POINTER(_dbl), c_i32p, _i32, _vp, _vp, _vp]),
     "wfs_tensor_rows": (ctypes.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _vp, _i64, _vp, _i32, _i32, _vp, _vp, _vp, _vp,
                                        _vp]),
+    "wfs_masked_regression_loss_workspace_bytes": (_sz, [_i64]),
+    "wfs_masked_regression_loss": (ctypes.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i64, _vp, _i32,
+                                                  _i32, _vp, _sz, _vp, _vp, _vp]),
+    "wfs_masked_regression_loss_backward": (ctypes.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i64,
+                                                           _vp, _i32, _vp, _vp, _vp, _vp]),
+    "wfs_error_edges": (ctypes.c_int, [_dbl, _i32, ctypes.POINTER(_dbl)]),
+    "wfs_segq_row_stats": (ctypes.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _vp, _i32, _i64, _vp, _i32, _vp, _i32, _i32,
+                                          _i32, _i32, _i32, _i32] + [_vp] * 11),
+    "wfs_segq_error_accumulate": (ctypes.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _i64, _vp, _i32, _i32, _i32]
+                                  + [_vp] * 7),
     "wfs_timing_enable": (ctypes.c_int, [_i32]),
     "wfs_timing_read": (ctypes.c_int, [_i32, ctypes.POINTER(ctypes.c_double), c_i64p]),
 }

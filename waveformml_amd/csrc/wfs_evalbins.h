@@ -23,6 +23,22 @@ __device__ __forceinline__ int bin_confusion(double v, double low, double high, 
         if (__dadd_rn(__dmul_rn((double)j, w), low) > v) return j - 1;
     return 0;
 }
+// get_bin_index(v, low, high, (high - low) / nb, nb) without the walk (metricpairs.hip, segquant.hip): the candidate
+// floor((v - low) / width) + 1 corrected by the reference's own predicate at the candidate and its neighbours
+__device__ __forceinline__ int bin_direct(double v, double low, double high, int nb) {
+    if (v < low) return 0;
+    if (v >= high) return nb + 1;
+    if (!(v == v)) return 0;                  // NaN: no edge compares above it
+    const double w = (high - low) / nb;
+    double c = floor((v - low) / w) + 1.0;
+    c = c < 1.0 ? 1.0 : (c > (double)nb ? (double)nb : c);
+    int k = (int)c;
+    // edges are non-decreasing in j, so "j * w + low > v" is false up to some j and true from there on
+    while (k > 1 && __dadd_rn(__dmul_rn((double)(k - 1), w), low) > v) --k;
+    while (k <= nb && !(__dadd_rn(__dmul_rn((double)k, w), low) > v)) ++k;
+    return k <= nb ? k : 0;                   // no edge above v: the reference's bin_index stays 0
+}
+
 __device__ __forceinline__ void add64(long long *p, long long v) {
     atomicAdd(reinterpret_cast<unsigned long long *>(p), (unsigned long long)v);
 }

@@ -875,6 +875,117 @@ class CrossEntropyMeanFunction(Function):
         return ctx.dlogits * grad_output, None, None
 
 
+# zero-initialised workspaces of the masked regression loss, one per device and size: the kernel's ticket word must be 0
+# before the first launch and every launch leaves it 0, so a buffer is zeroed once and reused (a captured step bakes its
+# address into the graph; the entry is never freed).  One stream at a time per device, as everything in this module.
+_MRL_WORKSPACE = {}
+
+
+def _mrl_workspace(device, n_cap):
+    nbytes = int(_lib.load().wfs_masked_regression_loss_workspace_bytes(int(n_cap)))
+    key = (device, nbytes)
+    if key not in _MRL_WORKSPACE:
+        _MRL_WORKSPACE[key] = torch.zeros((nbytes + 7) // 8, dtype=torch.int64, device=device)
+    return _MRL_WORKSPACE[key], nbytes
+
+
+def reset_regression_loss_workspaces():
+    """Zero every cached workspace of the masked regression loss (after a failed or abandoned launch)."""
+    for work in _MRL_WORKSPACE.values():
+        work.zero_()
+
+
+class MaskedRegressionLossFunction(Function):
+    """Mean-reduced nn.L1Loss / nn.MSELoss of ``pred`` [N] against ``target`` [N] or column ``col`` of ``target``
+    [N, n_cols] over the rows below ``n_valid`` that lie on a single-ended segment (``se_mask`` [nx, ny] == 1.0 at the
+    row's (x, y)): the reference's ``criterion(predictions[se_inds], target[se_inds, target_index])``
+    (src/engineering/LitSegQuantifier.py) with a static shape.  One HIP launch forward, one backward (csrc/segquant.hip);
+    returns ``(loss, mse)``, fp32 scalars, ``mse`` = the mean of d^2 over the same rows whatever the kind (no gradient).
+    Rows that are not counted are selected out: whatever they hold, the loss stays finite and their gradient is 0.
+
+    Precondition: ONE stream at a time per device.  The forward's workgroups hand over through a ticket word in a
+    workspace that is cached per (device, size), zeroed once and left zero by every completed launch; ``loss``, ``mse``
+    and the count are written by the workgroup that draws the last ticket.  Two forwards of the same size running at
+    once on different streams, or a launch that was cut short, leave the ticket off zero, and the outputs of later
+    calls of that size are then never written (they are ``torch.empty``: a fill would be a second launch).  A process
+    that met a failed launch calls ``reset_regression_loss_workspaces()`` before it goes on."""
+
+    @staticmethod
+    def forward(ctx, pred, target, col, coords, se_mask, n_valid, kind, max_blocks=0):
+        lib = _lib.load()
+        for t in (pred, target):
+            if not t.is_cuda:
+                raise RuntimeError("waveformml_amd: tensor must live on the GPU (there is no CPU path); got %s" % t.device)
+        pred, target = pred.contiguous(), target.contiguous()
+        n_cap = int(pred.shape[0])
+        if pred.dim() != 1 or target.dim() not in (1, 2) or target.shape[0] != n_cap:
+            raise RuntimeError("masked_regression_loss: pred must be [N] and target [N] or [N, n_cols], got %s and %s"
+                               % (tuple(pred.shape), tuple(target.shape)))
+        n_cols = int(target.shape[1]) if target.dim() == 2 else 1
+        col = int(col) if target.dim() == 2 else 0
+        nx = ny = 0
+        if se_mask is not None:
+            if coords is None or coords.dtype != torch.int32 or coords.dim() != 2 or coords.shape[1] != 3 or \
+                    coords.shape[0] != n_cap:
+                raise RuntimeError("masked_regression_loss: a mask needs coords int32 [N, 3] = (x, y, event)")
+            se_mask = se_mask.reshape(se_mask.shape[-2:]).contiguous()
+            if se_mask.dtype != torch.float32:
+                raise RuntimeError("masked_regression_loss: the mask must be float32")
+            nx, ny = int(se_mask.shape[0]), int(se_mask.shape[1])
+            coords = coords.contiguous()
+        else:
+            coords = None
+        if n_valid is not None and (n_valid.dtype != torch.int64 or not n_valid.is_cuda):
+            raise RuntimeError("masked_regression_loss: n_valid must be a device int64")
+        work, nbytes = _mrl_workspace(pred.device, n_cap)
+        out = torch.empty((2,), dtype=torch.float32, device=pred.device)
+        count = torch.empty((1,), dtype=torch.int64, device=pred.device)
+        p = _lib.ptr
+        _lib.check(lib.wfs_masked_regression_loss(
+            p(pred), _lib.dtype_code(pred), p(target), _lib.dtype_code(target), n_cols, col, p(coords), p(se_mask), nx, ny,
+            n_cap, p(n_valid), int(kind), int(max_blocks), p(work), nbytes, p(out), p(count), _lib.stream_ptr()))
+        ctx.save_for_backward(pred, target, coords, se_mask, n_valid, count)
+        ctx.args = (n_cols, col, nx, ny, n_cap, int(kind))
+        loss, mse = out[0], out[1]
+        ctx.mark_non_differentiable(mse)
+        return loss, mse
+
+    @staticmethod
+    def backward(ctx, grad_loss, _grad_mse):
+        pred, target, coords, se_mask, n_valid, count = ctx.saved_tensors
+        n_cols, col, nx, ny, n_cap, kind = ctx.args
+        grad = grad_loss if grad_loss.dtype == torch.float32 else grad_loss.float()
+        dpred = torch.empty_like(pred)
+        p = _lib.ptr
+        _lib.check(_lib.load().wfs_masked_regression_loss_backward(
+            p(pred), _lib.dtype_code(pred), p(target), _lib.dtype_code(target), n_cols, col, p(coords), p(se_mask), nx, ny,
+            n_cap, p(n_valid), kind, p(count), p(grad.contiguous()), p(dpred), _lib.stream_ptr()))
+        return dpred, None, None, None, None, None, None, None
+
+
+def regression_loss_kind(criterion):
+    """WFS_LOSS_L1 / WFS_LOSS_MSE for a mean-reduced nn.L1Loss / nn.MSELoss, else None."""
+    if getattr(criterion, "reduction", None) != "mean":
+        return None
+    if type(criterion) is torch.nn.L1Loss:
+        return _lib.WFS_LOSS_L1
+    if type(criterion) is torch.nn.MSELoss:
+        return _lib.WFS_LOSS_MSE
+    return None
+
+
+def can_fuse_regression_loss(criterion, pred, target):
+    return (regression_loss_kind(criterion) is not None and pred.is_cuda and target.is_cuda and pred.dim() == 1
+            and target.dim() in (1, 2) and target.shape[0] == pred.shape[0]
+            and pred.dtype in (torch.float32, torch.bfloat16, torch.float16)
+            and target.dtype in (torch.float32, torch.bfloat16, torch.float16))
+
+
+def masked_regression_loss(pred, target, kind, col=0, coords=None, se_mask=None, n_valid=None, max_blocks=0):
+    """``(loss, mse)`` of ``MaskedRegressionLossFunction``; ``kind`` from ``regression_loss_kind``."""
+    return MaskedRegressionLossFunction.apply(pred, target, col, coords, se_mask, n_valid, kind, max_blocks)
+
+
 # ``loss.backward()`` makes autograd fill a fresh ones tensor for d loss / d loss (a launch) and the loss node multiply
 # by it (another).  A runner that owns the backward call passes this persistent tensor instead:
 #     torch.autograd.backward(loss, grad_tensors=unit_loss_grad(loss.device))
