@@ -1007,6 +1007,47 @@ int wfs_segq_error_accumulate(const void *results, int32_t results_dtype, const 
                               int64_t *slot_scratch, double *edges, int32_t *edges_set, int32_t *error_flags,
                               int64_t *error_hist, int64_t *error_2d, void *stream);
 
+/* ---- prediction writers (csrc/predwrite.hip; reference src/datasets/PredictionWriter.py swap_values) ----------------
+ * A chunk of a table travels as RAW compound records uint8 [N, item_size] (include/wfh5w.h); the two entry points turn
+ * them into the net's input and put the net's output back into them, on the device.
+ *
+ * wfs_predict_prepare (reference normalize_waveforms, src/utils/SparseUtils.py:1564-1583), three launches:
+ *   coords    int32 [cap, 3] (x, y, event): the member at coord_offset, its event column renumbered from 0, +1 wherever a
+ *             row's event number differs from the previous row's (changes, not distinct values; row 0 starts event 0).
+ *             Integer block sums + an in-block scan: deterministic, no atomics.
+ *   feats     [cap, width] rows of feat_dtype (WFS_F32 / BF16 / F16) from the member at feat_offset:
+ *             WFS_PREDICT_WAVEFORM  int16 [width]: wf[i, j] * gain_factors[x, y, j >= width / 2] in fp64 (gain_factors
+ *                                   double [nx, ny, 2]), rounded once to fp32 and once more for 16-bit rows; a row whose
+ *                                   (x, y) lies outside [0, nx) x [0, ny) gets NaN instead of an out-of-bounds read
+ *             WFS_PREDICT_PULSE     float32 [width]: copied (rounded once for 16-bit rows)
+ *   rows [N, cap): zero features, zero coordinates (what the captured runners' buffers hold there); n_valid[0] = N.
+ *   Records need only be 2-byte friendly: 4-byte loads are used when item_size and the member's offset are multiples of
+ *   4, 2-byte loads otherwise, decided per call.  width must be even; `records` 4-byte aligned.
+ *   workspace: int32 [wfs_predict_workspace_ints(N)].
+ *
+ * wfs_predict_scatter (reference swap_sparse_from_dense / swap_sparse_from_event, :1459-1499): float32 columns
+ *   [col0, col0 + L) of the member at member_offset of every record, in place, from
+ *     WFS_PREDICT_DENSE  src [B, L, nx, ny]: row i takes src[event(i), l, x(i), y(i)]
+ *     WFS_PREDICT_EVENT  src [B, L]:         row i takes src[event(i), l]
+ *     WFS_PREDICT_ROWS   src [>= N, L]:      row i takes src[i, l]
+ *   (x, y, event) are the PREPARED coordinates int32 [N, 3]; a row whose coordinates fall outside src is left as it is.
+ *   src is fp32 / bf16 / fp16, widened exactly; affine != 0: (v - sub) * mul as an fp32 subtraction and an fp32
+ *   multiplication, each rounded once, never fused.  No other byte of a record is written; no atomics; one launch. */
+#define WFS_PREDICT_ROWS_PER_BLOCK 256   /* rows per workgroup of the coordinate scan */
+#define WFS_PREDICT_WAVEFORM 0
+#define WFS_PREDICT_PULSE 1
+#define WFS_PREDICT_DENSE 0
+#define WFS_PREDICT_EVENT 1
+#define WFS_PREDICT_ROWS 2
+size_t wfs_predict_workspace_ints(int64_t n);
+int wfs_predict_prepare(const void *records, int64_t n, int64_t item_size, int64_t coord_offset, int64_t feat_offset,
+                        int32_t feat_kind, int32_t width, const double *gain_factors, int32_t nx, int32_t ny, int64_t cap,
+                        int32_t *coords, void *feats, int32_t feat_dtype, int64_t *n_valid, int32_t *workspace,
+                        size_t workspace_ints, void *stream);
+int wfs_predict_scatter(void *records, int64_t n, int64_t item_size, int64_t member_offset, int32_t member_cols,
+                        int32_t col0, int32_t L, const int32_t *coords, const void *src, int32_t src_dtype, int32_t mode,
+                        int64_t B, int32_t nx, int32_t ny, int32_t affine, float sub, float mul, void *stream);
+
 /* opt-in per-kernel timing (HIP events on the launch stream), used by bench.py's roofline ---- */
 #define WFS_TIMER_GATHER_CONV 0
 #define WFS_TIMER_GATHER_DW 1

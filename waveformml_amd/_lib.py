@@ -15,6 +15,9 @@ WFS_TENSOR_TARGET_I64 = 3   # wfs_tensor_rows: a target of int64 class indices
 WFS_MAX_DIM = 4
 WFS_RNN_RELU, WFS_RNN_TANH = 0, 1
 WFS_LOSS_L1, WFS_LOSS_MSE = 0, 1
+WFS_PREDICT_ROWS_PER_BLOCK = 256      # rows per workgroup of wfs_predict_prepare's coordinate scan
+WFS_PREDICT_WAVEFORM, WFS_PREDICT_PULSE = 0, 1
+WFS_PREDICT_DENSE, WFS_PREDICT_EVENT, WFS_PREDICT_ROWS = 0, 1, 2
 WFS_ABI_VERSION = 6         # include/wfsparse.h: this binding's struct layouts and signatures
 TIMER_GATHER_CONV, TIMER_GATHER_DW, TIMER_RULEBOOK, TIMER_CONV_BACKWARD = 0, 1, 2, 3
 
@@ -195,6 +198,11 @@ SIGNATURES = {
                                           _i32, _i32, _i32, _i32] + [_vp] * 11),
     "wfs_segq_error_accumulate": (ctypes.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _i64, _vp, _i32, _i32, _i32]
                                   + [_vp] * 7),
+    "wfs_predict_workspace_ints": (_sz, [_i64]),
+    "wfs_predict_prepare": (ctypes.c_int, [_vp, _i64, _i64, _i64, _i64, _i32, _i32, _vp, _i32, _i32, _i64, _vp, _vp, _i32,
+                                           _vp, _vp, _sz, _vp]),
+    "wfs_predict_scatter": (ctypes.c_int, [_vp, _i64, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i64, _i32,
+                                           _i32, _i32, ctypes.c_float, ctypes.c_float, _vp]),
     "wfs_timing_enable": (ctypes.c_int, [_i32]),
     "wfs_timing_read": (ctypes.c_int, [_i32, ctypes.POINTER(ctypes.c_double), c_i64p]),
 }

@@ -569,10 +569,10 @@ class GraphedEvalStep(_CapturedRunner):
             logits = step.rerun(occlude_index=idx)     # forward only, column idx of the batch's features zeroed
     """
 
-    def __init__(self, module, example_batch, headroom=None, granule=None, sweep=False):
+    def __init__(self, module, example_batch, headroom=None, granule=None, sweep=False, min_rows=0):
         (coords, feats), labels = example_batch
         headroom, granule = self._headroom_granule(int(coords.shape[0]), int(labels.shape[0]), headroom, granule)
-        net = self._static_buffers(module, example_batch, headroom, granule)
+        net = self._static_buffers(module, example_batch, headroom, granule, min_rows=min_rows)
         self.feats_loaded = torch.zeros_like(self.feats) if sweep else None     # the batch's own features (sweeps)
         self._own_stream(coords.device)
         self._reuse, self.graph_fwd = None, None
