@@ -329,6 +329,24 @@ int wfs_conv_backward(const int32_t *table, int32_t K, int32_t identity_k, int64
 /* Second stage of up to 16 deferred wfs_gather_dw calls in one launch (deterministic: fixed summation order). */
 int wfs_dw_reduce_jobs(const wfs_dw_job *jobs, int32_t n, void *stream);
 
+/* Backward of  y = [relu](BatchNorm(z)),  z = first conv (2 -> 32 channels, no bias, K <= 27) of the network input X,
+ * in training mode (batch statistics), for 16-bit rows: dW [K, 2, 32], dgamma and dbeta as wfs_bn_relu_bwd followed by
+ * wfs_gather_dw (swap == 1) compute them -- the same arithmetic, roundings and summation orders, hence the same bits --
+ * in two launches instead of three and without the [R, 32] dz tensor.  The first layer has no dX, so dz is needed only
+ * as the stationary operand of the dW product: after the BatchNorm backward's reduce launch one kernel folds the
+ * partial sums, forms dz = gamma * invstd * (g - sum g / N - xhat * sum g xhat / N) per tile in registers, rounds it
+ * to the row type and contracts it with the gathered input rows.
+ * table / kmap_host / identity_k / R / r_dev: the by-output table as wfs_gather_dw takes it for this layer (kmap NULL,
+ * the identity or the SubM mirror).  Z, dY [R, 32] and X [X_rows, 2] have `dtype` WFS_BF16 or WFS_F16; dgamma / dbeta
+ * may be NULL.  `defer` as in wfs_gather_dw (an ordinary job: the slabs hold dW partials); dgamma and dbeta are written
+ * by the call itself either way.  Deterministic, no atomics.  Additions only: WFS_ABI_VERSION stays. */
+size_t wfs_first_conv_bn_backward_workspace_bytes(int32_t K, int64_t R);
+int wfs_first_conv_bn_backward(const int32_t *table, const int32_t *kmap_host, int32_t K, int32_t identity_k, int64_t R,
+                               const void *Z, const void *dY, const void *X, int64_t X_rows, const float *gamma,
+                               const float *beta, const float *save_mean, const float *save_invstd, int32_t relu,
+                               float *dW, float *dgamma, float *dbeta, int32_t dtype, void *workspace,
+                               size_t workspace_bytes, const int64_t *r_dev, wfs_dw_job *defer, void *stream);
+
 /* Conv bias gradient: out[c] = sum over the valid rows of X[r][c] (fp32 sums of fp32 / bf16 / fp16 rows; r_dev as
  * everywhere: NULL = R exact, else R is the capacity).  What autograd computes for spconv's `out_features += bias`
  * (reference layers with trainable_weights=True, src/models/SPConvBlocks.py:498).  Deterministic (fixed orders).      */

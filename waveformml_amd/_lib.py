@@ -85,6 +85,9 @@ SIGNATURES = {
     "wfs_conv_backward": (ctypes.c_int, [_vp, _i32, _i32, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _sz,
                                          _vp, ctypes.POINTER(DwJob), _i32, _vp]),
     "wfs_dw_reduce_jobs": (ctypes.c_int, [ctypes.POINTER(DwJob), _i32, _vp]),
+    "wfs_first_conv_bn_backward_workspace_bytes": (_sz, [_i32, _i64]),
+    "wfs_first_conv_bn_backward": (ctypes.c_int, [_vp, c_i32p, _i32, _i32, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp,
+                                                  _i32, _vp, _vp, _vp, _i32, _vp, _sz, _vp, ctypes.POINTER(DwJob), _vp]),
     "wfs_scatter_conv": (ctypes.c_int, [_vp, _i32, _i32, _i64, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _i32, _vp]),
     "wfs_maxpool_fwd": (ctypes.c_int, [_vp, c_i32p, _i32, _i64, _vp, _i64, _i32, _vp, _i32, _vp, _vp]),
     "wfs_maxpool_packed_ok": (ctypes.c_int, [_i32, _i32, _i32, _i32]),

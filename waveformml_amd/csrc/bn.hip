@@ -1060,6 +1060,45 @@ static int bn_bwd_slice(const void *X, const void *dY, int64_t N, int32_t C, lon
     return WFS_OK;
 }
 
+// The FIRST launch of wfs_bn_relu_bwd alone (the sums of g and g * xhat as per-block partials), with the kernel and the
+// grid that call would choose for whole rows of C channels: conv_mfma.hip's first-layer backward folds the partials
+// itself (fold order below, `*nblk` partials) and never writes dX.  C a multiple of 4, at most 128.
+int wfs_launch_bn_bwd_reduce(const void *X, const void *dY, long long N, int C, const float *gamma, const float *beta,
+                             const float *save_mean, const float *save_invstd, int relu, float *partial, int dtype,
+                             const long long *n_dev, hipStream_t stream, int *nblk_out) {
+    const dim3 block(TB);
+    long long rb = 0;
+    const int per = rr_plan(N, C, dtype == WFS_F32 ? 8 : 16, &rb);
+    if (per) {
+        const dim3 g2((unsigned)rb);
+#define WFS_BN_RED_RR(T, PER)                                                                                          \
+    k_bn_reduce_rr<T, PER, 1><<<g2, block, 0, stream>>>((const T *)X, (const T *)dY, N, n_dev, C, save_mean,           \
+                                                         save_invstd, gamma, beta, relu, partial)
+#define WFS_BN_RED_RR_T(T)                                                                                             \
+    if (per == 2) WFS_BN_RED_RR(T, 2); else if (per == 4) WFS_BN_RED_RR(T, 4); else if (per == 8) WFS_BN_RED_RR(T, 8);   \
+    else WFS_BN_RED_RR(T, 16)
+        if (dtype == WFS_F32) { WFS_BN_RED_RR_T(float); } else if (dtype == WFS_BF16) { WFS_BN_RED_RR_T(wfs_bf16); } else { WFS_BN_RED_RR_T(wfs_f16); }
+#undef WFS_BN_RED_RR_T
+#undef WFS_BN_RED_RR
+        *nblk_out = (int)rb;
+    } else {
+        const long long nblk = bn_reduce_blocks(N, C), rpb = wfs_cdiv(N, nblk);
+        const dim3 grid((unsigned)nblk);
+        if (dtype == WFS_F32)
+            k_bn_reduce<float, 4, 1><<<grid, block, 0, stream>>>((const float *)X, (const float *)dY, N, n_dev, C, C, rpb,
+                                                                 save_mean, save_invstd, gamma, beta, relu, partial);
+        else if (dtype == WFS_BF16)
+            k_bn_reduce<wfs_bf16, 4, 1><<<grid, block, 0, stream>>>((const wfs_bf16 *)X, (const wfs_bf16 *)dY, N, n_dev, C, C,
+                                                                    rpb, save_mean, save_invstd, gamma, beta, relu, partial);
+        else
+            k_bn_reduce<wfs_f16, 4, 1><<<grid, block, 0, stream>>>((const wfs_f16 *)X, (const wfs_f16 *)dY, N, n_dev, C, C,
+                                                                   rpb, save_mean, save_invstd, gamma, beta, relu, partial);
+        *nblk_out = (int)nblk;
+    }
+    WFS_LAUNCH_CHECK();
+    return WFS_OK;
+}
+
 extern "C" int wfs_bn_relu_bwd(const void *X, const void *dY, int64_t N, int32_t C, const float *gamma,
                                const float *beta, const float *save_mean, const float *save_invstd, int32_t training,
                                int32_t relu, void *dX, float *dgamma, float *dbeta, void *workspace,

@@ -1397,6 +1397,190 @@ __global__ void __launch_bounds__(512, 2) k_gdw_c32c2_bf16(const int *__restrict
     }
 }
 
+// First layer followed by BatchNorm (+ ReLU), 16-bit rows (include/wfsparse.h wfs_first_conv_bn_backward): the BatchNorm
+// backward's elementwise pass inside k_gdw_c32c2_bf16.  The first layer has no dX, so dz = a (g - k1 - xhat k2) is needed
+// only as the stationary operand of this product: the kernel folds the reduce launch's partials in its prologue (the
+// order of bn.hip's fold_partials; block 0 publishes dbeta / dgamma), loads the tile's z rows beside its dY rows, forms
+// dz in registers with the expressions of bn.hip's k_bn_bwd_apply_rr, rounds it to the row type as that kernel's store
+// does, and puts it in the B image.  Same tiles, same grid, same slabs and summation orders as k_gdw_c32c2_bf16 on a
+// stored dz: the same bits, without the elementwise launch and the [R, 32] dz round trip.
+template <typename H>
+__global__ void __launch_bounds__(512, 2) k_gdw_bnapply_c32c2(const int *__restrict__ table, int mirror, int K,
+                                                             int identity_k, long long Rcap,
+                                                             const long long *__restrict__ r_dev,
+                                                             const H *__restrict__ Z, const H *__restrict__ S,
+                                                             const H *__restrict__ G, const float *__restrict__ partial,
+                                                             int nblk, const float *__restrict__ mean,
+                                                             const float *__restrict__ invstd,
+                                                             const float *__restrict__ gamma, const float *__restrict__ beta,
+                                                             int relu, float *__restrict__ dgamma, float *__restrict__ dbeta,
+                                                             float *__restrict__ part) {
+    __shared__ __attribute__((aligned(16))) unsigned sA[C2_WAVES][32 * 33];
+    __shared__ __attribute__((aligned(16))) unsigned short sB[C2_WAVES][32 * 32];
+    __shared__ float sSlice[2 * 256];
+    __shared__ float4 sP[32], sQ[32];               // per channel: (mean, invstd, gamma, beta), (k1, k2, -, -)
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int c = lane & 31, h = lane >> 5;
+    const int grow = lane >> 2, gchunk = lane & 3;
+    unsigned *myA = sA[wid];
+    unsigned short *myB = sB[wid];
+    const long long R = valid_rows(Rcap, r_dev);
+    // ---- the sums of g and g * xhat from the reduce launch's partials [nblk][2][32], as fold_partials of bn.hip adds
+    // them with 256 threads: slice sl = 0..7 owns partials sl, sl + 8, ... (at most 32, all asked for before the first
+    // add), then the slices in slice order
+    {
+        const int col = threadIdx.x & 31, sl = (threadIdx.x >> 5) & 7;
+        if (threadIdx.x < 256) {
+            float av[32], bv[32];
+#pragma unroll
+            for (int i = 0; i < 32; ++i) {
+                const int p = sl + i * 8;
+                const float *q = partial + (long long)(p < nblk ? p : 0) * 64 + col;
+                av[i] = q[0];
+                bv[i] = q[32];
+            }
+            float a = 0.f, bb = 0.f;
+#pragma unroll
+            for (int i = 0; i < 32; ++i) {
+                const bool ok = sl + i * 8 < nblk;
+                a += ok ? av[i] : 0.f;
+                bb += ok ? bv[i] : 0.f;
+            }
+            sSlice[threadIdx.x] = a;
+            sSlice[256 + threadIdx.x] = bb;
+        }
+        __syncthreads();
+        if (threadIdx.x < 32) {
+            float ta = 0.f, tb = 0.f;
+            for (int q = 0; q < 8; ++q) {
+                ta += sSlice[q * 32 + col];
+                tb += sSlice[256 + q * 32 + col];
+            }
+            if (blockIdx.x == 0) {
+                if (dbeta) dbeta[col] = ta;
+                if (dgamma) dgamma[col] = tb;
+            }
+            const float invN = R > 0 ? 1.f / (float)R : 0.f;
+            sP[col] = make_float4(mean[col], invstd[col], gamma ? gamma[col] : 1.f, beta ? beta[col] : 0.f);
+            sQ[col] = make_float4(ta * invN, tb * invN, 0.f, 0.f);
+        }
+        __syncthreads();
+    }
+    const long long ntiles = (R + 31) >> 5;
+    f32x16 acc0, acc1;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc0[i] = acc1[i] = 0.f;
+    const unsigned *Gw = reinterpret_cast<const unsigned *>(G);          // one dword = the 2 channels of an input row
+    for (long long tile = (long long)blockIdx.x * C2_WAVES + wid; tile < ntiles; tile += (long long)gridDim.x * C2_WAVES) {
+        const long long row0 = tile * 32;
+        const long long trow = row0 + c < R ? row0 + c : R - 1;
+        const bool tlive = row0 + c < R;
+        int nb[14];
+#pragma unroll
+        for (int t = 0; t < 14; ++t) {
+            int k = 2 * t + h;
+            int kk = k < K ? k : K - 1;
+            nb[t] = table[(long long)(mirror ? K - 1 - kk : kk) * Rcap + trow];
+        }
+        // ---- stationary rows of dY and z (issued before the gathers' addresses are known)
+        const long long ra = row0 + grow, rb = row0 + grow + 16;
+        const long long oa = (ra < R ? ra : R - 1) * 32 + gchunk * 8, ob = (rb < R ? rb : R - 1) * 32 + gchunk * 8;
+        const uint4 s0 = *(const uint4 *)(S + oa);
+        const uint4 s1 = *(const uint4 *)(S + ob);
+        const uint4 z0 = *(const uint4 *)(Z + oa);
+        const uint4 z1 = *(const uint4 *)(Z + ob);
+        unsigned xv[14];
+#pragma unroll
+        for (int t = 0; t < 14; ++t) {
+            int k = 2 * t + h;
+            int n = (k == identity_k) ? (int)trow : nb[t];
+            bool ok = tlive && k < K && n >= 0;
+            nb[t] = ok ? n : -1;
+            xv[t] = Gw[ok ? n : 0];
+        }
+        __builtin_amdgcn_wave_barrier();            // the previous tile's fragment reads are done (LDS is in order)
+        // ---- dz of the tile's rows, under the gathers' latency: k_bn_bwd_apply_rr's arithmetic and rounding
+        {
+            const unsigned zw[2][4] = {{z0.x, z0.y, z0.z, z0.w}, {z1.x, z1.y, z1.z, z1.w}};
+            const unsigned gw[2][4] = {{s0.x, s0.y, s0.z, s0.w}, {s1.x, s1.y, s1.z, s1.w}};
+            unsigned ow[2][4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float4 pl = sP[gchunk * 8 + 2 * j], ph = sP[gchunk * 8 + 2 * j + 1];
+                const float4 ql = sQ[gchunk * 8 + 2 * j], qh = sQ[gchunk * 8 + 2 * j + 1];
+#pragma unroll
+                for (int half = 0; half < 2; ++half) {
+                    float xv2[2], gv2[2], o[2];
+                    wfs_unpack2<H>(zw[half][j], xv2[0], xv2[1]);
+                    wfs_unpack2<H>(gw[half][j], gv2[0], gv2[1]);
+#pragma unroll
+                    for (int e = 0; e < 2; ++e) {
+                        const float m = e ? ph.x : pl.x, is = e ? ph.y : pl.y, ga = e ? ph.z : pl.z, be = e ? ph.w : pl.w;
+                        const float k1 = e ? qh.x : ql.x, k2 = e ? qh.y : ql.y;
+                        float xh = (xv2[e] - m) * is;
+                        float gi = gv2[e];
+                        if (relu && !(fmaf(ga, xh, be) > 0.f)) gi = 0.f;
+                        o[e] = ga * is * (gi - k1 - xh * k2);
+                    }
+                    ow[half][j] = wfs_pack2<H>(o[0], o[1]);
+                }
+            }
+            *(uint4 *)(myB + grow * 32 + gchunk * 8) = keep_if(make_uint4(ow[0][0], ow[0][1], ow[0][2], ow[0][3]), ra < R);
+            *(uint4 *)(myB + (grow + 16) * 32 + gchunk * 8) = keep_if(make_uint4(ow[1][0], ow[1][1], ow[1][2], ow[1][3]), rb < R);
+        }
+#pragma unroll
+        for (int t = 0; t < 14; ++t) {
+            int k = 2 * t + h;
+            myA[c * 33 + k] = nb[t] >= 0 ? xv[t] : 0u;          // k = 27 (h = 1, t = 13) lands in the zero padding
+        }
+        if (h == 0) {
+#pragma unroll
+            for (int k = 28; k < 32; ++k) myA[c * 33 + k] = 0u;
+        }
+        __builtin_amdgcn_wave_barrier();
+        // ---- fragments: A^T (columns of the [row][66 u16] image), B (columns of the [row][32] image)
+        const unsigned short *A16 = reinterpret_cast<const unsigned short *>(myA);
+        unsigned wa[2][2][4], wb[2][4];
+#pragma unroll
+        for (int st = 0; st < 2; ++st)
+#pragma unroll
+            for (int m = 0; m < 4; ++m) {
+                int r0 = 16 * st + 8 * h + 2 * m;
+                wa[0][st][m] = (unsigned)A16[r0 * 66 + c] | ((unsigned)A16[(r0 + 1) * 66 + c] << 16);
+                wa[1][st][m] = (unsigned)A16[r0 * 66 + 32 + c] | ((unsigned)A16[(r0 + 1) * 66 + 32 + c] << 16);
+                wb[st][m] = (unsigned)myB[r0 * 32 + c] | ((unsigned)myB[(r0 + 1) * 32 + c] << 16);
+            }
+#pragma unroll
+        for (int st = 0; st < 2; ++st) {
+            uint4 a_lo = {wa[0][st][0], wa[0][st][1], wa[0][st][2], wa[0][st][3]};
+            uint4 a_hi = {wa[1][st][0], wa[1][st][1], wa[1][st][2], wa[1][st][3]};
+            uint4 bb = {wb[st][0], wb[st][1], wb[st][2], wb[st][3]};
+            acc0 = mfma16<H>(a_lo, bb, acc0);
+            acc1 = mfma16<H>(a_hi, bb, acc1);
+        }
+    }
+    // deterministic block reduction, as k_gdw_c32c2_bf16
+    __syncthreads();
+    float *sRed = reinterpret_cast<float *>(&sA[0][0]);                  // [C2_WAVES][1024] <= 8 x 32 x 33 words
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            int col = (i & 3) + 8 * (i >> 2) + 4 * h;
+            sRed[wid * 1024 + col * 32 + c] = half ? acc1[i] : acc0[i];
+        }
+        __syncthreads();
+        for (int e = threadIdx.x; e < 1024; e += 512) {
+            float v = 0.f;
+#pragma unroll
+            for (int w = 0; w < C2_WAVES; ++w) v += sRed[w * 1024 + e];
+            const int ee = half * 1024 + e;
+            if (ee < K * 64) part[(long long)blockIdx.x * K * 64 + ee] = v;
+        }
+        __syncthreads();
+    }
+}
+
 // fp32 form of the first-layer dW on the matrix cores (exact fp32, v_mfma_f32_32x32x2_f32 with the tile's ROWS as the
 // contraction): D[col = 2 k + ch][b] += sum_rows Xg[row][col] * dY[row][b].  Lane (c, h) supplies, for row pair s,
 // A = Xg[2 s + h][col = c (+ 32)] and B = dY[2 s + h][b = c] -- the dY rows straight from global memory (whole 128-byte
@@ -1980,6 +2164,36 @@ int wfs_launch_gdw_c32c2(const int *table, int mirror, int K, int identity_k, lo
         return WFS_OK;
     }
     k_slab_reduce<<<dim3((unsigned)((per + 31) / 32)), dim3(chunks > 64 ? 1024 : 256), 0, stream>>>(part, chunks, per, K, 2, 32, swap ? 0 : 1, dW);
+    WFS_LAUNCH_CHECK();
+    return WFS_OK;
+}
+
+long long wfs_first_bn_slabs(long long R) {
+    const long long ntiles = (R + 31) >> 5;
+    long long chunks = (ntiles + C2_WAVES - 1) / C2_WAVES;          // as wfs_launch_gdw_c32c2: the same slabs
+    return chunks > 512 ? 512 : (chunks < 1 ? 1 : chunks);
+}
+
+int wfs_launch_first_bn_bwd(const int *table, int mirror, int K, int identity_k, long long R, const long long *r_dev,
+                            const void *Z, const void *dY, const void *X, const float *gamma, const float *beta,
+                            const float *mean, const float *invstd, int relu, const float *partial, int nblk, float *dW,
+                            float *dgamma, float *dbeta, float *part, int dtype, wfs_dw_job *defer, hipStream_t stream) {
+    const long long chunks = wfs_first_bn_slabs(R);
+    if (dtype == WFS_BF16)
+        k_gdw_bnapply_c32c2<wfs_bf16><<<dim3((unsigned)chunks), dim3(512), 0, stream>>>(
+            table, mirror, K, identity_k, R, r_dev, (const wfs_bf16 *)Z, (const wfs_bf16 *)dY, (const wfs_bf16 *)X, partial,
+            nblk, mean, invstd, gamma, beta, relu, dgamma, dbeta, part);
+    else
+        k_gdw_bnapply_c32c2<wfs_f16><<<dim3((unsigned)chunks), dim3(512), 0, stream>>>(
+            table, mirror, K, identity_k, R, r_dev, (const wfs_f16 *)Z, (const wfs_f16 *)dY, (const wfs_f16 *)X, partial,
+            nblk, mean, invstd, gamma, beta, relu, dgamma, dbeta, part);
+    WFS_LAUNCH_CHECK();
+    const long long per = (long long)K * 64;          // part is [chunk][k][ci][co]: dW's own layout
+    if (defer) {
+        *defer = wfs_dw_job{part, chunks, per, K, 2, 32, 0, dW};
+        return WFS_OK;
+    }
+    k_slab_reduce<<<dim3((unsigned)((per + 31) / 32)), dim3(chunks > 64 ? 1024 : 256), 0, stream>>>(part, chunks, per, K, 2, 32, 0, dW);
     WFS_LAUNCH_CHECK();
     return WFS_OK;
 }

@@ -644,6 +644,54 @@ extern "C" int wfs_conv_backward(const int32_t *table, int32_t K, int32_t identi
                                 (float *)workspace, dtype, defer, stream);
 }
 
+static size_t first_bn_slab_bytes(int32_t K, int64_t R) {
+    return wfs_align_up((size_t)wfs_first_bn_slabs(R) * (size_t)K * 64 * sizeof(float), 256);
+}
+extern "C" size_t wfs_first_conv_bn_backward_workspace_bytes(int32_t K, int64_t R) {
+    return first_bn_slab_bytes(K, R) + wfs_bn_workspace_bytes(R, 32);      // the dW slabs, then the BatchNorm partials
+}
+
+// First conv (2 -> 32, no bias) + BatchNorm (+ ReLU) backward without a dz tensor: the BatchNorm backward's reduce launch
+// (bn.hip), then conv_mfma.hip's k_gdw_bnapply_c32c2
+extern "C" int wfs_first_conv_bn_backward(const int32_t *table, const int32_t *kmap_host, int32_t K, int32_t identity_k,
+                                          int64_t R, const void *Z, const void *dY, const void *X, int64_t X_rows,
+                                          const float *gamma, const float *beta, const float *save_mean,
+                                          const float *save_invstd, int32_t relu, float *dW, float *dgamma, float *dbeta,
+                                          int32_t dtype, void *workspace, size_t workspace_bytes, const int64_t *r_dev,
+                                          wfs_dw_job *defer, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    WFS_REQUIRE(K >= 1 && K <= 27, WFS_EINVAL, "K = %d (1 .. 27)", K);
+    WFS_REQUIRE(dtype == WFS_BF16 || dtype == WFS_F16, WFS_EINVAL, "16-bit rows only (dtype %d)", dtype);
+    WFS_REQUIRE(dW, WFS_EINVAL, "NULL dW");
+    WFS_REQUIRE(R >= 0 && R < (1ll << 31) && X_rows < (1ll << 31), WFS_EINVAL, "too many rows");
+    if (defer) *defer = wfs_dw_job{nullptr, 0, 0, 0, 0, 0, 0, nullptr};
+    if (R == 0) {
+        WFS_HIP_CHECK(hipMemsetAsync(dW, 0, (size_t)K * 64 * sizeof(float), stream));
+        if (dgamma) WFS_HIP_CHECK(hipMemsetAsync(dgamma, 0, 32 * sizeof(float), stream));
+        if (dbeta) WFS_HIP_CHECK(hipMemsetAsync(dbeta, 0, 32 * sizeof(float), stream));
+        return WFS_OK;
+    }
+    WFS_REQUIRE(table && Z && dY && X && save_mean && save_invstd && workspace, WFS_EINVAL, "NULL device pointer");
+    WFS_REQUIRE(((uintptr_t)workspace & 15) == 0, WFS_EINVAL, "the workspace must be 16-byte aligned");
+    WFS_REQUIRE(workspace_bytes >= wfs_first_conv_bn_backward_workspace_bytes(K, R), WFS_EWORKSPACE, "workspace too small");
+    bool is_ident = true, is_mirror = kmap_host != nullptr;
+    for (int k = 0; k < K && kmap_host; ++k) {
+        is_ident = is_ident && kmap_host[k] == k;
+        is_mirror = is_mirror && kmap_host[k] == K - 1 - k;
+    }
+    WFS_REQUIRE(is_ident || is_mirror, WFS_EINVAL, "the column map must be the identity or the SubM mirror");
+    float *part = (float *)workspace;
+    float *partial = (float *)((char *)workspace + first_bn_slab_bytes(K, R));
+    int nblk = 0;
+    int rc = wfs_launch_bn_bwd_reduce(Z, dY, R, 32, gamma, beta, save_mean, save_invstd, relu ? 1 : 0, partial, dtype,
+                                      (const long long *)r_dev, stream, &nblk);
+    if (rc != WFS_OK) return rc;
+    WfsTimerScope timer(WFS_TIMER_GATHER_DW, stream);
+    return wfs_launch_first_bn_bwd(table, is_ident ? 0 : 1, K, identity_k, R, (const long long *)r_dev, Z, dY, X, gamma, beta,
+                                   save_mean, save_invstd, relu ? 1 : 0, partial, nblk, dW, dgamma, dbeta, part, dtype, defer,
+                                   stream);
+}
+
 extern "C" int wfs_dw_reduce_jobs(const wfs_dw_job *jobs, int32_t n, void *stream) {
     WFS_REQUIRE(n >= 0 && n <= 16 && (n == 0 || jobs), WFS_EINVAL, "%d jobs (0 .. 16)", n);
     wfs_dw_job live[16];

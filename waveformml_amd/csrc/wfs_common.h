@@ -133,3 +133,13 @@ int wfs_launch_gdw_c32c2(const int *table, int mirror, int K, int identity_k, lo
                          const void *S, const void *G, int swap, float *dW, float *part, int dtype,
                          wfs_dw_job *defer, hipStream_t stream);
 int wfs_launch_dw_jobs(const wfs_dw_job *jobs, int n, hipStream_t stream);
+// first conv (2 -> 32) + BatchNorm backward without a dz tensor: bn.hip's reduce launch, then conv_mfma.hip's
+// k_gdw_bnapply_c32c2, which folds the partials, forms dz in registers and contracts it with the gathered input rows
+int wfs_launch_bn_bwd_reduce(const void *X, const void *dY, long long N, int C, const float *gamma, const float *beta,
+                             const float *save_mean, const float *save_invstd, int relu, float *partial, int dtype,
+                             const long long *n_dev, hipStream_t stream, int *nblk_out);
+long long wfs_first_bn_slabs(long long R);
+int wfs_launch_first_bn_bwd(const int *table, int mirror, int K, int identity_k, long long R, const long long *r_dev,
+                            const void *Z, const void *dY, const void *X, const float *gamma, const float *beta,
+                            const float *mean, const float *invstd, int relu, const float *partial, int nblk, float *dW,
+                            float *dgamma, float *dbeta, float *part, int dtype, wfs_dw_job *defer, hipStream_t stream);

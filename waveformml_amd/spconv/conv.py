@@ -59,7 +59,11 @@ class SparseConvolution(SparseModule, ops.StickyFlags):
             bound = 1 / math.sqrt(fan_in)
             init.uniform_(self.bias, -bound, bound)
 
-    def forward(self, input):
+    def forward(self, input, bn_tail=None):
+        """``bn_tail`` = (BatchNorm1d, relu, between): SparseSequential's offer to run the BatchNorm (+ ReLU) that
+        follows this layer in the same autograd node (functional.FirstConvBNFunction, taken by a first layer it covers;
+        ``between(out_tensor)`` runs between the conv and the BatchNorm launches).  The output tensor then has
+        ``bn_applied`` set."""
         assert isinstance(input, SparseConvTensor)
         features = input.features
         indices = input.indices
@@ -85,6 +89,7 @@ class SparseConvolution(SparseModule, ops.StickyFlags):
             out_tensor.prefetched = getattr(input, "prefetched", None)
             return out_tensor
         datas = input.find_indice_pair(self.indice_key)
+        fused = False
         if self.inverse:
             assert datas is not None and self.indice_key is not None
             rb = datas.rulebook
@@ -119,7 +124,12 @@ class SparseConvolution(SparseModule, ops.StickyFlags):
                 input.unique = not rb.has_dup
                 input.indice_dict[self.indice_key] = IndiceData(rb, spatial_shape)
             out_indices = rb.out_indices
-            if self.subm:
+            fused = (bn_tail is not None and not self.transposed
+                     and Fsp.first_conv_bn_ok(features, self.weight, self.bias, rb, bn_tail[0]))
+            if fused:
+                out_features = features          # stands in until the fused node below has run
+                out_unique = input.unique if self.subm else True
+            elif self.subm:
                 out_features = Fsp.indice_subm_conv(features, self.weight, self.bias, rb)
                 out_unique = input.unique
             else:
@@ -138,6 +148,11 @@ class SparseConvolution(SparseModule, ops.StickyFlags):
             out_tensor.events = rb.events_out                           # the event-local build numbered them by event
         if not self.subm and not self.inverse:
             out_tensor.cell_map = getattr(rb, "cell_map", None)      # dense() of THIS row set can use the build's map
+        if not self.inverse and fused:
+            bn, relu, between = bn_tail
+            out_tensor.features = Fsp.first_conv_bn_relu(features, self.weight, rb, bn, relu,
+                                                         None if between is None else (lambda: between(out_tensor)))
+            out_tensor.bn_applied = True
         return out_tensor
 
 

@@ -583,6 +583,25 @@ class ToDenseFunction(Function):
         return dX, None, None, None, None, None, None
 
 
+def _bn_relu_forward(x, weight, bias, running_mean, running_var, momentum, eps, training, relu, n_dev, batches_tracked):
+    """(y, save_mean, save_invstd) of y = [relu](BatchNorm1d(x)) over the active rows: the two forward launches."""
+    lib = _lib.load()
+    N, C = x.shape
+    y = _rows(tuple(x.shape), x, n_dev)
+    for t in (weight, bias, running_mean, running_var):
+        assert t is None or (t.dtype == torch.float32 and t.numel() == C and t.is_contiguous())
+    save_mean = torch.empty((C,), dtype=torch.float32, device=x.device)
+    save_invstd = torch.empty((C,), dtype=torch.float32, device=x.device)
+    ws = torch.empty((max(int(lib.wfs_bn_workspace_bytes(N, C)), 1),), dtype=torch.uint8, device=x.device)
+    _lib.check(lib.wfs_bn_relu_fwd(_lib.ptr(x), N, C, _lib.ptr(weight), _lib.ptr(bias), _lib.ptr(running_mean),
+                                   _lib.ptr(running_var), _lib.ptr(batches_tracked) if training else None,
+                                   float(momentum), float(eps), 1 if training else 0,
+                                   1 if relu else 0, _lib.ptr(y), _lib.ptr(save_mean), _lib.ptr(save_invstd),
+                                   _lib.ptr(ws), ws.numel(), _lib.dtype_code(x), _lib.ptr(n_dev),
+                                   _lib.stream_ptr()))
+    return y, save_mean, save_invstd
+
+
 class BatchNormReLUFunction(Function):
     """nn.BatchNorm1d (+ nn.ReLU) over the active rows [N, C] in two launches per direction
     (reference: the plain modules inside spconv.SparseSequential, src/models/SPConvBlocks.py:505-508)."""
@@ -590,21 +609,9 @@ class BatchNormReLUFunction(Function):
     @staticmethod
     def forward(ctx, x, weight, bias, running_mean, running_var, momentum, eps, training, relu, n_dev=None,
                 batches_tracked=None):
-        lib = _lib.load()
         x = _features_ok(x)
-        N, C = x.shape
-        y = _rows(tuple(x.shape), x, n_dev)
-        for t in (weight, bias, running_mean, running_var):
-            assert t is None or (t.dtype == torch.float32 and t.numel() == C and t.is_contiguous())
-        save_mean = torch.empty((C,), dtype=torch.float32, device=x.device)
-        save_invstd = torch.empty((C,), dtype=torch.float32, device=x.device)
-        ws = torch.empty((max(int(lib.wfs_bn_workspace_bytes(N, C)), 1),), dtype=torch.uint8, device=x.device)
-        _lib.check(lib.wfs_bn_relu_fwd(_lib.ptr(x), N, C, _lib.ptr(weight), _lib.ptr(bias), _lib.ptr(running_mean),
-                                       _lib.ptr(running_var), _lib.ptr(batches_tracked) if training else None,
-                                       float(momentum), float(eps), 1 if training else 0,
-                                       1 if relu else 0, _lib.ptr(y), _lib.ptr(save_mean), _lib.ptr(save_invstd),
-                                       _lib.ptr(ws), ws.numel(), _lib.dtype_code(x), _lib.ptr(n_dev),
-                                       _lib.stream_ptr()))
+        y, save_mean, save_invstd = _bn_relu_forward(x, weight, bias, running_mean, running_var, momentum, eps, training,
+                                                     relu, n_dev, batches_tracked)
         ctx.save_for_backward(x, weight, bias, save_mean, save_invstd)
         ctx.flags = (bool(training), bool(relu))
         ctx.n_dev = n_dev
@@ -655,6 +662,93 @@ def can_fuse_batch_norm(bn, features):
             and 1 <= c <= 65536
             and (bn.weight is None or bn.weight.dtype == torch.float32)
             and (bn.training or bn.running_mean is not None))
+
+
+def first_conv_bn_backward(table, kmap, K, identity_k, R, z, dY, features, gamma, beta, save_mean, save_invstd, relu,
+                           r_dev, filters):
+    """(dW [K, 2, 32], dgamma, dbeta) of y = [relu](BatchNorm1d(z)), z = the first conv (2 -> 32, no bias) of the network
+    input ``features``, from dL/dy in two launches and without a dz tensor (include/wfsparse.h
+    wfs_first_conv_bn_backward): the bits of bn_relu_backward + gather_dw.  The gradients go straight into their slots
+    of a registered flat gradient buffer; dW's slab reduction joins the pass's deferred ones as gather_dw's does."""
+    lib = _lib.load()
+    dW = grad_like(filters, (K, 2, 32)) if filters.numel() == K * 64 else torch.empty((K, 2, 32), dtype=torch.float32,
+                                                                                      device=z.device)
+    dgamma = grad_like(gamma) if gamma is not None else None
+    dbeta = grad_like(beta) if beta is not None else None
+    assert z.dtype == dY.dtype == features.dtype and z.shape == dY.shape == (R, 32) and features.shape[1] == 2
+    assert table.dtype == torch.int32 and table.shape == (K, R)
+    ws = torch.empty((int(lib.wfs_first_conv_bn_backward_workspace_bytes(K, R)),), dtype=torch.uint8, device=z.device)
+    job = _dw_job(dW)
+    _lib.check(lib.wfs_first_conv_bn_backward(_lib.ptr(table), kmap, K, identity_k, R, _lib.ptr(z), _lib.ptr(dY),
+                                              _lib.ptr(features), features.shape[0], _lib.ptr(gamma), _lib.ptr(beta),
+                                              _lib.ptr(save_mean), _lib.ptr(save_invstd), 1 if relu else 0, _lib.ptr(dW),
+                                              _lib.ptr(dgamma), _lib.ptr(dbeta), _lib.dtype_code(z), _lib.ptr(ws),
+                                              ws.numel(), _lib.ptr(r_dev), job, _lib.stream_ptr()))
+    _queue_dw_job(job, ws)
+    if ACCOUNT is not None:
+        _account("gather_dw", table, R, R, 32, features.shape[0], 2, K, 32, 2, z.element_size())
+    return dW, dgamma, dbeta
+
+
+def first_conv_bn_ok(features, filters, conv_bias, rulebook, bn):
+    """Does FirstConvBNFunction cover this conv + BatchNorm pair?  2 -> 32 channels, K <= 27, distinct outputs, no conv
+    bias, 16-bit rows that need no gradient (the network input), BatchNorm normalising with batch statistics."""
+    rb = rulebook
+    return bool(features.is_cuda and features.dim() == 2 and features.shape[1] == 2 and filters.shape[-2] == 2
+                and filters.shape[-1] == 32 and filters.dtype == torch.float32 and rb.K <= 27 and not rb.has_dup
+                and conv_bias is None and features.dtype in (torch.bfloat16, torch.float16)
+                and not features.requires_grad and bn.num_features == 32 and features.shape[0] > 0 and rb.M > 0
+                and (bn.training or (bn.running_mean is None and bn.running_var is None))
+                and type(bn) is torch.nn.BatchNorm1d and bn.momentum is not None
+                and (bn.weight is None or bn.weight.dtype == torch.float32))
+
+
+class FirstConvBNFunction(Function):
+    """First conv (2 -> 32, no bias) + nn.BatchNorm1d (+ nn.ReLU) of a sparse stack as one autograd node.  The forward
+    launches are those of SparseConvFunction and BatchNormReLUFunction, in their order (``between`` runs after the conv:
+    SparseSequential forks its rulebook prefetch there); the backward (first_conv_bn_backward) has the BatchNorm
+    backward's elementwise pass inside the dW kernel: one launch and the dz tensor fewer, the same gradients bit for
+    bit."""
+
+    @staticmethod
+    def forward(ctx, features, filters, weight, bias, running_mean, running_var, momentum, eps, relu, rulebook,
+                batches_tracked, between):
+        rb = rulebook
+        features = _features_ok(features)
+        K = rb.K
+        W = filters.detach().reshape(K, 2, 32).float().contiguous()
+        ident = rb.centre_k if rb.subm else -1
+        assert features.shape[0] == rb.N
+        table, kmap = rb.table_by_out()
+        z = gather_conv(table, kmap, K, ident, rb.M, features, W, False, None, rb.m_dev, None)
+        if between is not None:
+            between()
+        y, save_mean, save_invstd = _bn_relu_forward(z, weight, bias, running_mean, running_var, momentum, eps, True,
+                                                     relu, rb.m_dev, batches_tracked)
+        ctx.save_for_backward(features, filters, weight, bias, z, save_mean, save_invstd)
+        ctx.rb, ctx.relu = rb, bool(relu)
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        features, filters, weight, bias, z, save_mean, save_invstd = ctx.saved_tensors
+        rb = ctx.rb
+        dY = as_grad(grad_output, z.dtype)
+        table, kmap = rb.table_by_out()
+        dW, dgamma, dbeta = first_conv_bn_backward(table, kmap, rb.K, rb.centre_k if rb.subm else -1, rb.M, z, dY,
+                                                   features, weight, bias, save_mean, save_invstd, ctx.relu, rb.m_dev,
+                                                   filters)
+        dW = dW.reshape(filters.shape).to(filters.dtype)
+        return (None, dW if ctx.needs_input_grad[1] else None, dgamma if ctx.needs_input_grad[2] else None,
+                dbeta if ctx.needs_input_grad[3] else None, None, None, None, None, None, None, None, None)
+
+
+def first_conv_bn_relu(features, filters, rulebook, bn, relu, between=None):
+    """conv (filters, no bias) -> ``bn`` [-> ReLU] over a rulebook first_conv_bn_ok() accepted."""
+    tracked = bn.num_batches_tracked if (bn.training and bn.track_running_stats) else None
+    return FirstConvBNFunction.apply(
+        features, filters, bn.weight, bn.bias, bn.running_mean if bn.track_running_stats else None,
+        bn.running_var if bn.track_running_stats else None, bn.momentum, bn.eps, relu, rulebook, tracked, between)
 
 
 class SkinnyLinearFunction(Function):

@@ -131,6 +131,24 @@ class SparseSequential(SparseModule):
                     break                           # ToDense or an unknown sparse module ends the sparse stack
         x.prefetched = plan
 
+    def _bn_tail(self, mods, i, input, want_prefetch):
+        """(bn, relu, between) when mods[i] is a conv over the network input followed by a BatchNorm1d the fused kernels
+        cover -- what SparseConvolution.forward needs to run the pair as one autograd node -- else None."""
+        from . import functional as Fsp
+        from .conv import SparseConvolution
+        module = mods[i]
+        if not (isinstance(module, SparseConvolution) and _is_sparse_tensor(input) and i + 1 < len(mods)
+                and isinstance(mods[i + 1], nn.BatchNorm1d) and input.indices.shape[0] != 0
+                and module.in_channels == 2 and module.out_channels == 32 and module.bias is None
+                and not (module.conv1x1 or module.inverse or module.transposed)
+                and torch.is_tensor(input.features) and input.features.is_cuda
+                and input.features.dtype in (torch.bfloat16, torch.float16) and not input.features.requires_grad):
+            return None
+        relu = i + 2 < len(mods) and type(mods[i + 2]) is nn.ReLU
+        rest = mods[i + 1:]
+        between = (lambda out: self._prefetch_rulebooks(rest, out)) if want_prefetch else None
+        return mods[i + 1], relu, between
+
     def forward(self, input):
         return self.run(input, list(self._modules.values()))
 
@@ -150,7 +168,18 @@ class SparseSequential(SparseModule):
             if isinstance(module, SparseModule):
                 if _is_sparse_tensor(input):
                     input.dense_follows = self._dense_follows(mods, i)
-                input = module(input)
+                bn_tail = self._bn_tail(mods, i, input, want_prefetch)
+                if bn_tail is not None:
+                    # conv + BatchNorm1d [+ ReLU] of a first layer as one autograd node (two backward launches instead
+                    # of three, no dz tensor); the layer declines when it is not such a layer.  The prefetch below forks where it
+                    # always did, behind the conv launch.
+                    input = module(input, bn_tail=bn_tail)
+                    if getattr(input, "bn_applied", False):
+                        input.bn_applied = False
+                        want_prefetch = want_prefetch and getattr(input, "prefetched", None) is None
+                        i += 2 if bn_tail[1] else 1
+                else:
+                    input = module(input)
                 if want_prefetch and _is_sparse_tensor(input):
                     # the first layer has built its own rulebook and launched its conv on this stream; the
                     # remaining layers' rulebooks now build on the side stream beside what follows
