@@ -1286,14 +1286,103 @@ __global__ void __launch_bounds__(1024) k_bwd32_bf16(const int *__restrict__ tab
 // input rows are gathered through the by-output table:  part[chunk][k][c][b] = sum_i G[table[km(k)][i]][c] * S[i][b]
 // with c in {0,1}; both forms below run on the matrix cores.
 
-// bf16 form of the first-layer dW on the matrix cores.  Per 32-row tile the wave builds, in its own LDS region,
+// 16-bit form of the first-layer dW on the matrix cores.  Per 32-row tile the wave builds, in its own LDS region,
 //   A [32 rows][64]: column k*2+c = channel c of the row gathered through table[km(k)][row] (2 x bf16 = one dword
 //                    per (row, k); columns 54..63 are zero padding), row stride 33 dwords (conflict-free fill),
 //   B [32 rows][32]: the stationary dY rows,
 // and accumulates D[col][b] += sum_rows A[row][col] * B[row][b] with 4 x v_mfma_f32_32x32x16_bf16 (two 32-column
 // halves x two 16-row steps; both operands are read column-wise from LDS, as in k_gdw32_bf16).  All of a tile's
 // table reads are issued together, then all gathers: two memory latencies per tile, one tile per wave in flight.
+// The three kernels of the family (k_gdw_c32c2_bf16, k_gdw_bnapply_c32c2, k_gdw_c32c2_f32) are built from the c2_*
+// pieces below: one tile per wave, C2_WAVES waves per block, one slab of part per block (c2_slabs).
 constexpr int C2_WAVES = 8;
+
+// table entries of a tile: slot t covers offsets 2t (lanes 0..31) and 2t+1 (lanes 32..63); trow = the lane's row,
+// clamped to R - 1
+__device__ __forceinline__ void c2_fetch(const int *__restrict__ table, int mirror, int K, long long Rcap, long long trow,
+                                         int h, int (&nb)[14]) {
+#pragma unroll
+    for (int t = 0; t < 14; ++t) {
+        int k = 2 * t + h;
+        int kk = k < K ? k : K - 1;
+        nb[t] = table[(long long)(mirror ? K - 1 - kk : kk) * Rcap + trow];
+    }
+}
+
+// the fetched entries as gather rows: the row itself at the identity offset, -1 for no neighbour, a row past R or an
+// offset past K (k = 27 of slot 13 among them)
+__device__ __forceinline__ void c2_resolve(int K, int identity_k, long long trow, bool tlive, int h, int (&nb)[14]) {
+#pragma unroll
+    for (int t = 0; t < 14; ++t) {
+        int k = 2 * t + h;
+        int n = (k == identity_k) ? (int)trow : nb[t];
+        nb[t] = (tlive && k < K && n >= 0) ? n : -1;
+    }
+}
+
+// A image of a tile of 16-bit rows: row c, dword k = the gathered row's two channels or zero; k = 27 (h = 1, t = 13)
+// lands in the zero padding, which lanes 0..31 complete
+__device__ __forceinline__ void c2_fill_a(unsigned *myA, int c, int h, const int (&nb)[14], const unsigned (&xv)[14]) {
+#pragma unroll
+    for (int t = 0; t < 14; ++t) {
+        int k = 2 * t + h;
+        myA[c * 33 + k] = nb[t] >= 0 ? xv[t] : 0u;
+    }
+    if (h == 0) {
+#pragma unroll
+        for (int k = 28; k < 32; ++k) myA[c * 33 + k] = 0u;
+    }
+}
+
+// fragments A^T (columns of the [row][66 u16] image) and B (columns of the [row][32] image), then the 2 x 2 MFMA step
+template <typename H>
+__device__ __forceinline__ void c2_product(const unsigned *myA, const unsigned short *myB, int c, int h, f32x16 &acc0,
+                                           f32x16 &acc1) {
+    const unsigned short *A16 = reinterpret_cast<const unsigned short *>(myA);
+    unsigned wa[2][2][4], wb[2][4];
+#pragma unroll
+    for (int st = 0; st < 2; ++st)
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+            int r0 = 16 * st + 8 * h + 2 * m;
+            wa[0][st][m] = (unsigned)A16[r0 * 66 + c] | ((unsigned)A16[(r0 + 1) * 66 + c] << 16);
+            wa[1][st][m] = (unsigned)A16[r0 * 66 + 32 + c] | ((unsigned)A16[(r0 + 1) * 66 + 32 + c] << 16);
+            wb[st][m] = (unsigned)myB[r0 * 32 + c] | ((unsigned)myB[(r0 + 1) * 32 + c] << 16);
+        }
+#pragma unroll
+    for (int st = 0; st < 2; ++st) {
+        uint4 a_lo = {wa[0][st][0], wa[0][st][1], wa[0][st][2], wa[0][st][3]};
+        uint4 a_hi = {wa[1][st][0], wa[1][st][1], wa[1][st][2], wa[1][st][3]};
+        uint4 bb = {wb[st][0], wb[st][1], wb[st][2], wb[st][3]};
+        acc0 = mfma16<H>(a_lo, bb, acc0);
+        acc1 = mfma16<H>(a_hi, bb, acc1);
+    }
+}
+
+// deterministic block reduction in two halves (columns 0..31, 32..63): every wave parks its accumulator in
+// sRed [C2_WAVES][1024], then each thread adds output elements over the waves in wave order and writes
+// part[block][k][ch][b] = element ((2 k + ch) * 32 + b) for the first 2K columns
+__device__ __forceinline__ void c2_block_reduce(float *sRed, const f32x16 &acc0, const f32x16 &acc1, int c, int h, int wid,
+                                                int K, float *__restrict__ part) {
+    __syncthreads();
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            int col = (i & 3) + 8 * (i >> 2) + 4 * h;
+            sRed[wid * 1024 + col * 32 + c] = half ? acc1[i] : acc0[i];
+        }
+        __syncthreads();
+        for (int e = threadIdx.x; e < 1024; e += 512) {
+            float v = 0.f;
+#pragma unroll
+            for (int w = 0; w < C2_WAVES; ++w) v += sRed[w * 1024 + e];
+            const int ee = half * 1024 + e;
+            if (ee < K * 64) part[(long long)blockIdx.x * K * 64 + ee] = v;
+        }
+        __syncthreads();
+    }
+}
 
 template <typename H>
 __global__ void __launch_bounds__(512, 2) k_gdw_c32c2_bf16(const int *__restrict__ table, int mirror, int K,
@@ -1313,97 +1402,48 @@ __global__ void __launch_bounds__(512, 2) k_gdw_c32c2_bf16(const int *__restrict
     f32x16 acc0, acc1;
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc0[i] = acc1[i] = 0.f;
-    const unsigned *Gw = reinterpret_cast<const unsigned *>(G);          // one dword = the 2 bf16 channels of a row
+    const unsigned *Gw = reinterpret_cast<const unsigned *>(G);          // one dword = the 2 channels of an input row
     for (long long tile = (long long)blockIdx.x * C2_WAVES + wid; tile < ntiles; tile += (long long)gridDim.x * C2_WAVES) {
         const long long row0 = tile * 32;
-        // ---- table entries: slot t covers offsets 2t (lanes 0..31) and 2t+1 (lanes 32..63), row = lane & 31
         const long long trow = row0 + c < R ? row0 + c : R - 1;
-        const bool tlive = row0 + c < R;
         int nb[14];
-#pragma unroll
-        for (int t = 0; t < 14; ++t) {
-            int k = 2 * t + h;
-            int kk = k < K ? k : K - 1;
-            nb[t] = table[(long long)(mirror ? K - 1 - kk : kk) * Rcap + trow];
-        }
+        c2_fetch(table, mirror, K, Rcap, trow, h, nb);
         // ---- stationary rows (issued before the gathers' addresses are known)
         const long long ra = row0 + grow, rb = row0 + grow + 16;
         uint4 s0 = *(const uint4 *)(S + (ra < R ? ra : R - 1) * 32 + gchunk * 8);
         uint4 s1 = *(const uint4 *)(S + (rb < R ? rb : R - 1) * 32 + gchunk * 8);
+        c2_resolve(K, identity_k, trow, row0 + c < R, h, nb);
         unsigned xv[14];
 #pragma unroll
-        for (int t = 0; t < 14; ++t) {
-            int k = 2 * t + h;
-            int n = (k == identity_k) ? (int)trow : nb[t];
-            bool ok = tlive && k < K && n >= 0;
-            nb[t] = ok ? n : -1;
-            xv[t] = Gw[ok ? n : 0];
-        }
+        for (int t = 0; t < 14; ++t) xv[t] = Gw[nb[t] >= 0 ? nb[t] : 0];
         __builtin_amdgcn_wave_barrier();            // the previous tile's fragment reads are done (LDS is in order)
-#pragma unroll
-        for (int t = 0; t < 14; ++t) {
-            int k = 2 * t + h;
-            myA[c * 33 + k] = nb[t] >= 0 ? xv[t] : 0u;          // k = 27 (h = 1, t = 13) lands in the zero padding
-        }
-        if (h == 0) {
-#pragma unroll
-            for (int k = 28; k < 32; ++k) myA[c * 33 + k] = 0u;
-        }
+        c2_fill_a(myA, c, h, nb, xv);
         *(uint4 *)(myB + grow * 32 + gchunk * 8) = keep_if(s0, ra < R);
         *(uint4 *)(myB + (grow + 16) * 32 + gchunk * 8) = keep_if(s1, rb < R);
         __builtin_amdgcn_wave_barrier();
-        // ---- fragments: A^T (columns of the [row][66 u16] image), B (columns of the [row][32] image)
-        const unsigned short *A16 = reinterpret_cast<const unsigned short *>(myA);
-        unsigned wa[2][2][4], wb[2][4];
-#pragma unroll
-        for (int st = 0; st < 2; ++st)
-#pragma unroll
-            for (int m = 0; m < 4; ++m) {
-                int r0 = 16 * st + 8 * h + 2 * m;
-                wa[0][st][m] = (unsigned)A16[r0 * 66 + c] | ((unsigned)A16[(r0 + 1) * 66 + c] << 16);
-                wa[1][st][m] = (unsigned)A16[r0 * 66 + 32 + c] | ((unsigned)A16[(r0 + 1) * 66 + 32 + c] << 16);
-                wb[st][m] = (unsigned)myB[r0 * 32 + c] | ((unsigned)myB[(r0 + 1) * 32 + c] << 16);
-            }
-#pragma unroll
-        for (int st = 0; st < 2; ++st) {
-            uint4 a_lo = {wa[0][st][0], wa[0][st][1], wa[0][st][2], wa[0][st][3]};
-            uint4 a_hi = {wa[1][st][0], wa[1][st][1], wa[1][st][2], wa[1][st][3]};
-            uint4 bb = {wb[st][0], wb[st][1], wb[st][2], wb[st][3]};
-            acc0 = mfma16<H>(a_lo, bb, acc0);
-            acc1 = mfma16<H>(a_hi, bb, acc1);
-        }
+        c2_product<H>(myA, myB, c, h, acc0, acc1);
     }
-    // deterministic block reduction in two halves (offsets 0..15, 16..31): every wave parks its accumulator in the
-    // free A-staging area (8 x 4 KiB), then each thread adds output elements over the waves in wave order
-    __syncthreads();
-    float *sRed = reinterpret_cast<float *>(&sA[0][0]);                  // [C2_WAVES][1024] <= 8 x 32 x 33 words
-#pragma unroll
-    for (int half = 0; half < 2; ++half) {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            int col = (i & 3) + 8 * (i >> 2) + 4 * h;
-            sRed[wid * 1024 + col * 32 + c] = half ? acc1[i] : acc0[i];
-        }
-        __syncthreads();
-        // part[block][k][ch][b] = element (k*2 + ch, b) for the first 2K columns
-        for (int e = threadIdx.x; e < 1024; e += 512) {
-            float v = 0.f;
-#pragma unroll
-            for (int w = 0; w < C2_WAVES; ++w) v += sRed[w * 1024 + e];
-            const int ee = half * 1024 + e;
-            if (ee < K * 64) part[(long long)blockIdx.x * K * 64 + ee] = v;
-        }
-        __syncthreads();
-    }
+    // the free A-staging area holds the parked accumulators: [C2_WAVES][1024] floats <= 8 x 32 x 33 words
+    c2_block_reduce(reinterpret_cast<float *>(&sA[0][0]), acc0, acc1, c, h, wid, K, part);
+}
+
+// one element of the BatchNorm (+ ReLU) backward, dz = gamma invstd (g - k1 - xhat k2) with g masked by the forward's
+// sign.  bn.hip's k_bn_bwd_apply, k_bn_bwd_apply_rr and k_bnw_bwd_apply write the same expressions: keep the same
+// operations in the same order here and there
+__device__ __forceinline__ float c2_bn_dz(float x, float g, float m, float is, float ga, float be, float k1, float k2,
+                                          int relu) {
+    const float xh = (x - m) * is;
+    if (relu && !(fmaf(ga, xh, be) > 0.f)) g = 0.f;
+    return ga * is * (g - k1 - xh * k2);
 }
 
 // First layer followed by BatchNorm (+ ReLU), 16-bit rows (include/wfsparse.h wfs_first_conv_bn_backward): the BatchNorm
 // backward's elementwise pass inside k_gdw_c32c2_bf16.  The first layer has no dX, so dz = a (g - k1 - xhat k2) is needed
 // only as the stationary operand of this product: the kernel folds the reduce launch's partials in its prologue (the
 // order of bn.hip's fold_partials; block 0 publishes dbeta / dgamma), loads the tile's z rows beside its dY rows, forms
-// dz in registers with the expressions of bn.hip's k_bn_bwd_apply_rr, rounds it to the row type as that kernel's store
-// does, and puts it in the B image.  Same tiles, same grid, same slabs and summation orders as k_gdw_c32c2_bf16 on a
-// stored dz: the same bits, without the elementwise launch and the [R, 32] dz round trip.
+// dz in registers with c2_bn_dz, as bn.hip's k_bn_bwd_apply_rr does, rounds it to the row type as that kernel's store
+// does, and puts it in the B image.  The tile loop and the reduction are k_gdw_c32c2_bf16's own pieces, so on a stored dz
+// that kernel gives the same bits; this one saves the elementwise launch and the [R, 32] dz round trip.
 template <typename H>
 __global__ void __launch_bounds__(512, 2) k_gdw_bnapply_c32c2(const int *__restrict__ table, int mirror, int K,
                                                              int identity_k, long long Rcap,
@@ -1474,14 +1514,8 @@ __global__ void __launch_bounds__(512, 2) k_gdw_bnapply_c32c2(const int *__restr
     for (long long tile = (long long)blockIdx.x * C2_WAVES + wid; tile < ntiles; tile += (long long)gridDim.x * C2_WAVES) {
         const long long row0 = tile * 32;
         const long long trow = row0 + c < R ? row0 + c : R - 1;
-        const bool tlive = row0 + c < R;
         int nb[14];
-#pragma unroll
-        for (int t = 0; t < 14; ++t) {
-            int k = 2 * t + h;
-            int kk = k < K ? k : K - 1;
-            nb[t] = table[(long long)(mirror ? K - 1 - kk : kk) * Rcap + trow];
-        }
+        c2_fetch(table, mirror, K, Rcap, trow, h, nb);
         // ---- stationary rows of dY and z (issued before the gathers' addresses are known)
         const long long ra = row0 + grow, rb = row0 + grow + 16;
         const long long oa = (ra < R ? ra : R - 1) * 32 + gchunk * 8, ob = (rb < R ? rb : R - 1) * 32 + gchunk * 8;
@@ -1489,17 +1523,12 @@ __global__ void __launch_bounds__(512, 2) k_gdw_bnapply_c32c2(const int *__restr
         const uint4 s1 = *(const uint4 *)(S + ob);
         const uint4 z0 = *(const uint4 *)(Z + oa);
         const uint4 z1 = *(const uint4 *)(Z + ob);
+        c2_resolve(K, identity_k, trow, row0 + c < R, h, nb);
         unsigned xv[14];
 #pragma unroll
-        for (int t = 0; t < 14; ++t) {
-            int k = 2 * t + h;
-            int n = (k == identity_k) ? (int)trow : nb[t];
-            bool ok = tlive && k < K && n >= 0;
-            nb[t] = ok ? n : -1;
-            xv[t] = Gw[ok ? n : 0];
-        }
+        for (int t = 0; t < 14; ++t) xv[t] = Gw[nb[t] >= 0 ? nb[t] : 0];
         __builtin_amdgcn_wave_barrier();            // the previous tile's fragment reads are done (LDS is in order)
-        // ---- dz of the tile's rows, under the gathers' latency: k_bn_bwd_apply_rr's arithmetic and rounding
+        // ---- dz of the tile's rows, under the gathers' latency, rounded as k_bn_bwd_apply_rr's store rounds it
         {
             const unsigned zw[2][4] = {{z0.x, z0.y, z0.z, z0.w}, {z1.x, z1.y, z1.z, z1.w}};
             const unsigned gw[2][4] = {{s0.x, s0.y, s0.z, s0.w}, {s1.x, s1.y, s1.z, s1.w}};
@@ -1510,75 +1539,22 @@ __global__ void __launch_bounds__(512, 2) k_gdw_bnapply_c32c2(const int *__restr
                 const float4 ql = sQ[gchunk * 8 + 2 * j], qh = sQ[gchunk * 8 + 2 * j + 1];
 #pragma unroll
                 for (int half = 0; half < 2; ++half) {
-                    float xv2[2], gv2[2], o[2];
-                    wfs_unpack2<H>(zw[half][j], xv2[0], xv2[1]);
-                    wfs_unpack2<H>(gw[half][j], gv2[0], gv2[1]);
-#pragma unroll
-                    for (int e = 0; e < 2; ++e) {
-                        const float m = e ? ph.x : pl.x, is = e ? ph.y : pl.y, ga = e ? ph.z : pl.z, be = e ? ph.w : pl.w;
-                        const float k1 = e ? qh.x : ql.x, k2 = e ? qh.y : ql.y;
-                        float xh = (xv2[e] - m) * is;
-                        float gi = gv2[e];
-                        if (relu && !(fmaf(ga, xh, be) > 0.f)) gi = 0.f;
-                        o[e] = ga * is * (gi - k1 - xh * k2);
-                    }
-                    ow[half][j] = wfs_pack2<H>(o[0], o[1]);
+                    float zl, zh, gl, gh;
+                    wfs_unpack2<H>(zw[half][j], zl, zh);
+                    wfs_unpack2<H>(gw[half][j], gl, gh);
+                    ow[half][j] = wfs_pack2<H>(c2_bn_dz(zl, gl, pl.x, pl.y, pl.z, pl.w, ql.x, ql.y, relu),
+                                               c2_bn_dz(zh, gh, ph.x, ph.y, ph.z, ph.w, qh.x, qh.y, relu));
                 }
             }
             *(uint4 *)(myB + grow * 32 + gchunk * 8) = keep_if(make_uint4(ow[0][0], ow[0][1], ow[0][2], ow[0][3]), ra < R);
             *(uint4 *)(myB + (grow + 16) * 32 + gchunk * 8) = keep_if(make_uint4(ow[1][0], ow[1][1], ow[1][2], ow[1][3]), rb < R);
         }
-#pragma unroll
-        for (int t = 0; t < 14; ++t) {
-            int k = 2 * t + h;
-            myA[c * 33 + k] = nb[t] >= 0 ? xv[t] : 0u;          // k = 27 (h = 1, t = 13) lands in the zero padding
-        }
-        if (h == 0) {
-#pragma unroll
-            for (int k = 28; k < 32; ++k) myA[c * 33 + k] = 0u;
-        }
+        c2_fill_a(myA, c, h, nb, xv);
         __builtin_amdgcn_wave_barrier();
-        // ---- fragments: A^T (columns of the [row][66 u16] image), B (columns of the [row][32] image)
-        const unsigned short *A16 = reinterpret_cast<const unsigned short *>(myA);
-        unsigned wa[2][2][4], wb[2][4];
-#pragma unroll
-        for (int st = 0; st < 2; ++st)
-#pragma unroll
-            for (int m = 0; m < 4; ++m) {
-                int r0 = 16 * st + 8 * h + 2 * m;
-                wa[0][st][m] = (unsigned)A16[r0 * 66 + c] | ((unsigned)A16[(r0 + 1) * 66 + c] << 16);
-                wa[1][st][m] = (unsigned)A16[r0 * 66 + 32 + c] | ((unsigned)A16[(r0 + 1) * 66 + 32 + c] << 16);
-                wb[st][m] = (unsigned)myB[r0 * 32 + c] | ((unsigned)myB[(r0 + 1) * 32 + c] << 16);
-            }
-#pragma unroll
-        for (int st = 0; st < 2; ++st) {
-            uint4 a_lo = {wa[0][st][0], wa[0][st][1], wa[0][st][2], wa[0][st][3]};
-            uint4 a_hi = {wa[1][st][0], wa[1][st][1], wa[1][st][2], wa[1][st][3]};
-            uint4 bb = {wb[st][0], wb[st][1], wb[st][2], wb[st][3]};
-            acc0 = mfma16<H>(a_lo, bb, acc0);
-            acc1 = mfma16<H>(a_hi, bb, acc1);
-        }
+        c2_product<H>(myA, myB, c, h, acc0, acc1);
     }
-    // deterministic block reduction, as k_gdw_c32c2_bf16
-    __syncthreads();
-    float *sRed = reinterpret_cast<float *>(&sA[0][0]);                  // [C2_WAVES][1024] <= 8 x 32 x 33 words
-#pragma unroll
-    for (int half = 0; half < 2; ++half) {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            int col = (i & 3) + 8 * (i >> 2) + 4 * h;
-            sRed[wid * 1024 + col * 32 + c] = half ? acc1[i] : acc0[i];
-        }
-        __syncthreads();
-        for (int e = threadIdx.x; e < 1024; e += 512) {
-            float v = 0.f;
-#pragma unroll
-            for (int w = 0; w < C2_WAVES; ++w) v += sRed[w * 1024 + e];
-            const int ee = half * 1024 + e;
-            if (ee < K * 64) part[(long long)blockIdx.x * K * 64 + ee] = v;
-        }
-        __syncthreads();
-    }
+    // the free A-staging area holds the parked accumulators: [C2_WAVES][1024] floats <= 8 x 32 x 33 words
+    c2_block_reduce(reinterpret_cast<float *>(&sA[0][0]), acc0, acc1, c, h, wid, K, part);
 }
 
 // fp32 form of the first-layer dW on the matrix cores (exact fp32, v_mfma_f32_32x32x2_f32 with the tile's ROWS as the
@@ -1586,13 +1562,12 @@ __global__ void __launch_bounds__(512, 2) k_gdw_bnapply_c32c2(const int *__restr
 // A = Xg[2 s + h][col = c (+ 32)] and B = dY[2 s + h][b = c] -- the dY rows straight from global memory (whole 128-byte
 // rows), the gathered 2-channel rows through the tile's table entries, which are read coalesced and turned around
 // through a padded LDS image.  32 MFMAs per tile, one tile per wave, two memory round trips per tile.
-constexpr int C2F_WAVES = 8;
 __global__ void __launch_bounds__(512, 2) k_gdw_c32c2_f32(const int *__restrict__ table, int mirror, int K, int identity_k,
                                                          long long Rcap, const long long *__restrict__ r_dev,
                                                          const float *__restrict__ S, const float *__restrict__ G,
                                                          float *__restrict__ part) {
-    __shared__ int sNbT[C2F_WAVES][28 * 33];                     // [k][row], row stride 33: conflict-free both ways
-    __shared__ float sRed[C2F_WAVES][1024];
+    __shared__ int sNbT[C2_WAVES][28 * 33];                      // [k][row], row stride 33: conflict-free both ways
+    __shared__ float sRed[C2_WAVES][1024];
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const int c = lane & 31, h = lane >> 5;
     int *myNb = sNbT[wid];
@@ -1603,17 +1578,11 @@ __global__ void __launch_bounds__(512, 2) k_gdw_c32c2_f32(const int *__restrict_
     for (int i = 0; i < 16; ++i) acc0[i] = acc1[i] = 0.f;
     // the two columns this lane feeds: col0 = c (offset c >> 1), col1 = 32 + c (offset 16 + (c >> 1)), channel c & 1
     const int k0 = c >> 1, k1 = 16 + (c >> 1), ch = c & 1;
-    for (long long tile = (long long)blockIdx.x * C2F_WAVES + wid; tile < ntiles; tile += (long long)gridDim.x * C2F_WAVES) {
+    for (long long tile = (long long)blockIdx.x * C2_WAVES + wid; tile < ntiles; tile += (long long)gridDim.x * C2_WAVES) {
         const long long row0 = tile * 32;
         const long long trow = row0 + c < R ? row0 + c : R - 1;
-        const bool tlive = row0 + c < R;
         int nb[14];
-#pragma unroll
-        for (int t = 0; t < 14; ++t) {
-            const int k = 2 * t + h;
-            const int kk = k < K ? k : K - 1;
-            nb[t] = table[(long long)(mirror ? K - 1 - kk : kk) * Rcap + trow];
-        }
+        c2_fetch(table, mirror, K, Rcap, trow, h, nb);
         float bv[16];
 #pragma unroll
         for (int s2 = 0; s2 < 16; ++s2) {
@@ -1622,12 +1591,9 @@ __global__ void __launch_bounds__(512, 2) k_gdw_c32c2_f32(const int *__restrict_
             bv[s2] = row < R ? t : 0.f;
         }
         __builtin_amdgcn_wave_barrier();            // the previous tile's reads of the image are done (LDS is in order)
+        c2_resolve(K, identity_k, trow, row0 + c < R, h, nb);
 #pragma unroll
-        for (int t = 0; t < 14; ++t) {
-            const int k = 2 * t + h;
-            const int n = (k == identity_k) ? (int)trow : nb[t];
-            myNb[k * 33 + c] = (tlive && k < K && n >= 0) ? n : -1;       // k = 27 (h = 1, t = 13): never read as valid
-        }
+        for (int t = 0; t < 14; ++t) myNb[(2 * t + h) * 33 + c] = nb[t];          // k = 27 (h = 1, t = 13): never valid
         __builtin_amdgcn_wave_barrier();
         float x0[16], x1[16];
 #pragma unroll
@@ -1646,25 +1612,7 @@ __global__ void __launch_bounds__(512, 2) k_gdw_c32c2_f32(const int *__restrict_
             acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(x1[s2], bv[s2], acc1, 0, 0, 0);
         }
     }
-    // deterministic block reduction in two halves (columns 0..31, 32..63), waves added in wave order
-    __syncthreads();
-#pragma unroll
-    for (int half = 0; half < 2; ++half) {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const int col = (i & 3) + 8 * (i >> 2) + 4 * h;
-            sRed[wid][col * 32 + c] = half ? acc1[i] : acc0[i];
-        }
-        __syncthreads();
-        for (int e = threadIdx.x; e < 1024; e += 512) {
-            float v = 0.f;
-#pragma unroll
-            for (int w = 0; w < C2F_WAVES; ++w) v += sRed[w][e];
-            const int ee = half * 1024 + e;                       // = (2 k + ch) * 32 + b
-            if (ee < K * 64) part[(long long)blockIdx.x * K * 64 + ee] = v;
-        }
-        __syncthreads();
-    }
+    c2_block_reduce(&sRed[0][0], acc0, acc1, c, h, wid, K, part);
 }
 
 // dW[k][a][b] (swap==0) or dW[k][b][a] (swap==1) = sum over slabs of part[slab][k][a][b]; blockDim.x / 32 slab slices
@@ -1990,17 +1938,35 @@ static long long dw32_blocks(long long R, bool two_per_cu = false) {
     if (nblk > cap) nblk = cap;
     return nblk;
 }
-static long long dwc2_chunks(long long R) {
-    long long c = (R + 127) / 128;
-    if (c < 1) c = 1;
-    if (c > 512) c = 512;
-    return c;
+// slabs (= blocks) of the first-layer dW kernels: one 32-row tile per wave, at most 512 blocks
+static long long c2_slabs(long long R) {
+    const long long ntiles = (R + 31) >> 5;
+    const long long slabs = (ntiles + C2_WAVES - 1) / C2_WAVES;
+    return slabs > 512 ? 512 : (slabs < 1 ? 1 : slabs);
 }
 
 size_t wfs_dw_fast_workspace(int K, long long R, int Cs, int Cg) {
     if (Cs == 32 && Cg == 32) return (size_t)dw32_blocks(R, true) * K * 1024 * sizeof(float);   // the larger (fp32) grid
-    if (Cs == 32 && Cg == 2) return (size_t)dwc2_chunks(R) * K * 64 * sizeof(float);
+    if (Cs == 32 && Cg == 2) {
+        // ceil(R / 128) in 1 .. 512: an upper bound of c2_slabs(R) = ceil(ceil(R / 32) / 8), not the slab count itself;
+        // allocation sizes are behaviour, so the bound stays as it is
+        const long long bound = (R + 127) / 128;
+        return (size_t)(bound > 512 ? 512 : (bound < 1 ? 1 : bound)) * K * 64 * sizeof(float);
+    }
     return 0;
+}
+
+// second stage of a slab dW: handed to the caller's job list (wfs_launch_dw_jobs), or run now
+static int dw_reduce_or_defer(float *part, long long nslabs, long long per, int K, int A, int B, int transpose, float *dW,
+                              wfs_dw_job *defer, hipStream_t stream) {
+    if (defer) {
+        *defer = wfs_dw_job{part, nslabs, per, K, A, B, transpose, dW};
+        return WFS_OK;
+    }
+    k_slab_reduce<<<dim3((unsigned)((per + 31) / 32)), dim3(nslabs > 64 ? 1024 : 256), 0, stream>>>(part, nslabs, per, K, A, B,
+                                                                                                  transpose, dW);
+    WFS_LAUNCH_CHECK();
+    return WFS_OK;
 }
 
 int wfs_launch_gdw32(const int *table, int K, int identity_k, long long R, const long long *r_dev, const void *S,
@@ -2035,14 +2001,7 @@ int wfs_launch_gdw32(const int *table, int K, int identity_k, long long R, const
                                       tiles_per_block);
         if (rc != WFS_OK) return rc;
     }
-    const long long per = (long long)K * 1024;
-    if (defer) {
-        *defer = wfs_dw_job{part, nblk, per, K, 32, 32, swap, dW};
-        return WFS_OK;
-    }
-    k_slab_reduce<<<dim3((unsigned)((per + 31) / 32)), dim3(nblk > 64 ? 1024 : 256), 0, stream>>>(part, nblk, per, K, 32, 32, swap, dW);
-    WFS_LAUNCH_CHECK();
-    return WFS_OK;
+    return dw_reduce_or_defer(part, nblk, (long long)K * 1024, K, 32, 32, swap, dW, defer, stream);
 }
 
 // dW and dX of a 32 -> 32 layer with 16-bit rows in one launch (k_bwd32_bf16)
@@ -2124,76 +2083,43 @@ int wfs_launch_bwd32_h16(const int *table, int packed_kl, int K, int identity_k,
         rc = launch_bwd32_h16<wfs_bf16>(table, packed_kl, K, identity_k, R, r_dev, (const wfs_bf16 *)S, (const wfs_bf16 *)G,
                                         W, (wfs_bf16 *)dX, part, stream);
     if (rc != WFS_OK) return rc;
-    const long long nblk = dw32_blocks(R, false);
-    const long long per = (long long)K * 1024;
-    if (defer) {
-        *defer = wfs_dw_job{part, nblk, per, K, 32, 32, swap, dW};
-        return WFS_OK;
-    }
-    k_slab_reduce<<<dim3((unsigned)((per + 31) / 32)), dim3(nblk > 64 ? 1024 : 256), 0, stream>>>(part, nblk, per, K, 32, 32, swap, dW);
-    WFS_LAUNCH_CHECK();
-    return WFS_OK;
+    return dw_reduce_or_defer(part, dw32_blocks(R, false), (long long)K * 1024, K, 32, 32, swap, dW, defer, stream);
 }
 
 int wfs_launch_gdw_c32c2(const int *table, int mirror, int K, int identity_k, long long R, const long long *r_dev,
                          const void *S, const void *G, int swap, float *dW, float *part, int dtype,
                          wfs_dw_job *defer, hipStream_t stream) {
-    long long chunks = dwc2_chunks(R);
-    if (dtype == WFS_F32) {
-        const long long ntiles = (R + 31) >> 5;
-        chunks = (ntiles + C2F_WAVES - 1) / C2F_WAVES;        // one tile per wave, at most 512 blocks (= slabs)
-        if (chunks > 512) chunks = 512;
-        k_gdw_c32c2_f32<<<dim3((unsigned)chunks), dim3(512), 0, stream>>>(table, mirror, K, identity_k, R, r_dev,
-                                                                          (const float *)S, (const float *)G, part);
-    } else {
-        const long long ntiles = (R + 31) >> 5;
-        chunks = (ntiles + C2_WAVES - 1) / C2_WAVES;          // one tile per wave, at most 512 blocks (= slabs)
-        if (chunks > 512) chunks = 512;
-        if (dtype == WFS_BF16)
-            k_gdw_c32c2_bf16<wfs_bf16><<<dim3((unsigned)chunks), dim3(512), 0, stream>>>(
-                table, mirror, K, identity_k, R, r_dev, (const wfs_bf16 *)S, (const wfs_bf16 *)G, part);
-        else
-            k_gdw_c32c2_bf16<wfs_f16><<<dim3((unsigned)chunks), dim3(512), 0, stream>>>(
-                table, mirror, K, identity_k, R, r_dev, (const wfs_f16 *)S, (const wfs_f16 *)G, part);
-    }
+    const long long slabs = c2_slabs(R);
+    if (dtype == WFS_F32)
+        k_gdw_c32c2_f32<<<dim3((unsigned)slabs), dim3(512), 0, stream>>>(table, mirror, K, identity_k, R, r_dev,
+                                                                         (const float *)S, (const float *)G, part);
+    else if (dtype == WFS_BF16)
+        k_gdw_c32c2_bf16<wfs_bf16><<<dim3((unsigned)slabs), dim3(512), 0, stream>>>(
+            table, mirror, K, identity_k, R, r_dev, (const wfs_bf16 *)S, (const wfs_bf16 *)G, part);
+    else
+        k_gdw_c32c2_bf16<wfs_f16><<<dim3((unsigned)slabs), dim3(512), 0, stream>>>(
+            table, mirror, K, identity_k, R, r_dev, (const wfs_f16 *)S, (const wfs_f16 *)G, part);
     WFS_LAUNCH_CHECK();
-    // part is [chunk][k][c (gathered, 2)][b (stationary, 32)] = the "swap" orientation of (S=32, G=2)
-    const long long per = (long long)K * 64;
-    if (defer) {
-        *defer = wfs_dw_job{part, chunks, per, K, 2, 32, swap ? 0 : 1, dW};
-        return WFS_OK;
-    }
-    k_slab_reduce<<<dim3((unsigned)((per + 31) / 32)), dim3(chunks > 64 ? 1024 : 256), 0, stream>>>(part, chunks, per, K, 2, 32, swap ? 0 : 1, dW);
-    WFS_LAUNCH_CHECK();
-    return WFS_OK;
+    // part is [slab][k][c (gathered, 2)][b (stationary, 32)] = the "swap" orientation of (S=32, G=2)
+    return dw_reduce_or_defer(part, slabs, (long long)K * 64, K, 2, 32, swap ? 0 : 1, dW, defer, stream);
 }
 
-long long wfs_first_bn_slabs(long long R) {
-    const long long ntiles = (R + 31) >> 5;
-    long long chunks = (ntiles + C2_WAVES - 1) / C2_WAVES;          // as wfs_launch_gdw_c32c2: the same slabs
-    return chunks > 512 ? 512 : (chunks < 1 ? 1 : chunks);
-}
+long long wfs_first_bn_slabs(long long R) { return c2_slabs(R); }
 
 int wfs_launch_first_bn_bwd(const int *table, int mirror, int K, int identity_k, long long R, const long long *r_dev,
                             const void *Z, const void *dY, const void *X, const float *gamma, const float *beta,
                             const float *mean, const float *invstd, int relu, const float *partial, int nblk, float *dW,
                             float *dgamma, float *dbeta, float *part, int dtype, wfs_dw_job *defer, hipStream_t stream) {
-    const long long chunks = wfs_first_bn_slabs(R);
+    const long long slabs = c2_slabs(R);
     if (dtype == WFS_BF16)
-        k_gdw_bnapply_c32c2<wfs_bf16><<<dim3((unsigned)chunks), dim3(512), 0, stream>>>(
+        k_gdw_bnapply_c32c2<wfs_bf16><<<dim3((unsigned)slabs), dim3(512), 0, stream>>>(
             table, mirror, K, identity_k, R, r_dev, (const wfs_bf16 *)Z, (const wfs_bf16 *)dY, (const wfs_bf16 *)X, partial,
             nblk, mean, invstd, gamma, beta, relu, dgamma, dbeta, part);
     else
-        k_gdw_bnapply_c32c2<wfs_f16><<<dim3((unsigned)chunks), dim3(512), 0, stream>>>(
+        k_gdw_bnapply_c32c2<wfs_f16><<<dim3((unsigned)slabs), dim3(512), 0, stream>>>(
             table, mirror, K, identity_k, R, r_dev, (const wfs_f16 *)Z, (const wfs_f16 *)dY, (const wfs_f16 *)X, partial,
             nblk, mean, invstd, gamma, beta, relu, dgamma, dbeta, part);
     WFS_LAUNCH_CHECK();
-    const long long per = (long long)K * 64;          // part is [chunk][k][ci][co]: dW's own layout
-    if (defer) {
-        *defer = wfs_dw_job{part, chunks, per, K, 2, 32, 0, dW};
-        return WFS_OK;
-    }
-    k_slab_reduce<<<dim3((unsigned)((per + 31) / 32)), dim3(chunks > 64 ? 1024 : 256), 0, stream>>>(part, chunks, per, K, 2, 32, 0, dW);
-    WFS_LAUNCH_CHECK();
-    return WFS_OK;
+    // part is [slab][k][ci][co]: dW's own layout
+    return dw_reduce_or_defer(part, slabs, (long long)K * 64, K, 2, 32, 0, dW, defer, stream);
 }
