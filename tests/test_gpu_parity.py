@@ -200,11 +200,16 @@ def test_inverse_conv_and_rulebook_reuse():
     assert np.array_equal(outids.cpu().numpy(), o) and spatial == list(shape)
 
 
-@pytest.mark.parametrize("subm", [True, False], ids=["subm", "conv"])
-def test_duplicate_coordinates_follow_the_cpu_semantics(subm):
-    """Duplicate sites: SubM's hash keeps the last row, regular conv adds both rows (A.3/A.4)."""
+@pytest.mark.parametrize("subm,dtype,tol", [(True, torch.float32, 1e-5), (False, torch.float32, 1e-5),
+                                            (False, torch.bfloat16, 2e-2), (False, torch.float16, 3e-3)],
+                         ids=["subm", "conv", "conv-bf16", "conv-f16"])
+def test_duplicate_coordinates_follow_the_cpu_semantics(subm, dtype, tol):
+    """Duplicate sites: SubM's hash keeps the last row, regular conv adds both rows (A.3/A.4).  The conv case runs the
+    scatter kernels; with 16-bit rows the oracle gets the same rounded rows and the tolerances of
+    test_conv_bf16_storage_against_fp32_oracle apply."""
     case = (2, (7, 6), 3, 1 if subm else 2, 0 if subm else 1, 1, subm)
-    layer, ref_layer, xg, xr, rng = _conv_pair(case, 4, 6, 40, 2, 606)
+    layer, ref_layer, xg, xr, rng = _conv_pair(case, 4, 6, 40, 2, 606, dtype=dtype)
+    xr.features = xr.features.detach().to(dtype).float().requires_grad_(True)     # same rounded inputs
     idx = xr.indices.numpy().copy()
     idx[31] = idx[30]
     idx[12] = idx[11]
@@ -212,13 +217,13 @@ def test_duplicate_coordinates_follow_the_cpu_semantics(subm):
     xr.indices = torch.from_numpy(idx)
     xg.indices = torch.from_numpy(idx).to(DEV)
     yg, yr = layer(xg), ref_layer(xr)
-    assert np.array_equal(yg.indices.cpu().numpy(), yr.indices.numpy())
-    _assert_close(yg.features.detach().cpu().numpy(), yr.features.detach().numpy(), 1e-5, "dup forward")
-    g = rng.standard_normal(tuple(yr.features.shape)).astype(np.float32)
-    yr.features.backward(torch.from_numpy(g))
-    yg.features.backward(torch.from_numpy(g).to(DEV))
-    _assert_close(xg.features.grad.cpu().numpy(), xr.features.grad.numpy(), 1e-5, "dup dX")
-    _assert_close(layer.weight.grad.cpu().numpy(), ref_layer.weight.grad.numpy(), 1e-5, "dup dW")
+    assert np.array_equal(yg.indices.cpu().numpy(), yr.indices.numpy()) and yg.features.dtype == dtype
+    _assert_close(yg.features.detach().float().cpu().numpy(), yr.features.detach().numpy(), tol, "dup forward")
+    g = torch.from_numpy(rng.standard_normal(tuple(yr.features.shape)).astype(np.float32)).to(dtype)
+    yr.features.backward(g.float())
+    yg.features.backward(g.to(DEV))
+    _assert_close(xg.features.grad.float().cpu().numpy(), xr.features.grad.numpy(), tol, "dup dX")
+    _assert_close(layer.weight.grad.cpu().numpy(), ref_layer.weight.grad.numpy(), tol, "dup dW")
 
 
 def test_to_dense_and_backward():

@@ -58,7 +58,7 @@ def test_values_come_from_the_second_tensor_and_mask_from_the_first():
     assert np.array_equal(idx.cpu().numpy(), c3[:, [3, 0, 1, 2]])
 
 
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16], ids=["f32", "bf16", "f16"])
 def test_device_count_mode_ignores_stale_padding_rows(dtype):
     E, T = 256, 1024
     c2, f2, c3, f3 = _layouts(E, T)
@@ -160,7 +160,7 @@ def test_event_table_equals_event_offsets_of_the_voxels(n_valid):
     assert int(events[E + 4:].abs().sum()) == 0
 
 
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16], ids=["f32", "bf16", "f16"])
 @pytest.mark.parametrize("T", [150, 1024])
 def test_backward_is_the_exact_scatter_and_zero_elsewhere(T, dtype):
     E = 64

@@ -23,11 +23,7 @@ namespace {
 constexpr int TB = 256;
 constexpr int MAXC = 1024;
 
-// N = capacity (grid sizing); the number of valid rows comes from device memory when n_dev is given
-__device__ __forceinline__ long long valid_rows(long long N, const long long *n_dev) {
-    long long v = n_dev ? *n_dev : N;
-    return v < N ? v : N;
-}
+// N = capacity (grid sizing); the number of valid rows comes from device memory when n_dev is given (wfs_valid_rows)
 
 // thread layout of a block: (row slot, channel group of VEC channels); VEC = 4 when C % 4 == 0, else 1
 template <typename T, int VEC>
@@ -68,7 +64,7 @@ __global__ void __launch_bounds__(TB) k_bn_reduce(const T *__restrict__ X, const
                                                   const float *__restrict__ beta, int relu,
                                                   float *__restrict__ partial) {
     __shared__ float red[2][TB][VEC];
-    const long long N = valid_rows(Ncap, n_dev);
+    const long long N = wfs_valid_rows(Ncap, n_dev);
     const int groups = C / VEC, slots = TB / groups;
     const int grp = threadIdx.x % groups, slot = threadIdx.x / groups;
     const int c0 = grp * VEC;
@@ -201,7 +197,7 @@ __global__ void __launch_bounds__(TB) k_bn_apply(const T *__restrict__ X, long l
                                                  const float *__restrict__ partial, int nblk) {
     __shared__ float sSlice[2 * TB];
     __shared__ float sA[MAXC], sB[MAXC];
-    const long long N = valid_rows(Ncap, n_dev);
+    const long long N = wfs_valid_rows(Ncap, n_dev);
     if (partial) {
         fold_partials(partial, nblk, C, sSlice, sA, sB);
         const float n = N > 0 ? (float)N : 1.f;
@@ -278,7 +274,7 @@ __global__ void __launch_bounds__(TB) k_bn_bwd_apply(const T *__restrict__ X, co
                                                      float *__restrict__ dgamma, float *__restrict__ dbeta) {
     __shared__ float sSlice[2 * TB];
     __shared__ float sA[MAXC], sB[MAXC];
-    const long long N = valid_rows(Ncap, n_dev);
+    const long long N = wfs_valid_rows(Ncap, n_dev);
     fold_partials(partial, nblk, C, sSlice, sA, sB);
     if (blockIdx.x == 0) {
         for (int c = threadIdx.x; c < C; c += TB) {
@@ -423,7 +419,7 @@ __global__ void __launch_bounds__(TB) k_bn_reduce_rr(const T *__restrict__ X, co
         x[i].load(X + rc * C + c0);
         if (MODE == 1) g[i].load(dY + rc * C + c0);
     }
-    const long long N = valid_rows(Ncap, n_dev);                 // in flight together with the rows
+    const long long N = wfs_valid_rows(Ncap, n_dev);             // in flight together with the rows
     float m[VEC], is[VEC], ga[VEC], be[VEC], sa[VEC], sb[VEC];
     if (MODE == 0) {
         load_vec<T, VEC>(X + c0, m);                             // the shift: row 0
@@ -498,7 +494,7 @@ __global__ void __launch_bounds__(TB) k_bn_apply_rr(const T *__restrict__ X, lon
         const long long r = first + i * stride;
         x[i].load(X + (((WFS_BN_KNOCK & 2) || !(active && r < Ncap)) ? 0 : r) * C + c0);
     }
-    const long long N = valid_rows(Ncap, n_dev);
+    const long long N = wfs_valid_rows(Ncap, n_dev);
     float ga[VEC], be[VEC];
 #pragma unroll
     for (int i = 0; i < VEC; ++i) {
@@ -581,7 +577,7 @@ __global__ void __launch_bounds__(TB) k_bn_bwd_apply_rr(const T *__restrict__ X,
         x[i].load(X + rc * C + c0);
         g[i].load(dY + rc * C + c0);
     }
-    const long long N = valid_rows(Ncap, n_dev);
+    const long long N = wfs_valid_rows(Ncap, n_dev);
     float m[VEC], is[VEC], ga[VEC], be[VEC];
 #pragma unroll
     for (int i = 0; i < VEC; ++i) {
@@ -701,7 +697,7 @@ __global__ void __launch_bounds__(TB) k_bnw_reduce(const T *__restrict__ X, cons
                                                    const float *__restrict__ gamma, const float *__restrict__ beta,
                                                    int relu, float *__restrict__ partial) {
     __shared__ float red[2][TB];
-    const long long N = valid_rows(Ncap, n_dev);
+    const long long N = wfs_valid_rows(Ncap, n_dev);
     const int lane = threadIdx.x & (BW_COLS - 1), slot = threadIdx.x / BW_COLS;
     const int c = blockIdx.x * BW_COLS + lane;
     const bool ok = c < C;
@@ -774,7 +770,7 @@ __global__ void __launch_bounds__(TB) k_bnw_apply(const T *__restrict__ X, long 
                                                   const float *__restrict__ partial, int nch) {
     __shared__ float red[2][TB];
     __shared__ float tot[2][BW_COLS];
-    const long long N = valid_rows(Ncap, n_dev);
+    const long long N = wfs_valid_rows(Ncap, n_dev);
     const int lane = threadIdx.x & (BW_COLS - 1), slot = threadIdx.x / BW_COLS;
     const int c = blockIdx.x * BW_COLS + lane;
     const bool ok = c < C;
@@ -831,7 +827,7 @@ __global__ void __launch_bounds__(TB) k_bnw_bwd_apply(const T *__restrict__ X, c
                                                       float *__restrict__ dbeta) {
     __shared__ float red[2][TB];
     __shared__ float tot[2][BW_COLS];
-    const long long N = valid_rows(Ncap, n_dev);
+    const long long N = wfs_valid_rows(Ncap, n_dev);
     const int lane = threadIdx.x & (BW_COLS - 1), slot = threadIdx.x / BW_COLS;
     const int c = blockIdx.x * BW_COLS + lane;
     const bool ok = c < C;
@@ -916,49 +912,39 @@ static int bn_fwd_slice(const void *X, int64_t N, int32_t C, long long ld, const
         const int per = rr_plan(N, C, 16, &rb);
         if (per) {
             const dim3 g2((unsigned)rb);
-#define WFS_BN_FWD_RR(T, PER)                                                                                          \
-    do {                                                                                                               \
-        k_bn_reduce_rr<T, PER, 0><<<g2, block, 0, stream>>>((const T *)X, nullptr, N, n_dev, C, nullptr, nullptr,      \
-                                                             nullptr, nullptr, 0, partial);                            \
-        k_bn_apply_rr<T, PER><<<g2, block, 0, stream>>>(                                                               \
-            (const T *)X, N, n_dev, C, gamma, beta, running_mean, running_var, (long long *)num_batches_tracked,       \
-            momentum, eps, relu, (T *)Y, save_mean, save_invstd, partial, (int)rb);                                    \
-    } while (0)
-#define WFS_BN_FWD_RR_T(T)                                                                                             \
-    if (per == 2) WFS_BN_FWD_RR(T, 2); else if (per == 4) WFS_BN_FWD_RR(T, 4); else if (per == 8) WFS_BN_FWD_RR(T, 8);   \
-    else WFS_BN_FWD_RR(T, 16)
-            if (dtype == WFS_F32) { WFS_BN_FWD_RR_T(float); } else if (dtype == WFS_BF16) { WFS_BN_FWD_RR_T(wfs_bf16); } else { WFS_BN_FWD_RR_T(wfs_f16); }
-#undef WFS_BN_FWD_RR_T
-#undef WFS_BN_FWD_RR
-            WFS_LAUNCH_CHECK();
-            return WFS_OK;
+            return wfs_with_dtype(dtype, [&](auto t) -> int {
+                using T = decltype(t);
+                return wfs_with_int<2, 4, 8, 16>(per, [&](auto per_c) -> int {
+                    constexpr int PER = decltype(per_c)::value;
+                    k_bn_reduce_rr<T, PER, 0><<<g2, block, 0, stream>>>((const T *)X, nullptr, N, n_dev, C, nullptr, nullptr,
+                                                                         nullptr, nullptr, 0, partial);
+                    k_bn_apply_rr<T, PER><<<g2, block, 0, stream>>>(
+                        (const T *)X, N, n_dev, C, gamma, beta, running_mean, running_var, (long long *)num_batches_tracked,
+                        momentum, eps, relu, (T *)Y, save_mean, save_invstd, partial, (int)rb);
+                    WFS_LAUNCH_CHECK();
+                    return WFS_OK;
+                });
+            });
         }
     }
-#define WFS_BN_FWD(T, VEC)                                                                                          \
-    do {                                                                                                            \
-        if (training)                                                                                               \
-            k_bn_reduce<T, VEC, 0><<<grid, block, 0, stream>>>((const T *)X, nullptr, N, n_dev, C, ld, rpb, nullptr, \
-                                                                nullptr, nullptr, nullptr, 0, partial);             \
-        k_bn_apply<T, VEC><<<grid_a, block, 0, stream>>>(                                                           \
-            (const T *)X, N, n_dev, C, ld, rpb_a, gamma, beta, running_mean, running_var,                           \
-            (long long *)num_batches_tracked, momentum, eps, training, relu, (T *)Y, save_mean, save_invstd,        \
-            training ? partial : nullptr, (int)nblk);                                                               \
-    } while (0)
-    if (dtype == WFS_F32) {
-        if (vec4) WFS_BN_FWD(float, 4); else WFS_BN_FWD(float, 1);
-    } else if (dtype == WFS_BF16) {
-        if (vec4) WFS_BN_FWD(wfs_bf16, 4); else WFS_BN_FWD(wfs_bf16, 1);
-    } else {
-        if (vec4) WFS_BN_FWD(wfs_f16, 4); else WFS_BN_FWD(wfs_f16, 1);
-    }
-#undef WFS_BN_FWD
-    WFS_LAUNCH_CHECK();
-    return WFS_OK;
+    return wfs_with_dtype(dtype, [&](auto t) -> int {
+        using T = decltype(t);
+        return wfs_with_int<4, 1>(vec4 ? 4 : 1, [&](auto vec_c) -> int {
+            constexpr int VEC = decltype(vec_c)::value;
+            if (training)
+                k_bn_reduce<T, VEC, 0><<<grid, block, 0, stream>>>((const T *)X, nullptr, N, n_dev, C, ld, rpb, nullptr,
+                                                                    nullptr, nullptr, nullptr, 0, partial);
+            k_bn_apply<T, VEC><<<grid_a, block, 0, stream>>>(
+                (const T *)X, N, n_dev, C, ld, rpb_a, gamma, beta, running_mean, running_var,
+                (long long *)num_batches_tracked, momentum, eps, training, relu, (T *)Y, save_mean, save_invstd,
+                training ? partial : nullptr, (int)nblk);
+            WFS_LAUNCH_CHECK();
+            return WFS_OK;
+        });
+    });
 }
 
 // layers wider than one block's reach (MAXC channels; the hybrid net's first layers have 2 T = 2048) run slice by slice
-static inline size_t elem_bytes(int dtype) { return dtype == WFS_F32 ? 4 : 2; }
-
 extern "C" int wfs_bn_relu_fwd(const void *X, int64_t N, int32_t C, const float *gamma, const float *beta,
                                float *running_mean, float *running_var, int64_t *num_batches_tracked, float momentum,
                                float eps, int32_t training, int32_t relu, void *Y, float *save_mean,
@@ -971,14 +957,10 @@ extern "C" int wfs_bn_relu_fwd(const void *X, int64_t N, int32_t C, const float 
         WFS_REQUIRE(X && Y && save_mean && save_invstd && workspace, WFS_EINVAL, "NULL device pointer");
         WFS_REQUIRE(workspace_bytes >= wfs_bn_workspace_bytes(N, C), WFS_EWORKSPACE, "workspace too small");
         float *partial = (float *)workspace;
-        if (dtype == WFS_F32)
-            return bw_fwd<float>(X, N, C, gamma, beta, running_mean, running_var, num_batches_tracked, momentum, eps,
-                                 training, relu, Y, save_mean, save_invstd, partial, n_dev, stream);
-        if (dtype == WFS_BF16)
-            return bw_fwd<wfs_bf16>(X, N, C, gamma, beta, running_mean, running_var, num_batches_tracked, momentum, eps,
-                                    training, relu, Y, save_mean, save_invstd, partial, n_dev, stream);
-        return bw_fwd<wfs_f16>(X, N, C, gamma, beta, running_mean, running_var, num_batches_tracked, momentum, eps,
-                               training, relu, Y, save_mean, save_invstd, partial, n_dev, stream);
+        return wfs_with_dtype(dtype, [&](auto t) -> int {
+            return bw_fwd<decltype(t)>(X, N, C, gamma, beta, running_mean, running_var, num_batches_tracked, momentum, eps,
+                                       training, relu, Y, save_mean, save_invstd, partial, n_dev, stream);
+        });
     }
     if (C <= (C % 4 == 0 ? MAXC : TB))
         return bn_fwd_slice(X, N, C, C, gamma, beta, running_mean, running_var, num_batches_tracked, momentum, eps,
@@ -987,7 +969,7 @@ extern "C" int wfs_bn_relu_fwd(const void *X, int64_t N, int32_t C, const float 
     const int width = C % 4 == 0 ? MAXC : TB;          // odd widths: scalar path, one channel per thread
     for (int c0 = 0; c0 < C; c0 += width) {
         const int cs = C - c0 < width ? C - c0 : width;
-        const size_t off = (size_t)c0 * elem_bytes(dtype);
+        const size_t off = (size_t)c0 * wfs_dtype_bytes(dtype);
         int rc = bn_fwd_slice(X ? (const char *)X + off : nullptr, N, cs, C, gamma ? gamma + c0 : nullptr,
                               beta ? beta + c0 : nullptr, running_mean ? running_mean + c0 : nullptr,
                               running_var ? running_var + c0 : nullptr, c0 == 0 ? num_batches_tracked : nullptr,
@@ -1022,42 +1004,34 @@ static int bn_bwd_slice(const void *X, const void *dY, int64_t N, int32_t C, lon
         const int per = rr_plan(N, C, dtype == WFS_F32 ? 8 : 16, &rb);
         if (per) {
             const dim3 g2((unsigned)rb);
-#define WFS_BN_BWD_RR(T, PER)                                                                                          \
-    do {                                                                                                               \
-        k_bn_reduce_rr<T, PER, 1><<<g2, block, 0, stream>>>((const T *)X, (const T *)dY, N, n_dev, C, save_mean,       \
-                                                             save_invstd, gamma, beta, relu, partial);                 \
-        k_bn_bwd_apply_rr<T, PER><<<g2, block, 0, stream>>>((const T *)X, (const T *)dY, N, n_dev, C, partial, (int)rb, \
-                                                            save_mean, save_invstd, gamma, beta, training, relu,       \
-                                                            (T *)dX, dgamma, dbeta);                                   \
-    } while (0)
-#define WFS_BN_BWD_RR_T(T)                                                                                             \
-    if (per == 2) WFS_BN_BWD_RR(T, 2); else if (per == 4) WFS_BN_BWD_RR(T, 4); else if (per == 8) WFS_BN_BWD_RR(T, 8);   \
-    else WFS_BN_BWD_RR(T, 16)
-            if (dtype == WFS_F32) { WFS_BN_BWD_RR_T(float); } else if (dtype == WFS_BF16) { WFS_BN_BWD_RR_T(wfs_bf16); } else { WFS_BN_BWD_RR_T(wfs_f16); }
-#undef WFS_BN_BWD_RR_T
-#undef WFS_BN_BWD_RR
-            WFS_LAUNCH_CHECK();
-            return WFS_OK;
+            return wfs_with_dtype(dtype, [&](auto t) -> int {
+                using T = decltype(t);
+                return wfs_with_int<2, 4, 8, 16>(per, [&](auto per_c) -> int {
+                    constexpr int PER = decltype(per_c)::value;
+                    k_bn_reduce_rr<T, PER, 1><<<g2, block, 0, stream>>>((const T *)X, (const T *)dY, N, n_dev, C, save_mean,
+                                                                         save_invstd, gamma, beta, relu, partial);
+                    k_bn_bwd_apply_rr<T, PER><<<g2, block, 0, stream>>>((const T *)X, (const T *)dY, N, n_dev, C, partial,
+                                                                        (int)rb, save_mean, save_invstd, gamma, beta,
+                                                                        training, relu, (T *)dX, dgamma, dbeta);
+                    WFS_LAUNCH_CHECK();
+                    return WFS_OK;
+                });
+            });
         }
     }
-#define WFS_BN_BWD(T, VEC)                                                                                          \
-    do {                                                                                                            \
-        k_bn_reduce<T, VEC, 1><<<grid, block, 0, stream>>>((const T *)X, (const T *)dY, N, n_dev, C, ld, rpb, save_mean, \
-                                                            save_invstd, gamma, beta, relu, partial);               \
-        k_bn_bwd_apply<T, VEC><<<grid_a, block, 0, stream>>>((const T *)X, (const T *)dY, N, n_dev, C, ld, rpb_a, partial, \
-                                                              (int)nblk, save_mean, save_invstd, gamma, beta,       \
-                                                              training, relu, (T *)dX, dgamma, dbeta);              \
-    } while (0)
-    if (dtype == WFS_F32) {
-        if (vec4) WFS_BN_BWD(float, 4); else WFS_BN_BWD(float, 1);
-    } else if (dtype == WFS_BF16) {
-        if (vec4) WFS_BN_BWD(wfs_bf16, 4); else WFS_BN_BWD(wfs_bf16, 1);
-    } else {
-        if (vec4) WFS_BN_BWD(wfs_f16, 4); else WFS_BN_BWD(wfs_f16, 1);
-    }
-#undef WFS_BN_BWD
-    WFS_LAUNCH_CHECK();
-    return WFS_OK;
+    return wfs_with_dtype(dtype, [&](auto t) -> int {
+        using T = decltype(t);
+        return wfs_with_int<4, 1>(vec4 ? 4 : 1, [&](auto vec_c) -> int {
+            constexpr int VEC = decltype(vec_c)::value;
+            k_bn_reduce<T, VEC, 1><<<grid, block, 0, stream>>>((const T *)X, (const T *)dY, N, n_dev, C, ld, rpb, save_mean,
+                                                                save_invstd, gamma, beta, relu, partial);
+            k_bn_bwd_apply<T, VEC><<<grid_a, block, 0, stream>>>((const T *)X, (const T *)dY, N, n_dev, C, ld, rpb_a, partial,
+                                                                  (int)nblk, save_mean, save_invstd, gamma, beta,
+                                                                  training, relu, (T *)dX, dgamma, dbeta);
+            WFS_LAUNCH_CHECK();
+            return WFS_OK;
+        });
+    });
 }
 
 // The FIRST launch of wfs_bn_relu_bwd alone (the sums of g and g * xhat as per-block partials), with the kernel and the
@@ -1071,32 +1045,27 @@ int wfs_launch_bn_bwd_reduce(const void *X, const void *dY, long long N, int C, 
     const int per = rr_plan(N, C, dtype == WFS_F32 ? 8 : 16, &rb);
     if (per) {
         const dim3 g2((unsigned)rb);
-#define WFS_BN_RED_RR(T, PER)                                                                                          \
-    k_bn_reduce_rr<T, PER, 1><<<g2, block, 0, stream>>>((const T *)X, (const T *)dY, N, n_dev, C, save_mean,           \
-                                                         save_invstd, gamma, beta, relu, partial)
-#define WFS_BN_RED_RR_T(T)                                                                                             \
-    if (per == 2) WFS_BN_RED_RR(T, 2); else if (per == 4) WFS_BN_RED_RR(T, 4); else if (per == 8) WFS_BN_RED_RR(T, 8);   \
-    else WFS_BN_RED_RR(T, 16)
-        if (dtype == WFS_F32) { WFS_BN_RED_RR_T(float); } else if (dtype == WFS_BF16) { WFS_BN_RED_RR_T(wfs_bf16); } else { WFS_BN_RED_RR_T(wfs_f16); }
-#undef WFS_BN_RED_RR_T
-#undef WFS_BN_RED_RR
         *nblk_out = (int)rb;
-    } else {
-        const long long nblk = bn_reduce_blocks(N, C), rpb = wfs_cdiv(N, nblk);
-        const dim3 grid((unsigned)nblk);
-        if (dtype == WFS_F32)
-            k_bn_reduce<float, 4, 1><<<grid, block, 0, stream>>>((const float *)X, (const float *)dY, N, n_dev, C, C, rpb,
-                                                                 save_mean, save_invstd, gamma, beta, relu, partial);
-        else if (dtype == WFS_BF16)
-            k_bn_reduce<wfs_bf16, 4, 1><<<grid, block, 0, stream>>>((const wfs_bf16 *)X, (const wfs_bf16 *)dY, N, n_dev, C, C,
-                                                                    rpb, save_mean, save_invstd, gamma, beta, relu, partial);
-        else
-            k_bn_reduce<wfs_f16, 4, 1><<<grid, block, 0, stream>>>((const wfs_f16 *)X, (const wfs_f16 *)dY, N, n_dev, C, C,
-                                                                   rpb, save_mean, save_invstd, gamma, beta, relu, partial);
-        *nblk_out = (int)nblk;
+        return wfs_with_dtype(dtype, [&](auto t) -> int {
+            using T = decltype(t);
+            return wfs_with_int<2, 4, 8, 16>(per, [&](auto per_c) -> int {
+                k_bn_reduce_rr<T, decltype(per_c)::value, 1><<<g2, block, 0, stream>>>(
+                    (const T *)X, (const T *)dY, N, n_dev, C, save_mean, save_invstd, gamma, beta, relu, partial);
+                WFS_LAUNCH_CHECK();
+                return WFS_OK;
+            });
+        });
     }
-    WFS_LAUNCH_CHECK();
-    return WFS_OK;
+    const long long nblk = bn_reduce_blocks(N, C), rpb = wfs_cdiv(N, nblk);
+    const dim3 grid((unsigned)nblk);
+    *nblk_out = (int)nblk;
+    return wfs_with_dtype(dtype, [&](auto t) -> int {
+        using T = decltype(t);
+        k_bn_reduce<T, 4, 1><<<grid, block, 0, stream>>>((const T *)X, (const T *)dY, N, n_dev, C, C, rpb, save_mean,
+                                                         save_invstd, gamma, beta, relu, partial);
+        WFS_LAUNCH_CHECK();
+        return WFS_OK;
+    });
 }
 
 extern "C" int wfs_bn_relu_bwd(const void *X, const void *dY, int64_t N, int32_t C, const float *gamma,
@@ -1109,14 +1078,10 @@ extern "C" int wfs_bn_relu_bwd(const void *X, const void *dY, int64_t N, int32_t
         WFS_REQUIRE(X && dY && dX && save_mean && save_invstd && workspace, WFS_EINVAL, "NULL device pointer");
         WFS_REQUIRE(workspace_bytes >= wfs_bn_workspace_bytes(N, C), WFS_EWORKSPACE, "workspace too small");
         float *partial = (float *)workspace;
-        if (dtype == WFS_F32)
-            return bw_bwd<float>(X, dY, N, C, gamma, beta, save_mean, save_invstd, training, relu, dX, dgamma, dbeta,
-                                 partial, n_dev, stream);
-        if (dtype == WFS_BF16)
-            return bw_bwd<wfs_bf16>(X, dY, N, C, gamma, beta, save_mean, save_invstd, training, relu, dX, dgamma, dbeta,
-                                    partial, n_dev, stream);
-        return bw_bwd<wfs_f16>(X, dY, N, C, gamma, beta, save_mean, save_invstd, training, relu, dX, dgamma, dbeta,
-                               partial, n_dev, stream);
+        return wfs_with_dtype(dtype, [&](auto t) -> int {
+            return bw_bwd<decltype(t)>(X, dY, N, C, gamma, beta, save_mean, save_invstd, training, relu, dX, dgamma, dbeta,
+                                       partial, n_dev, stream);
+        });
     }
     if (C <= (C % 4 == 0 ? MAXC : TB))
         return bn_bwd_slice(X, dY, N, C, C, gamma, beta, save_mean, save_invstd, training, relu, dX, dgamma, dbeta,
@@ -1125,7 +1090,7 @@ extern "C" int wfs_bn_relu_bwd(const void *X, const void *dY, int64_t N, int32_t
     const int width = C % 4 == 0 ? MAXC : TB;          // odd widths: scalar path, one channel per thread
     for (int c0 = 0; c0 < C; c0 += width) {
         const int cs = C - c0 < width ? C - c0 : width;
-        const size_t off = (size_t)c0 * elem_bytes(dtype);
+        const size_t off = (size_t)c0 * wfs_dtype_bytes(dtype);
         int rc = bn_bwd_slice(X ? (const char *)X + off : nullptr, dY ? (const char *)dY + off : nullptr, N, cs, C,
                               gamma ? gamma + c0 : nullptr, beta ? beta + c0 : nullptr,
                               save_mean ? save_mean + c0 : nullptr, save_invstd ? save_invstd + c0 : nullptr, training,

@@ -60,11 +60,6 @@ struct Plan {
     int n;
 };
 
-__device__ __forceinline__ long long valid_rows(long long N, const long long *n_dev) {
-    long long v = n_dev ? *n_dev : N;
-    v = v < N ? v : N;
-    return v > 0 ? v : 0;
-}
 
 // Sums of the per-block partials [nblk][nv] (nv <= 2 MAXC) into tot[nv], computed by EVERY block in the same order:
 // slice s adds partials s, s + S, ...; the slices are then added in slice order.
@@ -190,7 +185,7 @@ __global__ void __launch_bounds__(TB) k_c1d_fwd(FwdArgs a, const Conv1dPtrs *__r
         Ws[i] = co < ly.cout ? p.w[(long long)co * ck + (i - (i / ck) * ck)] : 0.f;
     }
     if (threadIdx.x < CH) Bs[threadIdx.x] = (p.b && co0 + threadIdx.x < ly.cout) ? p.b[co0 + threadIdx.x] : 0.f;
-    const long long Nv = valid_rows(N, n_dev);
+    const long long Nv = wfs_valid_rows_nonneg(N, n_dev);
     if (a.has_prev)
         bn_prologue(pp[a.layer - 1], ly.cin, a.pstat, a.pnblk, Nv * ly.lin, training, a.pmom, a.peps, a.pstats_out,
                     blockIdx.x == 0 && blockIdx.y == 0, sl, tot, bn);
@@ -250,7 +245,7 @@ __global__ void __launch_bounds__(TB) k_c1d_out(const float *__restrict__ Z, int
                                                 long long N, const long long *__restrict__ n_dev, int training) {
     __shared__ BnLds bn;
     __shared__ double sl[TB], tot[2 * MAXC];
-    const long long Nv = valid_rows(N, n_dev);
+    const long long Nv = wfs_valid_rows_nonneg(N, n_dev);
     bn_prologue(pp[layer], C, stat, nblk, Nv * L, training, momentum, eps, stats_out, blockIdx.x == 0, sl, tot, bn);
     const long long total = N * C * L, per = (long long)C * L;
     for (long long i = (long long)blockIdx.x * TB + threadIdx.x; i < total; i += (long long)gridDim.x * TB) {
@@ -281,7 +276,7 @@ __global__ void __launch_bounds__(TB) k_c1d_bwd_head(const void *__restrict__ dY
         bn.be[threadIdx.x] = p.be[threadIdx.x];
     }
     __syncthreads();
-    const long long Nv = valid_rows(N, n_dev);
+    const long long Nv = wfs_valid_rows_nonneg(N, n_dev);
     const int c0 = blockIdx.y * CH;
     double s[CH], q[CH];
 #pragma unroll
@@ -350,7 +345,7 @@ __global__ void __launch_bounds__(TB) k_c1d_bwd(BwdArgs a, const Conv1dPtrs *__r
     __shared__ double sl[TB], tot[2 * MAXC], red[TB / 64][2 * CH];
     const Layer ly = a.ly;
     const Conv1dPtrs p = pp[a.layer];
-    const long long Nv = valid_rows(N, n_dev);
+    const long long Nv = wfs_valid_rows_nonneg(N, n_dev);
     // ---- both roles: layer i's sums, dz_i = coef (g - k1 - xhat k2)
     fold(a.gstat, a.gnblk, 2 * ly.cout, sl, tot);
     if (threadIdx.x < ly.cout) {

@@ -574,9 +574,7 @@ __global__ void __launch_bounds__(TB) k_densify(const T *__restrict__ rows, cons
                                                 T *__restrict__ out) {
     __shared__ int first[MAXHW], count[MAXHW];
     const int b = blockIdx.x, x = blockIdx.y;
-    long long n = n_dev ? *n_dev : n_cap;
-    n = n < n_cap ? n : n_cap;
-    n = n > 0 ? n : 0;
+    const long long n = wfs_valid_rows_nonneg(n_cap, n_dev);
     if (threadIdx.x < MAXHW) {
         first[threadIdx.x] = 0x7FFFFFFF;
         count[threadIdx.x] = 0;
@@ -665,8 +663,7 @@ int check_common(int32_t c0, const int32_t *channels, const int32_t *fs, const i
     return WFS_OK;
 }
 
-int es_of(int dtype) { return dtype == WFS_F32 ? 4 : 2; }
-size_t as_floats(size_t elems, int dtype) { return ((elems * es_of(dtype) + 7) / 8) * 2; }     // 8-byte granules
+size_t as_floats(size_t elems, int dtype) { return ((elems * wfs_dtype_bytes(dtype) + 7) / 8) * 2; }     // 8-byte granules
 int row_blocks(long long M, int cap) {
     long long b = (M + 4 * RL - 1) / (4 * RL);
     return (int)(b < 1 ? 1 : (b > cap ? cap : b));
@@ -762,12 +759,10 @@ void launch_gemm(const GemmArgs &a, const Conv2dPtrs *pp, int nz, hipStream_t st
 }
 template <int MODE>
 void launch_gemm_dt(int dtype, const GemmArgs &a, const Conv2dPtrs *pp, int nz, hipStream_t stream) {
-    if (dtype == WFS_F32)
-        launch_gemm<float, MODE>(a, pp, nz, stream);
-    else if (dtype == WFS_BF16)
-        launch_gemm<wfs_bf16, MODE>(a, pp, nz, stream);
-    else
-        launch_gemm<wfs_f16, MODE>(a, pp, nz, stream);
+    wfs_with_dtype(dtype, [&](auto t) -> int {
+        launch_gemm<decltype(t), MODE>(a, pp, nz, stream);
+        return WFS_OK;
+    });
 }
 
 void launch_pack(int dtype, const Plan &pl, const size_t *layer_off, const Conv2dPtrs *pp, void *out, void *out_lo,
@@ -844,7 +839,7 @@ extern "C" int wfs_conv2d_fwd(const void *X, int64_t B, int32_t H, int32_t W, in
     WFS_REQUIRE(X && param_ptrs && saved && Y, WFS_EINVAL, "NULL device pointer");
     const SavedLayout sl = saved_layout(pl, B, dtype);
     const Conv2dPtrs *pp = (const Conv2dPtrs *)param_ptrs;
-    const int es = es_of(dtype);
+    const int es = wfs_dtype_bytes(dtype);
     char *wf = (char *)(saved + sl.wf);
     const bool split = dtype != WFS_F32;
     char *wf_lo = (char *)(saved + sl.wf_lo);
@@ -914,7 +909,7 @@ extern "C" int wfs_conv2d_bwd(const void *X, const void *dY, int64_t B, int32_t 
     const SavedLayout sl = saved_layout(pl, B, dtype);
     const WorkLayout wl = work_layout(pl, B, dtype);
     const Conv2dPtrs *pp = (const Conv2dPtrs *)param_ptrs;
-    const int es = es_of(dtype);
+    const int es = wfs_dtype_bytes(dtype);
     char *wt = (char *)(workspace + wl.wt);
     launch_pack(dtype, pl, wl.wt_layer, pp, wt, nullptr, nullptr, 1, stream);
     WFS_LAUNCH_CHECK();
@@ -1002,14 +997,10 @@ extern "C" int wfs_densify_rows(const void *rows, const int32_t *coords, int64_t
     WFS_REQUIRE(out && (n_cap == 0 || (rows && coords)), WFS_EINVAL, "NULL device pointer");
     const dim3 grid((unsigned)B, (unsigned)H);
     const long long *n_dev = (const long long *)n_valid_dev;
-    if (dtype == WFS_F32)
-        k_densify<float><<<grid, dim3(TB), 0, stream>>>((const float *)rows, coords, n_cap, C, H, W, n_dev, (float *)out);
-    else if (dtype == WFS_BF16)
-        k_densify<wfs_bf16><<<grid, dim3(TB), 0, stream>>>((const wfs_bf16 *)rows, coords, n_cap, C, H, W, n_dev,
-                                                          (wfs_bf16 *)out);
-    else
-        k_densify<wfs_f16><<<grid, dim3(TB), 0, stream>>>((const wfs_f16 *)rows, coords, n_cap, C, H, W, n_dev,
-                                                         (wfs_f16 *)out);
-    WFS_LAUNCH_CHECK();
-    return WFS_OK;
+    return wfs_with_dtype(dtype, [&](auto t) -> int {
+        using T = decltype(t);
+        k_densify<T><<<grid, dim3(TB), 0, stream>>>((const T *)rows, coords, n_cap, C, H, W, n_dev, (T *)out);
+        WFS_LAUNCH_CHECK();
+        return WFS_OK;
+    });
 }

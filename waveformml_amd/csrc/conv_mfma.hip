@@ -26,11 +26,7 @@ struct KMap {
     int v[128];
 };
 
-// R = capacity (strides, grid); the number of valid rows comes from device memory when r_dev is given
-__device__ __forceinline__ long long valid_rows(long long R, const long long *r_dev) {
-    long long v = r_dev ? *r_dev : R;
-    return v < R ? v : R;
-}
+// R = capacity (strides, grid); the number of valid rows comes from device memory when r_dev is given (wfs_valid_rows)
 
 // Packed by-input tables (evconv.hip; include/wfsparse.h "packed tables"): where the kernel is no longer than the
 // stride along the last dimension an input row reaches at most ONE output cell per leading offset q, so the table is
@@ -184,7 +180,7 @@ __device__ __forceinline__ void gconv16_f32_body(float *sW, int *sNextp, int vbi
     // XCD-aware: blocks with equal blockIdx % 8 share an L2 and take one contiguous range of the VALID tiles; inside it
     // block bi owns tiles bi, bi + bpx, ... (consecutive tiles -- one event's, alike in cost -- go to different CUs)
     const int xcd = vbid & 7, bi = vbid >> 3, bpx = vgrid >> 3;
-    const long long Rv = valid_rows(R, r_dev);
+    const long long Rv = wfs_valid_rows(R, r_dev);
     const long long nt_v = (Rv + 15) >> 4, tpx_v = (nt_v + 7) >> 3;
     const long long t_begin = (long long)xcd * tpx_v;
     const long long t_end = t_begin + tpx_v < nt_v ? t_begin + tpx_v : nt_v;
@@ -500,7 +496,7 @@ __device__ __forceinline__ void gconv32_bf16_body(unsigned char *smem, int vbid,
     int *myNb = sNb + (size_t)wid * K * 32;
     // tile ranges per XCD cut from the VALID tiles (see k_gconv32_f32): the padding of a captured step costs nothing
     const int xcd = vbid & 7, bi = vbid >> 3, bpx = vgrid >> 3;
-    const long long Rv = valid_rows(R, r_dev);
+    const long long Rv = wfs_valid_rows(R, r_dev);
     const long long nt_v = (Rv + 31) >> 5, tpx_v = (nt_v + 7) >> 3;
     (void)ntiles;
     (void)tiles_per_xcd;
@@ -632,7 +628,7 @@ __global__ void __launch_bounds__(256) k_gconv_c2c32(const int *__restrict__ tab
     const int rsub = threadIdx.x >> 3, cq = threadIdx.x & 7;
     f32x4 bv = {0.f, 0.f, 0.f, 0.f};
     if (bias) bv = *(const f32x4 *)(bias + cq * 4);
-    const long long Rv = valid_rows(R, r_dev);
+    const long long Rv = wfs_valid_rows(R, r_dev);
     for (long long row = (long long)blockIdx.x * 32 + rsub; row < Rv; row += (long long)gridDim.x * 32) {
         f32x4 acc = bv;
         for (int k = 0; k < K; ++k) {
@@ -681,7 +677,7 @@ __device__ __forceinline__ void gdw32_body(float *sRed, int bx, int by, int nbx,
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const int j = lane & 31, h = lane >> 5;
     const int g = by;
-    const long long R = valid_rows(Rcap, r_dev);            // rows to process; Rcap stays the table stride
+    const long long R = wfs_valid_rows(Rcap, r_dev);        // rows to process; Rcap stays the table stride
     const long long ntiles = (R + 31) >> 5;
     static_assert(sizeof(T) == 4, "fp32 rows");
     // raw buffers (stride 0, byte offsets): S holds R valid rows of 128 B; G is addressed below 2 GiB, anything at or
@@ -800,7 +796,7 @@ __global__ void __launch_bounds__(256) k_gconv_c2c32_f32(const int *__restrict__
 #pragma unroll
     for (int k = 0; k < 27; ++k) wreg[k] = k < K ? W[((long long)k * 2 + h) * 32 + r] : 0.f;
     const float bj = bias ? bias[r] : 0.f;
-    const long long Rv = valid_rows(R, r_dev);
+    const long long Rv = wfs_valid_rows(R, r_dev);
     const long long ntiles = (Rv + 31) >> 5;
     for (long long tile = (long long)blockIdx.x * nw + wid; tile < ntiles; tile += (long long)gridDim.x * nw) {
         const long long row = tile * 32 + r;
@@ -867,7 +863,7 @@ __global__ void __launch_bounds__(256) k_gconv_c2c32_bf16(const int *__restrict_
     __syncthreads();
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const int r = lane & 31, h = lane >> 5;
-    const long long Rv = valid_rows(R, r_dev);
+    const long long Rv = wfs_valid_rows(R, r_dev);
     const long long ntiles = (Rv + 31) >> 5;
     const float bj = bias ? bias[r] : 0.f;
     const unsigned *Xw = reinterpret_cast<const unsigned *>(X);
@@ -967,7 +963,7 @@ __device__ __forceinline__ void gdw32_bf16_body(unsigned char *smem, int bx, int
     const int grow = lane >> 2, gchunk = lane & 3;   // staging coordinates: rows grow and grow+16, 16-B chunk gchunk
     unsigned short *sS = sTiles[wid][0], *sG = sTiles[wid][1];
     const int g = by;
-    const long long R = valid_rows(Rcap, r_dev);            // rows to process; Rcap stays the table stride
+    const long long R = wfs_valid_rows(Rcap, r_dev);        // rows to process; Rcap stays the table stride
     const long long ntiles = (R + 31) >> 5;
     // cut from the VALID tiles (not the capacity): the padding of a captured step costs nothing
     const long long tpb = (ntiles + nbx - 1) / nbx;
@@ -1092,7 +1088,7 @@ __device__ __forceinline__ void gdw32_split_body(unsigned char *smem, int bx, in
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const int c = lane & 31, h = lane >> 5;          // fragment coordinates
     const int srow = lane >> 3, chunk = lane & 7;    // staging coordinates: rows srow + 8 p, 16-B chunk (4 floats)
-    const long long R = valid_rows(Rcap, r_dev);
+    const long long R = wfs_valid_rows(Rcap, r_dev);
     const long long ntiles = (R + 31) >> 5;
     const __amdgpu_buffer_rsrc_t rsrcS = __builtin_amdgcn_make_buffer_rsrc((void *)S, 0, (int)(R * 128), 0x00020000);
     const __amdgpu_buffer_rsrc_t rsrcG = __builtin_amdgcn_make_buffer_rsrc((void *)G, 0, 0x7FFFFFFF, 0x00020000);
@@ -1397,7 +1393,7 @@ __global__ void __launch_bounds__(512, 2) k_gdw_c32c2_bf16(const int *__restrict
     const int grow = lane >> 2, gchunk = lane & 3;
     unsigned *myA = sA[wid];
     unsigned short *myB = sB[wid];
-    const long long R = valid_rows(Rcap, r_dev);
+    const long long R = wfs_valid_rows(Rcap, r_dev);
     const long long ntiles = (R + 31) >> 5;
     f32x16 acc0, acc1;
 #pragma unroll
@@ -1464,7 +1460,7 @@ __global__ void __launch_bounds__(512, 2) k_gdw_bnapply_c32c2(const int *__restr
     const int grow = lane >> 2, gchunk = lane & 3;
     unsigned *myA = sA[wid];
     unsigned short *myB = sB[wid];
-    const long long R = valid_rows(Rcap, r_dev);
+    const long long R = wfs_valid_rows(Rcap, r_dev);
     // ---- the sums of g and g * xhat from the reduce launch's partials [nblk][2][32], as fold_partials of bn.hip adds
     // them with 256 threads: slice sl = 0..7 owns partials sl, sl + 8, ... (at most 32, all asked for before the first
     // add), then the slices in slice order
@@ -1571,7 +1567,7 @@ __global__ void __launch_bounds__(512, 2) k_gdw_c32c2_f32(const int *__restrict_
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const int c = lane & 31, h = lane >> 5;
     int *myNb = sNbT[wid];
-    const long long R = valid_rows(Rcap, r_dev);
+    const long long R = wfs_valid_rows(Rcap, r_dev);
     const long long ntiles = (R + 31) >> 5;
     f32x16 acc0, acc1;
 #pragma unroll
@@ -1886,17 +1882,13 @@ int wfs_launch_gconv_c2c32(const int *table, const int *kmap, int K, int identit
                            const long long *r_dev, const void *X, const float *W, const float *bias, void *Y, int dtype,
                            hipStream_t stream) {
     KMap km;
-    bool is_ident = true, is_mirror = true;
-    for (int k = 0; k < K; ++k) {
-        km.v[k] = kmap ? kmap[k] : k;
-        is_ident = is_ident && km.v[k] == k;
-        is_mirror = is_mirror && km.v[k] == K - 1 - k;
-    }
-    if (dtype != WFS_F32 && K <= 32 && (is_ident || is_mirror)) {
+    for (int k = 0; k < K; ++k) km.v[k] = kmap ? kmap[k] : k;
+    const int kind = wfs_kmap_kind(kmap, K);
+    const int mir = kind == WFS_KMAP_MIRROR;
+    if (dtype != WFS_F32 && K <= 32 && kind != WFS_KMAP_OTHER) {
         long long nb = ((R + 31) / 32 + 3) / 4;              // one 32-row tile per wave, 4 waves per block
         if (nb > 4096) nb = 4096;
         const dim3 grid((unsigned)nb), block(256);
-        const int mir = is_ident ? 0 : 1;
         if (dtype == WFS_F16)
             k_gconv_c2c32_bf16<wfs_f16><<<grid, block, 0, stream>>>(table, mir, K, identity_k, R, r_dev, (const wfs_f16 *)X, W,
                                                                     bias, (wfs_f16 *)Y);
@@ -1906,27 +1898,23 @@ int wfs_launch_gconv_c2c32(const int *table, const int *kmap, int K, int identit
         WFS_LAUNCH_CHECK();
         return WFS_OK;
     }
-    if (dtype == WFS_F32 && K <= 27 && (is_ident || is_mirror)) {
+    if (dtype == WFS_F32 && K <= 27 && kind != WFS_KMAP_OTHER) {
         long long nb = ((R + 31) / 32 + 3) / 4;              // one 32-row tile per wave, 4 waves per block
         if (nb > 4096) nb = 4096;
-        k_gconv_c2c32_f32<<<dim3((unsigned)nb), dim3(256), 0, stream>>>(table, is_ident ? 0 : 1, K, identity_k, R, r_dev,
-                                                                        (const float *)X, W, bias, (float *)Y);
+        k_gconv_c2c32_f32<<<dim3((unsigned)nb), dim3(256), 0, stream>>>(table, mir, K, identity_k, R, r_dev, (const float *)X,
+                                                                        W, bias, (float *)Y);
         WFS_LAUNCH_CHECK();
         return WFS_OK;
     }
     long long nblk = (R + 31) / 32;
     if (nblk > 8192) nblk = 8192;
-    if (dtype == WFS_F32)
-        k_gconv_c2c32<float><<<dim3((unsigned)nblk), dim3(256), 0, stream>>>(table, km, K, identity_k, R, r_dev,
-                                                                            (const float *)X, W, bias, (float *)Y);
-    else if (dtype == WFS_BF16)
-        k_gconv_c2c32<wfs_bf16><<<dim3((unsigned)nblk), dim3(256), 0, stream>>>(
-            table, km, K, identity_k, R, r_dev, (const wfs_bf16 *)X, W, bias, (wfs_bf16 *)Y);
-    else
-        k_gconv_c2c32<wfs_f16><<<dim3((unsigned)nblk), dim3(256), 0, stream>>>(
-            table, km, K, identity_k, R, r_dev, (const wfs_f16 *)X, W, bias, (wfs_f16 *)Y);
-    WFS_LAUNCH_CHECK();
-    return WFS_OK;
+    return wfs_with_dtype(dtype, [&](auto t) -> int {
+        using T = decltype(t);
+        k_gconv_c2c32<T><<<dim3((unsigned)nblk), dim3(256), 0, stream>>>(table, km, K, identity_k, R, r_dev, (const T *)X, W,
+                                                                        bias, (T *)Y);
+        WFS_LAUNCH_CHECK();
+        return WFS_OK;
+    });
 }
 
 // slabs for the 32x32 dW: blocks over rows; returns the slab count through *nslabs
@@ -1988,17 +1976,13 @@ int wfs_launch_gdw32(const int *table, int K, int identity_k, long long R, const
         k_gdw32<float><<<grid, dim3(512), 0, stream>>>(table, packed_kl, K, identity_k, R, r_dev, (const float *)S,
                                                        (const float *)G, part, ngroups, tiles_per_block);
         WFS_LAUNCH_CHECK();
-    } else if (dtype == WFS_BF16) {
-        static bool attr = false;
-        const int rc = launch_big_lds(k_gdw32_bf16<wfs_bf16>, &attr, grid, dim3(1024), DWB_LDS, stream, table, packed_kl, K,
-                                      identity_k, R, r_dev, (const wfs_bf16 *)S, (const wfs_bf16 *)G, part, ngroups,
-                                      tiles_per_block);
-        if (rc != WFS_OK) return rc;
     } else {
-        static bool attr = false;
-        const int rc = launch_big_lds(k_gdw32_bf16<wfs_f16>, &attr, grid, dim3(1024), DWB_LDS, stream, table, packed_kl, K,
-                                      identity_k, R, r_dev, (const wfs_f16 *)S, (const wfs_f16 *)G, part, ngroups,
-                                      tiles_per_block);
+        const int rc = wfs_with_h16(dtype, [&](auto t) -> int {
+            using H = decltype(t);
+            static bool attr = false;               // one per instantiation, i.e. per H
+            return launch_big_lds(k_gdw32_bf16<H>, &attr, grid, dim3(1024), DWB_LDS, stream, table, packed_kl, K, identity_k,
+                                  R, r_dev, (const H *)S, (const H *)G, part, ngroups, tiles_per_block);
+        });
         if (rc != WFS_OK) return rc;
     }
     return dw_reduce_or_defer(part, nblk, (long long)K * 1024, K, 32, 32, swap, dW, defer, stream);
@@ -2093,12 +2077,13 @@ int wfs_launch_gdw_c32c2(const int *table, int mirror, int K, int identity_k, lo
     if (dtype == WFS_F32)
         k_gdw_c32c2_f32<<<dim3((unsigned)slabs), dim3(512), 0, stream>>>(table, mirror, K, identity_k, R, r_dev,
                                                                          (const float *)S, (const float *)G, part);
-    else if (dtype == WFS_BF16)
-        k_gdw_c32c2_bf16<wfs_bf16><<<dim3((unsigned)slabs), dim3(512), 0, stream>>>(
-            table, mirror, K, identity_k, R, r_dev, (const wfs_bf16 *)S, (const wfs_bf16 *)G, part);
     else
-        k_gdw_c32c2_bf16<wfs_f16><<<dim3((unsigned)slabs), dim3(512), 0, stream>>>(
-            table, mirror, K, identity_k, R, r_dev, (const wfs_f16 *)S, (const wfs_f16 *)G, part);
+        wfs_with_h16(dtype, [&](auto t) -> int {
+            using H = decltype(t);
+            k_gdw_c32c2_bf16<H><<<dim3((unsigned)slabs), dim3(512), 0, stream>>>(table, mirror, K, identity_k, R, r_dev,
+                                                                                (const H *)S, (const H *)G, part);
+            return WFS_OK;
+        });
     WFS_LAUNCH_CHECK();
     // part is [slab][k][c (gathered, 2)][b (stationary, 32)] = the "swap" orientation of (S=32, G=2)
     return dw_reduce_or_defer(part, slabs, (long long)K * 64, K, 2, 32, swap ? 0 : 1, dW, defer, stream);
@@ -2111,15 +2096,15 @@ int wfs_launch_first_bn_bwd(const int *table, int mirror, int K, int identity_k,
                             const float *mean, const float *invstd, int relu, const float *partial, int nblk, float *dW,
                             float *dgamma, float *dbeta, float *part, int dtype, wfs_dw_job *defer, hipStream_t stream) {
     const long long slabs = c2_slabs(R);
-    if (dtype == WFS_BF16)
-        k_gdw_bnapply_c32c2<wfs_bf16><<<dim3((unsigned)slabs), dim3(512), 0, stream>>>(
-            table, mirror, K, identity_k, R, r_dev, (const wfs_bf16 *)Z, (const wfs_bf16 *)dY, (const wfs_bf16 *)X, partial,
-            nblk, mean, invstd, gamma, beta, relu, dgamma, dbeta, part);
-    else
-        k_gdw_bnapply_c32c2<wfs_f16><<<dim3((unsigned)slabs), dim3(512), 0, stream>>>(
-            table, mirror, K, identity_k, R, r_dev, (const wfs_f16 *)Z, (const wfs_f16 *)dY, (const wfs_f16 *)X, partial,
-            nblk, mean, invstd, gamma, beta, relu, dgamma, dbeta, part);
-    WFS_LAUNCH_CHECK();
+    const int rc = wfs_with_h16(dtype, [&](auto t) -> int {
+        using H = decltype(t);
+        k_gdw_bnapply_c32c2<H><<<dim3((unsigned)slabs), dim3(512), 0, stream>>>(
+            table, mirror, K, identity_k, R, r_dev, (const H *)Z, (const H *)dY, (const H *)X, partial, nblk, mean, invstd,
+            gamma, beta, relu, dgamma, dbeta, part);
+        WFS_LAUNCH_CHECK();
+        return WFS_OK;
+    });
+    if (rc != WFS_OK) return rc;
     // part is [slab][k][ci][co]: dW's own layout
     return dw_reduce_or_defer(part, slabs, (long long)K * 64, K, 2, 32, 0, dW, defer, stream);
 }

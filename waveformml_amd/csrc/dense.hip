@@ -25,16 +25,12 @@ __device__ __forceinline__ long long cell_of(const Shape &s, const int *row, int
     return pos;
 }
 
-// M = capacity (grid); the number of valid rows comes from device memory when m_dev is given
-__device__ __forceinline__ long long valid_rows(long long M, const long long *m_dev) {
-    long long v = m_dev ? *m_dev : M;
-    return v < M ? v : M;
-}
+// M = capacity (grid); the number of valid rows comes from device memory when m_dev is given (wfs_valid_rows)
 
 __global__ void k_dense_winner(Shape s, const int *__restrict__ idx, long long M, const long long *m_dev,
                                int *__restrict__ winner) {
     long long m = (long long)blockIdx.x * TB + threadIdx.x;
-    if (m >= valid_rows(M, m_dev)) return;
+    if (m >= wfs_valid_rows(M, m_dev)) return;
     int b;
     long long pos = cell_of(s, idx + m * (s.ndim + 1), b);
     atomicMax(&winner[(long long)b * s.volume + pos], (int)m);
@@ -44,7 +40,7 @@ template <typename T>
 __global__ void k_to_dense(Shape s, const T *__restrict__ X, const int *__restrict__ idx, long long M,
                            const long long *m_dev, int C, const int *__restrict__ winner, T *__restrict__ Y) {
     long long e = (long long)blockIdx.x * TB + threadIdx.x;
-    if (e >= valid_rows(M, m_dev) * C) return;
+    if (e >= wfs_valid_rows(M, m_dev) * C) return;
     long long m = e / C;
     int c = (int)(e % C);
     int b;
@@ -57,7 +53,7 @@ template <typename T>
 __global__ void k_to_dense_bwd(Shape s, const T *__restrict__ dY, const int *__restrict__ idx, long long M,
                                const long long *m_dev, int C, T *__restrict__ dX) {
     long long e = (long long)blockIdx.x * TB + threadIdx.x;
-    if (e >= valid_rows(M, m_dev) * C) return;
+    if (e >= wfs_valid_rows(M, m_dev) * C) return;
     long long m = e / C;
     int c = (int)(e % C);
     int b;
@@ -89,7 +85,7 @@ __global__ void __launch_bounds__(TB) k_to_dense_mapped(const T *__restrict__ X,
     constexpr int WORDS = DM_CELLS / PACK;                // words per channel and tile
     extern __shared__ unsigned sT[];                      // [C][WORDS + 1]
     __shared__ int sRow[DM_CELLS];
-    const long long Mv = valid_rows(M, m_dev);
+    const long long Mv = wfs_valid_rows(M, m_dev);
     const long long b = blockIdx.y, p0 = (long long)blockIdx.x * DM_CELLS;
     if (threadIdx.x < DM_CELLS) {
         const long long p = p0 + threadIdx.x;
@@ -143,7 +139,7 @@ __global__ void __launch_bounds__(TB) k_to_dense_bwd_mapped(const T *__restrict_
     constexpr int WORDS = DM_CELLS / PACK;
     extern __shared__ unsigned sT[];
     __shared__ int sRow[DM_CELLS];
-    const long long Mv = valid_rows(M, m_dev);
+    const long long Mv = wfs_valid_rows(M, m_dev);
     const long long b = blockIdx.y, p0 = (long long)blockIdx.x * DM_CELLS;
     if (threadIdx.x < DM_CELLS) {
         const long long p = p0 + threadIdx.x;

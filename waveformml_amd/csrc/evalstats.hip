@@ -30,7 +30,7 @@ constexpr int EB = 256;                      // 4 waves per event
 constexpr int EW = EB / WFS_WAVE;
 constexpr int NPART = 9;
 
-#include "wfs_evoffsets.h"                   // valid_rows, k_eval_offsets (shared with segstats.hip)
+#include "wfs_evoffsets.h"                   // k_eval_offsets (shared with segstats.hip)
 static_assert(EB == WFS_EVOFF_THREADS, "k_eval_offsets is launched with EB threads");
 #include "wfs_evalbins.h"                   // bin_metric, bin_confusion, add64 (shared with metricpairs.hip)
 
@@ -107,7 +107,7 @@ k_event_stats(const int *__restrict__ coords, const T *__restrict__ rows, int Ts
     float *raw = reinterpret_cast<float *>(smem + EW * W);      // [EW][W] the row a wave is working on
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int e = blockIdx.x;
-    const long long nv = valid_rows(n_cap, n_dev);
+    const long long nv = wfs_valid_rows_nonneg(n_cap, n_dev);
     long long b = off[e], en = off[e + 1];
     b = b < 0 ? 0 : (b > nv ? nv : b);
     en = en < 0 ? 0 : (en > nv ? nv : en);
@@ -422,19 +422,14 @@ extern "C" int wfs_event_pulse_stats(const int32_t *coords, const void *rows, in
     k_eval_offsets<<<rb, EB, 0, s>>>(coords, n_cap, (const long long *)n_dev, E, offsets, flags);
     WFS_LAUNCH_CHECK();
     const size_t lds = stats_lds_bytes(T);
-#define WFS_EVSTATS(TYPE)                                                                                             \
-    k_event_stats<TYPE><<<E, EB, lds, s>>>(coords, (const TYPE *)rows, T, n_cap, (const long long *)n_dev, offsets, E, \
-                                           gains, seg_status, nx, ny, fix_last_n_se, rowstats, avg_coo, summed, stats, \
-                                           multiplicity, n_se, psdl, psdr, energy, features, flags)
-    if (dtype == WFS_F32)
-        WFS_EVSTATS(float);
-    else if (dtype == WFS_BF16)
-        WFS_EVSTATS(wfs_bf16);
-    else
-        WFS_EVSTATS(wfs_f16);
-#undef WFS_EVSTATS
-    WFS_LAUNCH_CHECK();
-    return WFS_OK;
+    return wfs_with_dtype(dtype, [&](auto t) -> int {
+        using TYPE = decltype(t);
+        k_event_stats<TYPE><<<E, EB, lds, s>>>(coords, (const TYPE *)rows, T, n_cap, (const long long *)n_dev, offsets, E,
+                                               gains, seg_status, nx, ny, fix_last_n_se, rowstats, avg_coo, summed, stats,
+                                               multiplicity, n_se, psdl, psdr, energy, features, flags);
+        WFS_LAUNCH_CHECK();
+        return WFS_OK;
+    });
 }
 
 extern "C" int wfs_eval_accumulate(int32_t E, int32_t T, int32_t n_classes, const double *avg_coo, const float *summed,

@@ -64,10 +64,6 @@ struct ECGeo {
     unsigned dig[32];
 };
 
-__device__ __forceinline__ long long valid_rows(long long R, const long long *r_dev) {
-    long long v = r_dev ? *r_dev : R;
-    return v < R ? v : R;
-}
 
 // The candidates of one input row, in registers: slot t (compile-time index) holds the event-local output cell the
 // row reaches through that slot's kernel offset, or -1.  PACKED: o_star = the one offset along the last dim that can
@@ -248,7 +244,7 @@ __global__ void __launch_bounds__(EC_THREADS) __attribute__((amdgpu_waves_per_eu
     const int e = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int cols = g.ndim + 1, last = g.ndim - 1;
     const unsigned tag = state[0] + 1u;                 // this launch's epoch: bumped by the LAST event's workgroup
-    const long long Nv = valid_rows(N, n_dev);
+    const long long Nv = wfs_valid_rows(N, n_dev);
     // the event table's flag words: any != 0 <=> the batch column is not grouped by event
     const bool structured = __ballot(ev_in[B + 1 + lane] != 0) == 0ull;
     int r0 = ev_in[e], r1 = ev_in[e + 1];
@@ -482,7 +478,7 @@ __global__ void __launch_bounds__(256) k_unpack_table(const int *__restrict__ pa
                                                       const long long *__restrict__ r_dev, int *__restrict__ dense) {
     const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
     const int q = blockIdx.y;
-    if (j >= valid_rows(R, r_dev) || q >= Kq) return;
+    if (j >= wfs_valid_rows(R, r_dev) || q >= Kq) return;
     const int ev = packed[(long long)q * R + j];
     for (int o = 0; o < kl; ++o) dense[((long long)q * kl + o) * R + j] = (ev >= 0 && (ev & 7) == o) ? (ev >> 3) : -1;
 }

@@ -31,10 +31,6 @@ struct EGeo {
 constexpr int EV_FLAG_BLOCKS = WFS_EVENT_FLAG_WORDS;      // k_event_offsets runs this many blocks, one flag word each
 constexpr int ER_THREADS = 512;
 
-__device__ __forceinline__ long long valid_rows(long long R, const long long *r_dev) {
-    long long v = r_dev ? *r_dev : R;
-    return v < R ? v : R;
-}
 
 __device__ __forceinline__ bool ev_structured(const int *ev, int B) {
     const int fl = ev[B + 1 + (threadIdx.x & 63)];
@@ -58,7 +54,7 @@ __device__ __forceinline__ void offset_digits(const EGeo &g, int k, int *off) {
 // batch index out of [0, B) or smaller than its predecessor's.  Every word is written by every launch (no clearing).
 __global__ void __launch_bounds__(256) k_event_offsets(const int *__restrict__ idx, long long N, int cols, int B,
                                                        const long long *__restrict__ n_dev, int *__restrict__ off) {
-    const long long Nv = valid_rows(N, n_dev);
+    const long long Nv = wfs_valid_rows(N, n_dev);
     int bad = 0;
     if (Nv == 0) {
         for (int e = blockIdx.x * 256 + threadIdx.x; e <= B; e += gridDim.x * 256) off[e] = 0;
@@ -111,7 +107,7 @@ __global__ void __launch_bounds__(ER_THREADS) k_ev_subm(EGeo g, EQTab qt, int Q,
     extern __shared__ __attribute__((aligned(16))) unsigned short pool[];      // pool_bytes
     __shared__ int2 sQt[32];
     __shared__ int sCount[ER_THREADS / 64 + 1];
-    const int Nv = (int)valid_rows(N, n_dev);
+    const int Nv = (int)wfs_valid_rows(N, n_dev);
     // flags: one word per workgroup and kind, flags[kind * gridDim.x + block]; set, never cleared, by a launch (see the end)
     int f_fail = 0, f_dup = 0, f_range = 0;
     const bool structured = ev_structured(ev, B);
@@ -366,14 +362,13 @@ extern "C" int wfs_event_rulebook_subm(const wfs_geometry *g, const int32_t *ind
     const EGeo G = make_egeo(g);
     const dim3 grid((unsigned)nblk), block(ER_THREADS);
     const int kl = g->ksize[g->ndim - 1];
-#define WFS_EVS(KL)                                                                                                    \
-    k_ev_subm<KL><<<grid, block, pool_bytes, stream>>>(G, qt, Q, L, split, pool_bytes, indices, N,                     \
-                                              (const long long *)n_dev, events, B, nbr_out,                            \
-                                              (uint4 *)slots, flags)
-    if (kl == 1) WFS_EVS(1); else if (kl == 2) WFS_EVS(2); else WFS_EVS(3);
-#undef WFS_EVS
-    WFS_LAUNCH_CHECK();
-    return WFS_OK;
+    return wfs_with_int<1, 2, 3>(kl, [&](auto kl_c) -> int {
+        k_ev_subm<decltype(kl_c)::value><<<grid, block, pool_bytes, stream>>>(G, qt, Q, L, split, pool_bytes, indices, N,
+                                                                             (const long long *)n_dev, events, B, nbr_out,
+                                                                             (uint4 *)slots, flags);
+        WFS_LAUNCH_CHECK();
+        return WFS_OK;
+    });
 }
 
 extern "C" size_t wfs_event_offsets_ints(int32_t batch_size) {

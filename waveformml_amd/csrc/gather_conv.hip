@@ -21,11 +21,7 @@ struct KMap {                // table column used for filter offset k (identity 
     int v[128];
 };
 
-// R = capacity (strides, grid); the number of valid rows comes from device memory when r_dev is given
-__device__ __forceinline__ long long valid_rows(long long R, const long long *r_dev) {
-    long long v = r_dev ? *r_dev : R;
-    return v < R ? v : R;
-}
+// R = capacity (strides, grid); the number of valid rows comes from device memory when r_dev is given (wfs_valid_rows)
 
 // ------------------------------------------------------------------------------------------
 // generic gather conv: block = 64 rows x 4 waves; wave w owns output channels
@@ -42,7 +38,7 @@ __global__ void __launch_bounds__(TB) k_gather_conv(const int *__restrict__ tabl
     const long long r = (long long)blockIdx.x * 64 + lane;
     const int c0 = blockIdx.y * (4 * CT) + wid * CT;
     if (c0 >= Cy) return;
-    const bool live = r < valid_rows(R, r_dev);
+    const bool live = r < wfs_valid_rows(R, r_dev);
     float acc[CT];
 #pragma unroll
     for (int c = 0; c < CT; ++c) acc[c] = (bias != nullptr && c0 + c < Cy) ? bias[c0 + c] : 0.f;
@@ -126,7 +122,7 @@ __global__ void __launch_bounds__(TB) k_gather_dw(const int *__restrict__ table,
     const int ta = blockIdx.z / tiles_b, tb = blockIdx.z % tiles_b;
     const int a0 = ta * DW_TA, b0 = tb * DW_TBB;
     const long long chunk = blockIdx.x;
-    const long long Rv = valid_rows(R, r_dev);
+    const long long Rv = wfs_valid_rows(R, r_dev);
     const long long r_begin = chunk * rows_per_chunk;
     const long long r_end = r_begin + rows_per_chunk < Rv ? r_begin + rows_per_chunk : Rv;
     // thread -> 2x2 micro tile of the 32x32 output tile
@@ -226,7 +222,7 @@ __global__ void __launch_bounds__(64 * GM_WAVES) k_gconv_mfma(const int *__restr
     const long long tile = blockIdx.x;
     const int col0 = blockIdx.y * 32, col = col0 + r;
     const bool col_ok = col < Cy;
-    const long long Rv = valid_rows(R, r_dev);
+    const long long Rv = wfs_valid_rows(R, r_dev);
     for (int e = threadIdx.x; e < K * 32; e += 64 * GM_WAVES) {
         const int k = e >> 5;
         const long long row = tile * 32 + (e & 31);
@@ -332,7 +328,7 @@ __global__ void __launch_bounds__(64) k_gdw_mfma(const int *__restrict__ table, 
     const int k = blockIdx.y;
     const int a0 = (blockIdx.z / tiles_b) * 32, b0 = (blockIdx.z % tiles_b) * 32;
     const long long chunk = blockIdx.x;
-    const long long Rv = valid_rows(R, r_dev);
+    const long long Rv = wfs_valid_rows(R, r_dev);
     const long long r_begin = chunk * rows_per_chunk;
     const long long r_end = r_begin + rows_per_chunk < Rv ? r_begin + rows_per_chunk : Rv;
     const bool a_ok = a0 + j < Cs, b_ok = b0 + j < Cg;
@@ -427,54 +423,47 @@ static int gather_conv_impl(const int32_t *table, const int32_t *kmap_host, int3
     }
     WfsTimerScope timer(WFS_TIMER_GATHER_CONV, stream);
     // the fast kernels know two column maps: identity, and the SubM mirror k -> K-1-k
-    bool is_ident = true, is_mirror = true;
-    for (int k = 0; k < K; ++k) {
-        is_ident = is_ident && km.v[k] == k;
-        is_mirror = is_mirror && km.v[k] == K - 1 - k;
-    }
+    const int kind = wfs_kmap_kind(kmap_host, K);
+    const int mirror = kind == WFS_KMAP_MIRROR;
     // (the fp32 kernel addresses the gathered rows through 32-bit byte offsets: fewer than 2^24 rows of 128 B)
-    if (dtype == WFS_F32 && Cx == 32 && Cy == 32 && wfs_mfma_gconv32_ok(K) && table && (is_ident || is_mirror) &&
+    if (dtype == WFS_F32 && Cx == 32 && Cy == 32 && wfs_mfma_gconv32_ok(K) && table && kind != WFS_KMAP_OTHER &&
         X_rows < (1ll << 24)) {
-        return wfs_launch_gconv32_f32(table, is_ident ? 0 : 1, K, identity_k, R, r_dev, (const float *)X, W, transpose_w,
-                                      bias, (float *)Y, stream, packed_kl);
+        return wfs_launch_gconv32_f32(table, mirror, K, identity_k, R, r_dev, (const float *)X, W, transpose_w, bias,
+                                      (float *)Y, stream, packed_kl);
     }
-    if (dtype != WFS_F32 && Cx == 32 && Cy == 32 && K <= 27 && table && (is_ident || is_mirror) && X_rows < (1ll << 25)) {
-        return wfs_launch_gconv32_h16(table, is_ident ? 0 : 1, K, identity_k, R, r_dev, X, W, transpose_w, bias, Y,
-                                      dtype, stream, packed_kl);
+    if (dtype != WFS_F32 && Cx == 32 && Cy == 32 && K <= 27 && table && kind != WFS_KMAP_OTHER && X_rows < (1ll << 25)) {
+        return wfs_launch_gconv32_h16(table, mirror, K, identity_k, R, r_dev, X, W, transpose_w, bias, Y, dtype, stream,
+                                      packed_kl);
     }
     WFS_REQUIRE(packed_kl == 0, WFS_EINVAL, "a packed table reached a kernel that reads dense ones");
     if (Cx == 2 && Cy == 32 && !transpose_w && table)
         return wfs_launch_gconv_c2c32(table, kmap_host, K, identity_k, R, r_dev, X, W, bias, Y, dtype, stream);
     if (gm_shape(Cx, Cy) && table) {
         const dim3 g((unsigned)wfs_cdiv(R, 32), (unsigned)wfs_cdiv(Cy, 32)), b(64 * GM_WAVES);
-#define WFS_GM(T, TR)                                                                                            \
-    k_gconv_mfma<T, TR><<<g, b, 0, stream>>>(table, km, K, identity_k, R, r_dev, (const T *)X, Cx, W, Cw_in, Cw_out, \
-                                             bias, (T *)Y, Cy)
-        if (dtype == WFS_F32) {
-            if (transpose_w) WFS_GM(float, true); else WFS_GM(float, false);
-        } else if (dtype == WFS_BF16) {
-            if (transpose_w) WFS_GM(wfs_bf16, true); else WFS_GM(wfs_bf16, false);
-        } else {
-            if (transpose_w) WFS_GM(wfs_f16, true); else WFS_GM(wfs_f16, false);
-        }
-#undef WFS_GM
-        WFS_LAUNCH_CHECK();
-        return WFS_OK;
+        return wfs_with_dtype(dtype, [&](auto t) -> int {
+            using T = decltype(t);
+            if (transpose_w)
+                k_gconv_mfma<T, true><<<g, b, 0, stream>>>(table, km, K, identity_k, R, r_dev, (const T *)X, Cx, W, Cw_in,
+                                                           Cw_out, bias, (T *)Y, Cy);
+            else
+                k_gconv_mfma<T, false><<<g, b, 0, stream>>>(table, km, K, identity_k, R, r_dev, (const T *)X, Cx, W, Cw_in,
+                                                            Cw_out, bias, (T *)Y, Cy);
+            WFS_LAUNCH_CHECK();
+            return WFS_OK;
+        });
     }
     dim3 grid((unsigned)wfs_cdiv(R, 64), (unsigned)wfs_cdiv(Cy, 4 * CT)), block(TB);
-#define WFS_GC(T, TR)                                                                                           \
-    k_gather_conv<T, TR><<<grid, block, 0, stream>>>(table, km, K, identity_k, R, r_dev, (const T *)X, Cx, W,  \
-                                                      Cw_in, Cw_out, bias, (T *)Y, Cy)
-    if (dtype == WFS_F32) {
-        if (transpose_w) WFS_GC(float, true); else WFS_GC(float, false);
-    } else if (dtype == WFS_BF16) {
-        if (transpose_w) WFS_GC(wfs_bf16, true); else WFS_GC(wfs_bf16, false);
-    } else {
-        if (transpose_w) WFS_GC(wfs_f16, true); else WFS_GC(wfs_f16, false);
-    }
-#undef WFS_GC
-    WFS_LAUNCH_CHECK();
-    return WFS_OK;
+    return wfs_with_dtype(dtype, [&](auto t) -> int {
+        using T = decltype(t);
+        if (transpose_w)
+            k_gather_conv<T, true><<<grid, block, 0, stream>>>(table, km, K, identity_k, R, r_dev, (const T *)X, Cx, W, Cw_in,
+                                                               Cw_out, bias, (T *)Y, Cy);
+        else
+            k_gather_conv<T, false><<<grid, block, 0, stream>>>(table, km, K, identity_k, R, r_dev, (const T *)X, Cx, W, Cw_in,
+                                                                Cw_out, bias, (T *)Y, Cy);
+        WFS_LAUNCH_CHECK();
+        return WFS_OK;
+    });
 }
 
 extern "C" int wfs_gather_conv(const int32_t *table, const int32_t *kmap_host, int32_t K, int32_t identity_k,
@@ -505,19 +494,17 @@ extern "C" int wfs_scatter_conv(const int32_t *table, int32_t K, int32_t identit
     if (R == 0) return WFS_OK;
     WFS_REQUIRE(table && X && W && Y_accum, WFS_EINVAL, "NULL device pointer");
     dim3 grid((unsigned)wfs_cdiv(R, 64), (unsigned)wfs_cdiv(Cy, 4 * CT)), block(TB);
-#define WFS_SC(T, TR)                                                                                          \
-    k_scatter_conv<T, TR><<<grid, block, 0, stream>>>(table, K, identity_k, R, (const T *)X, Cx, W, Cw_in, Cw_out, \
-                                                       Y_accum, Cy)
-    if (dtype == WFS_F32) {
-        if (transpose_w) WFS_SC(float, true); else WFS_SC(float, false);
-    } else if (dtype == WFS_BF16) {
-        if (transpose_w) WFS_SC(wfs_bf16, true); else WFS_SC(wfs_bf16, false);
-    } else {
-        if (transpose_w) WFS_SC(wfs_f16, true); else WFS_SC(wfs_f16, false);
-    }
-#undef WFS_SC
-    WFS_LAUNCH_CHECK();
-    return WFS_OK;
+    return wfs_with_dtype(dtype, [&](auto t) -> int {
+        using T = decltype(t);
+        if (transpose_w)
+            k_scatter_conv<T, true><<<grid, block, 0, stream>>>(table, K, identity_k, R, (const T *)X, Cx, W, Cw_in, Cw_out,
+                                                                Y_accum, Cy);
+        else
+            k_scatter_conv<T, false><<<grid, block, 0, stream>>>(table, K, identity_k, R, (const T *)X, Cx, W, Cw_in, Cw_out,
+                                                                 Y_accum, Cy);
+        WFS_LAUNCH_CHECK();
+        return WFS_OK;
+    });
 }
 
 extern "C" size_t wfs_gather_dw_workspace_bytes(int32_t K, int64_t R, int32_t Cs, int32_t Cg) {
@@ -542,7 +529,7 @@ static int gather_dw_impl(const int32_t *table, const int32_t *kmap_host, int32_
     WFS_REQUIRE(K >= 1 && K <= 65535, WFS_EINVAL, "bad K");
     WFS_REQUIRE(wfs_dtype_ok(dtype), WFS_EINVAL, "bad dtype %d", dtype);
     WFS_REQUIRE(dW, WFS_EINVAL, "NULL dW");
-    if (defer) *defer = wfs_dw_job{nullptr, 0, 0, 0, 0, 0, 0, nullptr};        // nothing pending unless a fast path says so
+    if (defer) *defer = wfs_dw_job_none();        // nothing pending unless a fast path says so
     if (R == 0) {
         WFS_HIP_CHECK(hipMemsetAsync(dW, 0, (size_t)K * Cs * Cg * sizeof(float), stream));
         return WFS_OK;
@@ -563,45 +550,35 @@ static int gather_dw_impl(const int32_t *table, const int32_t *kmap_host, int32_
         return wfs_launch_gdw32(table, K, identity_k, R, r_dev, S, G, swap, dW, (float *)workspace, dtype, defer, stream,
                                 packed_kl);
     WFS_REQUIRE(packed_kl == 0, WFS_EINVAL, "a packed table reached a kernel that reads dense ones");
-    bool is_ident = true, is_mirror = true;
-    for (int k = 0; k < K && kmap_host; ++k) {
-        is_ident = is_ident && kmap_host[k] == k;
-        is_mirror = is_mirror && kmap_host[k] == K - 1 - k;
-    }
-    if (!kmap_host) is_mirror = false;
-    if (Cs == 32 && Cg == 2 && K <= 27 && table && (is_ident || is_mirror))
-        return wfs_launch_gdw_c32c2(table, is_ident ? 0 : 1, K, identity_k, R, r_dev, S, G, swap, dW, (float *)workspace,
-                                    dtype, defer, stream);
-    WFS_REQUIRE(is_ident, WFS_EINVAL, "a column map is only supported by the 32 x 2 dW kernel");
+    const int kind = wfs_kmap_kind(kmap_host, K);
+    if (Cs == 32 && Cg == 2 && K <= 27 && table && kind != WFS_KMAP_OTHER)
+        return wfs_launch_gdw_c32c2(table, kind == WFS_KMAP_MIRROR, K, identity_k, R, r_dev, S, G, swap, dW,
+                                    (float *)workspace, dtype, defer, stream);
+    WFS_REQUIRE(kind == WFS_KMAP_IDENTITY, WFS_EINVAL, "a column map is only supported by the 32 x 2 dW kernel");
     long long chunks = gm_shape(Cs, Cg) ? dw_chunks_mfma(R, K, Cs, Cg) : dw_chunks(R);
     long long rows_per_chunk = wfs_cdiv(wfs_cdiv(R, chunks), DW_ROWS) * DW_ROWS;
     int tiles_a = (int)wfs_cdiv(Cs, DW_TA), tiles_b = (int)wfs_cdiv(Cg, DW_TBB);
     WFS_REQUIRE((long long)tiles_a * tiles_b <= 65535, WFS_EINVAL, "channel tile grid too large");
     dim3 grid((unsigned)chunks, (unsigned)K, (unsigned)(tiles_a * tiles_b)), block(TB);
     float *part = (float *)workspace;
-    if (gm_shape(Cs, Cg) && table) {
-        const dim3 b64(64);
-        if (dtype == WFS_F32)
-            k_gdw_mfma<float><<<grid, b64, 0, stream>>>(table, K, identity_k, R, r_dev, rows_per_chunk, (const float *)S, Cs,
-                                                        (const float *)G, Cg, part, tiles_b);
-        else if (dtype == WFS_BF16)
-            k_gdw_mfma<wfs_bf16><<<grid, b64, 0, stream>>>(table, K, identity_k, R, r_dev, rows_per_chunk,
-                                                           (const wfs_bf16 *)S, Cs, (const wfs_bf16 *)G, Cg, part, tiles_b);
-        else
-            k_gdw_mfma<wfs_f16><<<grid, b64, 0, stream>>>(table, K, identity_k, R, r_dev, rows_per_chunk, (const wfs_f16 *)S,
-                                                          Cs, (const wfs_f16 *)G, Cg, part, tiles_b);
-    } else if (dtype == WFS_F32)
-        k_gather_dw<float><<<grid, block, 0, stream>>>(table, K, identity_k, R, r_dev, rows_per_chunk, (const float *)S,
-                                                       Cs, (const float *)G, Cg, part, tiles_a, tiles_b);
-    else if (dtype == WFS_BF16)
-        k_gather_dw<wfs_bf16><<<grid, block, 0, stream>>>(table, K, identity_k, R, r_dev, rows_per_chunk,
-                                                          (const wfs_bf16 *)S, Cs, (const wfs_bf16 *)G, Cg, part,
-                                                          tiles_a, tiles_b);
+    int rc;
+    if (gm_shape(Cs, Cg) && table)
+        rc = wfs_with_dtype(dtype, [&](auto t) -> int {
+            using T = decltype(t);
+            k_gdw_mfma<T><<<grid, dim3(64), 0, stream>>>(table, K, identity_k, R, r_dev, rows_per_chunk, (const T *)S, Cs,
+                                                         (const T *)G, Cg, part, tiles_b);
+            WFS_LAUNCH_CHECK();
+            return WFS_OK;
+        });
     else
-        k_gather_dw<wfs_f16><<<grid, block, 0, stream>>>(table, K, identity_k, R, r_dev, rows_per_chunk,
-                                                         (const wfs_f16 *)S, Cs, (const wfs_f16 *)G, Cg, part, tiles_a,
-                                                         tiles_b);
-    WFS_LAUNCH_CHECK();
+        rc = wfs_with_dtype(dtype, [&](auto t) -> int {
+            using T = decltype(t);
+            k_gather_dw<T><<<grid, block, 0, stream>>>(table, K, identity_k, R, r_dev, rows_per_chunk, (const T *)S, Cs,
+                                                       (const T *)G, Cg, part, tiles_a, tiles_b);
+            WFS_LAUNCH_CHECK();
+            return WFS_OK;
+        });
+    if (rc != WFS_OK) return rc;
     long long per = (long long)K * Cs * Cg;
     k_dw_reduce<<<dim3((unsigned)wfs_cdiv(per, TB)), block, 0, stream>>>(part, chunks, K, Cs, Cg, swap, dW);
     WFS_LAUNCH_CHECK();
@@ -638,7 +615,7 @@ extern "C" int wfs_conv_backward(const int32_t *table, int32_t K, int32_t identi
     WFS_REQUIRE(X && dY && W && workspace, WFS_EINVAL, "NULL device pointer");
     const size_t need = wfs_gather_dw_workspace_bytes(K, R, Cin, Cout);
     WFS_REQUIRE(workspace_bytes >= need, WFS_EWORKSPACE, "workspace %zu < %zu", workspace_bytes, need);
-    if (defer) *defer = wfs_dw_job{nullptr, 0, 0, 0, 0, 0, 0, nullptr};
+    if (defer) *defer = wfs_dw_job_none();
     WfsTimerScope timer(WFS_TIMER_CONV_BACKWARD, stream);
     return wfs_launch_bwd32_h16(table, packed_kl, K, identity_k, R, (const long long *)r_dev, X, dY, W, dX, 0, dW,
                                 (float *)workspace, dtype, defer, stream);
@@ -664,7 +641,7 @@ extern "C" int wfs_first_conv_bn_backward(const int32_t *table, const int32_t *k
     WFS_REQUIRE(dtype == WFS_BF16 || dtype == WFS_F16, WFS_EINVAL, "16-bit rows only (dtype %d)", dtype);
     WFS_REQUIRE(dW, WFS_EINVAL, "NULL dW");
     WFS_REQUIRE(R >= 0 && R < (1ll << 31) && X_rows < (1ll << 31), WFS_EINVAL, "too many rows");
-    if (defer) *defer = wfs_dw_job{nullptr, 0, 0, 0, 0, 0, 0, nullptr};
+    if (defer) *defer = wfs_dw_job_none();
     if (R == 0) {
         WFS_HIP_CHECK(hipMemsetAsync(dW, 0, (size_t)K * 64 * sizeof(float), stream));
         if (dgamma) WFS_HIP_CHECK(hipMemsetAsync(dgamma, 0, 32 * sizeof(float), stream));
@@ -674,12 +651,8 @@ extern "C" int wfs_first_conv_bn_backward(const int32_t *table, const int32_t *k
     WFS_REQUIRE(table && Z && dY && X && save_mean && save_invstd && workspace, WFS_EINVAL, "NULL device pointer");
     WFS_REQUIRE(((uintptr_t)workspace & 15) == 0, WFS_EINVAL, "the workspace must be 16-byte aligned");
     WFS_REQUIRE(workspace_bytes >= wfs_first_conv_bn_backward_workspace_bytes(K, R), WFS_EWORKSPACE, "workspace too small");
-    bool is_ident = true, is_mirror = kmap_host != nullptr;
-    for (int k = 0; k < K && kmap_host; ++k) {
-        is_ident = is_ident && kmap_host[k] == k;
-        is_mirror = is_mirror && kmap_host[k] == K - 1 - k;
-    }
-    WFS_REQUIRE(is_ident || is_mirror, WFS_EINVAL, "the column map must be the identity or the SubM mirror");
+    const int kind = wfs_kmap_kind(kmap_host, K);
+    WFS_REQUIRE(kind != WFS_KMAP_OTHER, WFS_EINVAL, "the column map must be the identity or the SubM mirror");
     float *part = (float *)workspace;
     float *partial = (float *)((char *)workspace + first_bn_slab_bytes(K, R));
     int nblk = 0;
@@ -687,9 +660,9 @@ extern "C" int wfs_first_conv_bn_backward(const int32_t *table, const int32_t *k
                                       (const long long *)r_dev, stream, &nblk);
     if (rc != WFS_OK) return rc;
     WfsTimerScope timer(WFS_TIMER_GATHER_DW, stream);
-    return wfs_launch_first_bn_bwd(table, is_ident ? 0 : 1, K, identity_k, R, (const long long *)r_dev, Z, dY, X, gamma, beta,
-                                   save_mean, save_invstd, relu ? 1 : 0, partial, nblk, dW, dgamma, dbeta, part, dtype, defer,
-                                   stream);
+    return wfs_launch_first_bn_bwd(table, kind == WFS_KMAP_MIRROR, K, identity_k, R, (const long long *)r_dev, Z, dY, X, gamma,
+                                   beta, save_mean, save_invstd, relu ? 1 : 0, partial, nblk, dW, dgamma, dbeta, part, dtype,
+                                   defer, stream);
 }
 
 extern "C" int wfs_dw_reduce_jobs(const wfs_dw_job *jobs, int32_t n, void *stream) {
@@ -717,7 +690,7 @@ __global__ void __launch_bounds__(256) k_colsum_partial(const T *__restrict__ X,
                                                         const long long *__restrict__ r_dev, int C,
                                                         float *__restrict__ partial) {
     const int c = blockIdx.y * 256 + threadIdx.x;
-    const long long R = r_dev ? (*r_dev < Rcap ? *r_dev : Rcap) : Rcap;
+    const long long R = wfs_valid_rows(Rcap, r_dev);
     if (c >= C) return;
     float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;              // four independent chains, added in a fixed order
     long long r = blockIdx.x;
@@ -759,12 +732,11 @@ extern "C" int wfs_column_sum(const void *X, int64_t R, int32_t C, float *out, v
     const dim3 grid((unsigned)nblk, (unsigned)wfs_cdiv(C, 256)), block(256);
     float *partial = (float *)workspace;
     const long long *rd = (const long long *)r_dev;
-    if (dtype == WFS_F32)
-        k_colsum_partial<float><<<grid, block, 0, stream>>>((const float *)X, R, rd, C, partial);
-    else if (dtype == WFS_BF16)
-        k_colsum_partial<wfs_bf16><<<grid, block, 0, stream>>>((const wfs_bf16 *)X, R, rd, C, partial);
-    else
-        k_colsum_partial<wfs_f16><<<grid, block, 0, stream>>>((const wfs_f16 *)X, R, rd, C, partial);
+    wfs_with_dtype(dtype, [&](auto t) -> int {
+        using T = decltype(t);
+        k_colsum_partial<T><<<grid, block, 0, stream>>>((const T *)X, R, rd, C, partial);
+        return WFS_OK;
+    });
     k_colsum_fold<<<dim3((unsigned)wfs_cdiv(C, 256)), block, 0, stream>>>(partial, (int)nblk, C, out);
     WFS_LAUNCH_CHECK();
     return WFS_OK;

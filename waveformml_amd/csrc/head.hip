@@ -349,17 +349,13 @@ extern "C" size_t wfs_head_workspace_bytes(int64_t B, int64_t I, int32_t O) {
     return (size_t)head_chunks(B) * O * I * sizeof(float);
 }
 
-#define WFS_HEAD_DISPATCH(O, CALL)                    \
-    switch (O) {                                      \
-        case 1: { constexpr int OO = 1; CALL; } break; \
-        case 2: { constexpr int OO = 2; CALL; } break; \
-        case 3: { constexpr int OO = 3; CALL; } break; \
-        case 4: { constexpr int OO = 4; CALL; } break; \
-        case 5: { constexpr int OO = 5; CALL; } break; \
-        case 6: { constexpr int OO = 6; CALL; } break; \
-        case 7: { constexpr int OO = 7; CALL; } break; \
-        default: { constexpr int OO = 8; CALL; } break; \
-    }
+// f(T{}, std::integral_constant<int, O>{}) for the rows' dtype and the number of outputs (1 .. MAXO)
+template <typename F>
+static int with_dtype_o(int dtype, int O, F f) {
+    return wfs_with_dtype(dtype, [&](auto t) -> int {
+        return wfs_with_int<1, 2, 3, 4, 5, 6, 7, 8>(O, [&](auto o) -> int { return f(t, o); });
+    });
+}
 
 extern "C" int wfs_head_fwd(const void *X, int64_t B, int64_t I, const float *W, const float *bias, int32_t O,
                             float *Y, int32_t dtype, void *stream_) {
@@ -369,23 +365,22 @@ extern "C" int wfs_head_fwd(const void *X, int64_t B, int64_t I, const float *W,
     if (B == 0) return WFS_OK;
     WFS_REQUIRE(X && W && Y, WFS_EINVAL, "NULL device pointer");
     dim3 grid((unsigned)B);
-    if (head_any(I)) {
-#define WFS_HEAD_FWD_ANY(T) WFS_HEAD_DISPATCH(O, (k_head_fwd_any<T, OO><<<grid, dim3(64), 0, stream>>>((const T *)X, W, bias, Y, I)))
-        if (dtype == WFS_F32) { WFS_HEAD_FWD_ANY(float); } else if (dtype == WFS_BF16) { WFS_HEAD_FWD_ANY(wfs_bf16); } else { WFS_HEAD_FWD_ANY(wfs_f16); }
-#undef WFS_HEAD_FWD_ANY
-        WFS_LAUNCH_CHECK();
-        return WFS_OK;
-    }
-#define WFS_HEAD_FWD(T, NT)                                                                                          \
-    WFS_HEAD_DISPATCH(O, (k_head_fwd<T, OO, NT><<<grid, dim3(NT), 0, stream>>>((const T *)X, W, bias, Y, I)))
-    if (I >= 8192) {
-        if (dtype == WFS_F32) { WFS_HEAD_FWD(float, 1024); } else if (dtype == WFS_BF16) { WFS_HEAD_FWD(wfs_bf16, 1024); } else { WFS_HEAD_FWD(wfs_f16, 1024); }
-    } else {
-        if (dtype == WFS_F32) { WFS_HEAD_FWD(float, 256); } else if (dtype == WFS_BF16) { WFS_HEAD_FWD(wfs_bf16, 256); } else { WFS_HEAD_FWD(wfs_f16, 256); }
-    }
-#undef WFS_HEAD_FWD
-    WFS_LAUNCH_CHECK();
-    return WFS_OK;
+    if (head_any(I))
+        return with_dtype_o(dtype, O, [&](auto t, auto o) -> int {
+            using T = decltype(t);
+            k_head_fwd_any<T, decltype(o)::value><<<grid, dim3(64), 0, stream>>>((const T *)X, W, bias, Y, I);
+            WFS_LAUNCH_CHECK();
+            return WFS_OK;
+        });
+    return wfs_with_int<1024, 256>(I >= 8192 ? 1024 : 256, [&](auto nt) -> int {
+        return with_dtype_o(dtype, O, [&](auto t, auto o) -> int {
+            using T = decltype(t);
+            constexpr int NT = decltype(nt)::value;
+            k_head_fwd<T, decltype(o)::value, NT><<<grid, dim3(NT), 0, stream>>>((const T *)X, W, bias, Y, I);
+            WFS_LAUNCH_CHECK();
+            return WFS_OK;
+        });
+    });
 }
 
 extern "C" int wfs_head_bwd(const void *X, const float *G, int64_t B, int64_t I, const float *W, int32_t O, void *dX,
@@ -399,21 +394,26 @@ extern "C" int wfs_head_bwd(const void *X, const float *G, int64_t B, int64_t I,
         return WFS_OK;
     }
     WFS_REQUIRE(X && G && W, WFS_EINVAL, "NULL device pointer");
+    if (defer) *defer = wfs_dw_job_none();
     if (head_any(I)) {
-        if (defer) *defer = wfs_dw_job{nullptr, 0, 0, 0, 0, 0, 0, nullptr};
         const dim3 gdx((unsigned)wfs_cdiv(B * I, TB)), gdw((unsigned)wfs_cdiv(I + 1, 16)), block(TB);
-#define WFS_HEAD_BWD_ANY(T)                                                                                          \
-    do {                                                                                                             \
-        if (dX) WFS_HEAD_DISPATCH(O, (k_head_dx_any<T, OO><<<gdx, block, 0, stream>>>(G, W, (T *)dX, B, I)));        \
-        if (dW) WFS_HEAD_DISPATCH(O, (k_head_dw_any<T, OO><<<gdw, block, 0, stream>>>(G, (const T *)X, dW, dB, B, I))); \
-    } while (0)
-        if (dtype == WFS_F32) { WFS_HEAD_BWD_ANY(float); } else if (dtype == WFS_BF16) { WFS_HEAD_BWD_ANY(wfs_bf16); } else { WFS_HEAD_BWD_ANY(wfs_f16); }
-#undef WFS_HEAD_BWD_ANY
-        WFS_LAUNCH_CHECK();
-        return WFS_OK;
+        return wfs_with_dtype(dtype, [&](auto t) -> int {
+            using T = decltype(t);
+            if (dX)
+                wfs_with_int<1, 2, 3, 4, 5, 6, 7, 8>(O, [&](auto o) -> int {
+                    k_head_dx_any<T, decltype(o)::value><<<gdx, block, 0, stream>>>(G, W, (T *)dX, B, I);
+                    return WFS_OK;
+                });
+            if (dW)
+                wfs_with_int<1, 2, 3, 4, 5, 6, 7, 8>(O, [&](auto o) -> int {
+                    k_head_dw_any<T, decltype(o)::value><<<gdw, block, 0, stream>>>(G, (const T *)X, dW, dB, B, I);
+                    return WFS_OK;
+                });
+            WFS_LAUNCH_CHECK();
+            return WFS_OK;
+        });
     }
     const unsigned gx = (unsigned)wfs_cdiv(I, TB * 8);
-    if (defer) *defer = wfs_dw_job{nullptr, 0, 0, 0, 0, 0, 0, nullptr};
     if (dX && dW && B + 16 <= 65535) {
         // one launch for dX and the dW partials (+ dB); the reduction over the partials runs now, or later as one of the
         // caller's deferred jobs (wfs_dw_reduce_jobs)
@@ -422,12 +422,14 @@ extern "C" int wfs_head_bwd(const void *X, const float *G, int64_t B, int64_t I,
         const int rpc = (int)wfs_cdiv(B, nchunk);
         dim3 grid(gx, (unsigned)(B + nchunk)), block(TB);
         float *part = (float *)workspace;
-#define WFS_HEAD_BWD(T)                                                                                              \
-    WFS_HEAD_DISPATCH(O, (k_head_bwd<T, OO><<<grid, block, 0, stream>>>(G, W, (const T *)X, (T *)dX, part, dB, B, I, rpc, \
-                                                                       (int)B)))
-        if (dtype == WFS_F32) { WFS_HEAD_BWD(float); } else if (dtype == WFS_BF16) { WFS_HEAD_BWD(wfs_bf16); } else { WFS_HEAD_BWD(wfs_f16); }
-#undef WFS_HEAD_BWD
-        WFS_LAUNCH_CHECK();
+        int rc = with_dtype_o(dtype, O, [&](auto t, auto o) -> int {
+            using T = decltype(t);
+            k_head_bwd<T, decltype(o)::value><<<grid, block, 0, stream>>>(G, W, (const T *)X, (T *)dX, part, dB, B, I, rpc,
+                                                                          (int)B);
+            WFS_LAUNCH_CHECK();
+            return WFS_OK;
+        });
+        if (rc != WFS_OK) return rc;
         const long long OI = (long long)O * I;
         if (defer) {
             *defer = wfs_dw_job{part, nchunk, OI, 1, 1, 1, 0, dW};
@@ -439,14 +441,13 @@ extern "C" int wfs_head_bwd(const void *X, const float *G, int64_t B, int64_t I,
     }
     if (dX) {
         dim3 grid(gx, (unsigned)B), block(TB);
-        if (dtype == WFS_F32) {
-            WFS_HEAD_DISPATCH(O, (k_head_dx<float, OO><<<grid, block, 0, stream>>>(G, W, (float *)dX, I)));
-        } else if (dtype == WFS_BF16) {
-            WFS_HEAD_DISPATCH(O, (k_head_dx<wfs_bf16, OO><<<grid, block, 0, stream>>>(G, W, (wfs_bf16 *)dX, I)));
-        } else {
-            WFS_HEAD_DISPATCH(O, (k_head_dx<wfs_f16, OO><<<grid, block, 0, stream>>>(G, W, (wfs_f16 *)dX, I)));
-        }
-        WFS_LAUNCH_CHECK();
+        int rc = with_dtype_o(dtype, O, [&](auto t, auto o) -> int {
+            using T = decltype(t);
+            k_head_dx<T, decltype(o)::value><<<grid, block, 0, stream>>>(G, W, (T *)dX, I);
+            WFS_LAUNCH_CHECK();
+            return WFS_OK;
+        });
+        if (rc != WFS_OK) return rc;
     }
     if (dW) {
         const int nchunk = head_chunks(B);
@@ -454,14 +455,13 @@ extern "C" int wfs_head_bwd(const void *X, const float *G, int64_t B, int64_t I,
         const int rpc = (int)wfs_cdiv(B, nchunk);
         dim3 grid(gx, (unsigned)nchunk), block(TB);
         float *part = (float *)workspace;
-        if (dtype == WFS_F32) {
-            WFS_HEAD_DISPATCH(O, (k_head_dw<float, OO><<<grid, block, 0, stream>>>(G, (const float *)X, part, B, I, rpc)));
-        } else if (dtype == WFS_BF16) {
-            WFS_HEAD_DISPATCH(O, (k_head_dw<wfs_bf16, OO><<<grid, block, 0, stream>>>(G, (const wfs_bf16 *)X, part, B, I, rpc)));
-        } else {
-            WFS_HEAD_DISPATCH(O, (k_head_dw<wfs_f16, OO><<<grid, block, 0, stream>>>(G, (const wfs_f16 *)X, part, B, I, rpc)));
-        }
-        WFS_LAUNCH_CHECK();
+        int rc = with_dtype_o(dtype, O, [&](auto t, auto o) -> int {
+            using T = decltype(t);
+            k_head_dw<T, decltype(o)::value><<<grid, block, 0, stream>>>(G, (const T *)X, part, B, I, rpc);
+            WFS_LAUNCH_CHECK();
+            return WFS_OK;
+        });
+        if (rc != WFS_OK) return rc;
         const long long OI = (long long)O * I;
         k_head_dw_reduce<<<dim3((unsigned)wfs_cdiv(OI, TB)), dim3(TB), 0, stream>>>(part, nchunk, OI, dW, G, B, O, dB);
         WFS_LAUNCH_CHECK();

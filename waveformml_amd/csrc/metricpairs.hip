@@ -53,7 +53,7 @@ k_metric_pairs(const float *__restrict__ params, const int *__restrict__ result,
                long long M, const long long *__restrict__ n_dev, PairPlan pl, long long *__restrict__ tab,
                int *__restrict__ flags) {
     extern __shared__ int image[];            // [2][cells1]: counts, then match sums
-    const long long nv = valid_rows(M, n_dev);
+    const long long nv = wfs_valid_rows_nonneg(M, n_dev);
     const int P = pl.P, C = pl.C;
     for (long long base = (long long)blockIdx.x * MP_SLICE; base < nv; base += (long long)gridDim.x * MP_SLICE) {
         if (LDS1D) {
@@ -140,7 +140,7 @@ k_pid_rows(const int *__restrict__ coords, const long long *__restrict__ pred, c
            const float *__restrict__ seg, PidPlan pp, const int *__restrict__ off, int *__restrict__ accuracy,
            int *__restrict__ mult, int *__restrict__ se, int *__restrict__ n_se, float *__restrict__ params,
            int *__restrict__ category, long long *__restrict__ tab, int *__restrict__ flags) {
-    const long long nv = valid_rows(n_cap, n_dev);
+    const long long nv = wfs_valid_rows_nonneg(n_cap, n_dev);
     const long long r = (long long)blockIdx.x * MB + threadIdx.x;
     if (r >= n_cap) return;
     // a row that is not scored (beyond the valid count or flagged) still gets defined outputs; category -1 keeps it out
@@ -298,19 +298,14 @@ extern "C" int wfs_pid_row_stats(const int32_t *coords, const int64_t *predictio
     k_eval_offsets<<<rb, MB, 0, s>>>(coords, n_cap, (const long long *)n_dev, E, offsets, flags);
     WFS_LAUNCH_CHECK();
     const PidPlan pp = {nx, ny, n_phys, e_index, psd_index, z_index, n_confusion, n_se_max, e_high};
-#define WFS_PIDROWS(TYPE)                                                                                              \
-    k_pid_rows<TYPE><<<rb, MB, 0, s>>>(coords, (const long long *)predictions, (const long long *)targets,            \
-                                       (const TYPE *)phys, n_cap, (const long long *)n_dev, E, seg_status, pp, offsets, \
-                                       accuracy, multiplicity, se, n_se, params, category, (long long *)tables, flags)
-    if (dtype == WFS_F32)
-        WFS_PIDROWS(float);
-    else if (dtype == WFS_BF16)
-        WFS_PIDROWS(wfs_bf16);
-    else
-        WFS_PIDROWS(wfs_f16);
-#undef WFS_PIDROWS
-    WFS_LAUNCH_CHECK();
-    return WFS_OK;
+    return wfs_with_dtype(dtype, [&](auto t) -> int {
+        using TYPE = decltype(t);
+        k_pid_rows<TYPE><<<rb, MB, 0, s>>>(coords, (const long long *)predictions, (const long long *)targets,
+                                           (const TYPE *)phys, n_cap, (const long long *)n_dev, E, seg_status, pp, offsets,
+                                           accuracy, multiplicity, se, n_se, params, category, (long long *)tables, flags);
+        WFS_LAUNCH_CHECK();
+        return WFS_OK;
+    });
 }
 
 // ---- real-valued results: the reference's TensorEvaluator (src/evaluation/TensorEvaluator.py:70-91) -------------------
@@ -367,7 +362,7 @@ k_metric_pairs_real(const float *__restrict__ params, const float *__restrict__ 
     // in scratch memory
     __shared__ int bins[MP_MAX][MB];
 #endif
-    const long long nv = valid_rows(M, n_dev);
+    const long long nv = wfs_valid_rows_nonneg(M, n_dev);
     const int P = pl.P, C = pl.C, cells1 = pl.cells1;
     for (long long base = (long long)blockIdx.x * MPR_SLICE; base < nv; base += (long long)gridDim.x * MPR_SLICE) {
         if (LDS1D) {
@@ -471,7 +466,7 @@ k_tensor_rows(const CT *__restrict__ c, int c_cols, const T *__restrict__ target
               const float *__restrict__ results, long long N, const long long *__restrict__ n_dev, int nx, int ny,
               float *__restrict__ params, int *__restrict__ category, long long *__restrict__ det,
               int *__restrict__ flags) {
-    const long long nv = valid_rows(N, n_dev);
+    const long long nv = wfs_valid_rows_nonneg(N, n_dev);
     const long long r = (long long)blockIdx.x * MB + threadIdx.x;
     if (r >= N) return;
     if (r >= nv) {                            // beyond the valid count: defined outputs, category -1, nothing read
@@ -550,27 +545,19 @@ extern "C" int wfs_tensor_rows(const void *c, int32_t c_int64, int32_t c_cols, c
     if (N == 0) return WFS_OK;
     const unsigned rb = (unsigned)wfs_cdiv(N, MB);
     hipStream_t s = (hipStream_t)stream;
-#define WFS_TROWS(CT, TYPE)                                                                                            \
-    k_tensor_rows<CT, TYPE><<<rb, MB, 0, s>>>((const CT *)c, c_cols, (const TYPE *)target, P, results, N,              \
-                                              (const long long *)n_dev, nx, ny, params, category,                     \
-                                              (long long *)det_tables, flags)
-#define WFS_TROWS_C(TYPE)                                                                                              \
-    do {                                                                                                               \
-        if (c_int64)                                                                                                   \
-            WFS_TROWS(long long, TYPE);                                                                                \
-        else                                                                                                           \
-            WFS_TROWS(int, TYPE);                                                                                      \
-    } while (0)
-    if (target_dtype == WFS_F32)
-        WFS_TROWS_C(float);
-    else if (target_dtype == WFS_BF16)
-        WFS_TROWS_C(wfs_bf16);
-    else if (target_dtype == WFS_F16)
-        WFS_TROWS_C(wfs_f16);
-    else
-        WFS_TROWS_C(long long);
-#undef WFS_TROWS_C
-#undef WFS_TROWS
-    WFS_LAUNCH_CHECK();
-    return WFS_OK;
+    const auto rows = [&](auto t) -> int {
+        using TYPE = decltype(t);
+        if (c_int64)
+            k_tensor_rows<long long, TYPE><<<rb, MB, 0, s>>>((const long long *)c, c_cols, (const TYPE *)target, P, results, N,
+                                                             (const long long *)n_dev, nx, ny, params, category,
+                                                             (long long *)det_tables, flags);
+        else
+            k_tensor_rows<int, TYPE><<<rb, MB, 0, s>>>((const int *)c, c_cols, (const TYPE *)target, P, results, N,
+                                                       (const long long *)n_dev, nx, ny, params, category,
+                                                       (long long *)det_tables, flags);
+        WFS_LAUNCH_CHECK();
+        return WFS_OK;
+    };
+    if (wfs_dtype_ok(target_dtype)) return wfs_with_dtype(target_dtype, rows);
+    return rows((long long)0);                   // WFS_TENSOR_TARGET_I64: class indices
 }

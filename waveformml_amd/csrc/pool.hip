@@ -21,11 +21,7 @@ namespace {
 constexpr int TB = 256;
 constexpr int GROUP = 9;         // offsets whose gathers are in flight together (27 = 3 groups; a packed 9-row table = 1)
 
-// R = capacity (strides, grid); the number of valid rows comes from device memory when r_dev is given
-__device__ __forceinline__ long long valid_rows(long long R, const long long *r_dev) {
-    long long v = r_dev ? *r_dev : R;
-    return v < R ? v : R;
-}
+// R = capacity (strides, grid); the number of valid rows comes from device memory when r_dev is given (wfs_valid_rows)
 
 template <typename T>
 struct Chunk {                   // 16 bytes of a row
@@ -88,7 +84,7 @@ __global__ void __launch_bounds__(TB) k_maxpool_fwd(const int *__restrict__ tabl
     constexpr int NE = Chunk<T>::NE;
     const int rloc = (int)threadIdx.x / L, sub = (int)threadIdx.x - rloc * L;
     const long long row = (long long)blockIdx.x * rows_pb + rloc;
-    if (rloc >= rows_pb || row >= valid_rows(R, r_dev)) return;
+    if (rloc >= rows_pb || row >= wfs_valid_rows(R, r_dev)) return;
     const unsigned row_bytes = (unsigned)L * 16u;
     // byte offsets below 2 GiB: the dispatcher checks X_rows * row_bytes
     const __amdgpu_buffer_rsrc_t rsrcX = __builtin_amdgcn_make_buffer_rsrc((void *)X, 0, (int)(X_rows * row_bytes), 0x00020000);
@@ -123,7 +119,7 @@ __global__ void __launch_bounds__(TB) k_maxpool_fwd_any(const int *__restrict__ 
     const long long e = (long long)blockIdx.x * TB + threadIdx.x;
     const long long row = e / C;
     const int c = (int)(e - row * C);
-    if (row >= valid_rows(R, r_dev)) return;
+    if (row >= wfs_valid_rows(R, r_dev)) return;
     float y = 0.f;
     for (int k = 0; k < K; ++k) {
         const int nb = table[(long long)k * R + row];
@@ -146,7 +142,7 @@ __global__ void __launch_bounds__(TB) k_maxpool_bwd(const int *__restrict__ tabl
     constexpr int NE = Chunk<T>::NE;
     const int rloc = (int)threadIdx.x / L, sub = (int)threadIdx.x - rloc * L;
     const long long row = (long long)blockIdx.x * rows_pb + rloc;
-    if (rloc >= rows_pb || row >= valid_rows(N, n_dev)) return;
+    if (rloc >= rows_pb || row >= wfs_valid_rows(N, n_dev)) return;
     const unsigned row_bytes = (unsigned)L * 16u;
     const __amdgpu_buffer_rsrc_t rsrcY = __builtin_amdgcn_make_buffer_rsrc((void *)Y, 0, (int)(M_rows * row_bytes), 0x00020000);
     const __amdgpu_buffer_rsrc_t rsrcG = __builtin_amdgcn_make_buffer_rsrc((void *)dY, 0, (int)(M_rows * row_bytes), 0x00020000);
@@ -188,7 +184,7 @@ __global__ void __launch_bounds__(TB) k_maxpool_bwd_any(const int *__restrict__ 
     const long long e = (long long)blockIdx.x * TB + threadIdx.x;
     const long long row = e / C;
     const int c = (int)(e - row * C);
-    if (row >= valid_rows(N, n_dev)) return;
+    if (row >= wfs_valid_rows(N, n_dev)) return;
     const float x = wfs_ld(X + row * C + c);
     float acc = 0.f;
     for (int k = 0; k < TR; ++k) {
@@ -199,11 +195,9 @@ __global__ void __launch_bounds__(TB) k_maxpool_bwd_any(const int *__restrict__ 
     wfs_st(dX + row * C + c, acc);
 }
 
-inline int elem_size(int dtype) { return dtype == WFS_F32 ? 4 : 2; }
-
 // rows as whole 16-byte chunks, at most one block wide, gathered rows addressable through 32-bit byte offsets
 inline bool vector_rows(int C, int dtype, long long gathered_rows) {
-    const long long row_bytes = (long long)C * elem_size(dtype);
+    const long long row_bytes = (long long)C * wfs_dtype_bytes(dtype);
     return row_bytes % 16 == 0 && row_bytes / 16 <= TB && gathered_rows * row_bytes < (1ll << 31);
 }
 
@@ -229,31 +223,24 @@ extern "C" int wfs_maxpool_fwd(const int32_t *table, const int32_t *kmap_host, i
     WFS_REQUIRE(table && Y && (X || X_rows == 0), WFS_EINVAL, "NULL device pointer");
     if (vector_rows(C, dtype, X_rows)) {
         WFS_REQUIRE((((uintptr_t)X | (uintptr_t)Y) & 15) == 0, WFS_EINVAL, "rows must be 16-byte aligned");
-        const int L = C * elem_size(dtype) / 16, rows_pb = TB / L;
+        const int L = C * wfs_dtype_bytes(dtype) / 16, rows_pb = TB / L;
         const dim3 grid((unsigned)wfs_cdiv(R, rows_pb)), block(TB);
-        if (dtype == WFS_F32)
-            k_maxpool_fwd<float><<<grid, block, 0, stream>>>(table, K, R, r_dev, (const float *)X, X_rows, L, rows_pb, (float *)Y);
-        else if (dtype == WFS_BF16)
-            k_maxpool_fwd<wfs_bf16><<<grid, block, 0, stream>>>(table, K, R, r_dev, (const wfs_bf16 *)X, X_rows, L, rows_pb,
-                                                                (wfs_bf16 *)Y);
-        else
-            k_maxpool_fwd<wfs_f16><<<grid, block, 0, stream>>>(table, K, R, r_dev, (const wfs_f16 *)X, X_rows, L, rows_pb,
-                                                               (wfs_f16 *)Y);
-    } else {
-        const long long blocks = wfs_cdiv((long long)R * C, TB);
-        WFS_REQUIRE(blocks < (1ll << 31), WFS_EINVAL, "%lld x %d elements are too many for one launch", (long long)R, C);
-        const dim3 grid((unsigned)blocks), block(TB);
-        if (dtype == WFS_F32)
-            k_maxpool_fwd_any<float><<<grid, block, 0, stream>>>(table, K, R, r_dev, (const float *)X, X_rows, C, (float *)Y);
-        else if (dtype == WFS_BF16)
-            k_maxpool_fwd_any<wfs_bf16><<<grid, block, 0, stream>>>(table, K, R, r_dev, (const wfs_bf16 *)X, X_rows, C,
-                                                                    (wfs_bf16 *)Y);
-        else
-            k_maxpool_fwd_any<wfs_f16><<<grid, block, 0, stream>>>(table, K, R, r_dev, (const wfs_f16 *)X, X_rows, C,
-                                                                   (wfs_f16 *)Y);
+        return wfs_with_dtype(dtype, [&](auto t) -> int {
+            using T = decltype(t);
+            k_maxpool_fwd<T><<<grid, block, 0, stream>>>(table, K, R, r_dev, (const T *)X, X_rows, L, rows_pb, (T *)Y);
+            WFS_LAUNCH_CHECK();
+            return WFS_OK;
+        });
     }
-    WFS_LAUNCH_CHECK();
-    return WFS_OK;
+    const long long blocks = wfs_cdiv((long long)R * C, TB);
+    WFS_REQUIRE(blocks < (1ll << 31), WFS_EINVAL, "%lld x %d elements are too many for one launch", (long long)R, C);
+    const dim3 grid((unsigned)blocks), block(TB);
+    return wfs_with_dtype(dtype, [&](auto t) -> int {
+        using T = decltype(t);
+        k_maxpool_fwd_any<T><<<grid, block, 0, stream>>>(table, K, R, r_dev, (const T *)X, X_rows, C, (T *)Y);
+        WFS_LAUNCH_CHECK();
+        return WFS_OK;
+    });
 }
 
 // does wfs_maxpool_bwd take the packed by-input table [K / kl, N] of wfs_event_rulebook_conv as it is?
@@ -275,32 +262,35 @@ extern "C" int wfs_maxpool_bwd(const int32_t *table, int32_t K, int32_t packed_k
     if (N == 0) return WFS_OK;
     WFS_REQUIRE(table && X && dX && ((Y && dY) || M_rows == 0), WFS_EINVAL, "NULL device pointer");
     const int TR = packed_kl ? K / packed_kl : K;
-#define WFS_POOL_BWD(KERNEL, T, ...)                                                                              \
-    do {                                                                                                          \
-        if (packed_kl)                                                                                            \
-            KERNEL<T, true><<<grid, block, 0, stream>>>(table, TR, N, n_dev, (const T *)X, (const T *)Y, (const T *)dY, \
-                                                        M_rows, __VA_ARGS__, (T *)dX);                            \
-        else                                                                                                      \
-            KERNEL<T, false><<<grid, block, 0, stream>>>(table, TR, N, n_dev, (const T *)X, (const T *)Y, (const T *)dY, \
-                                                         M_rows, __VA_ARGS__, (T *)dX);                           \
-    } while (0)
     if (vector_rows(C, dtype, M_rows)) {
         WFS_REQUIRE((((uintptr_t)X | (uintptr_t)Y | (uintptr_t)dY | (uintptr_t)dX) & 15) == 0, WFS_EINVAL,
                     "rows must be 16-byte aligned");
-        const int L = C * elem_size(dtype) / 16, rows_pb = TB / L;
+        const int L = C * wfs_dtype_bytes(dtype) / 16, rows_pb = TB / L;
         const dim3 grid((unsigned)wfs_cdiv(N, rows_pb)), block(TB);
-        if (dtype == WFS_F32) WFS_POOL_BWD(k_maxpool_bwd, float, L, rows_pb);
-        else if (dtype == WFS_BF16) WFS_POOL_BWD(k_maxpool_bwd, wfs_bf16, L, rows_pb);
-        else WFS_POOL_BWD(k_maxpool_bwd, wfs_f16, L, rows_pb);
-    } else {
-        const long long blocks = wfs_cdiv((long long)N * C, TB);
-        WFS_REQUIRE(blocks < (1ll << 31), WFS_EINVAL, "%lld x %d elements are too many for one launch", (long long)N, C);
-        const dim3 grid((unsigned)blocks), block(TB);
-        if (dtype == WFS_F32) WFS_POOL_BWD(k_maxpool_bwd_any, float, C);
-        else if (dtype == WFS_BF16) WFS_POOL_BWD(k_maxpool_bwd_any, wfs_bf16, C);
-        else WFS_POOL_BWD(k_maxpool_bwd_any, wfs_f16, C);
+        return wfs_with_dtype(dtype, [&](auto t) -> int {
+            using T = decltype(t);
+            if (packed_kl)
+                k_maxpool_bwd<T, true><<<grid, block, 0, stream>>>(table, TR, N, n_dev, (const T *)X, (const T *)Y,
+                                                                   (const T *)dY, M_rows, L, rows_pb, (T *)dX);
+            else
+                k_maxpool_bwd<T, false><<<grid, block, 0, stream>>>(table, TR, N, n_dev, (const T *)X, (const T *)Y,
+                                                                    (const T *)dY, M_rows, L, rows_pb, (T *)dX);
+            WFS_LAUNCH_CHECK();
+            return WFS_OK;
+        });
     }
-#undef WFS_POOL_BWD
-    WFS_LAUNCH_CHECK();
-    return WFS_OK;
+    const long long blocks = wfs_cdiv((long long)N * C, TB);
+    WFS_REQUIRE(blocks < (1ll << 31), WFS_EINVAL, "%lld x %d elements are too many for one launch", (long long)N, C);
+    const dim3 grid((unsigned)blocks), block(TB);
+    return wfs_with_dtype(dtype, [&](auto t) -> int {
+        using T = decltype(t);
+        if (packed_kl)
+            k_maxpool_bwd_any<T, true><<<grid, block, 0, stream>>>(table, TR, N, n_dev, (const T *)X, (const T *)Y,
+                                                                   (const T *)dY, M_rows, C, (T *)dX);
+        else
+            k_maxpool_bwd_any<T, false><<<grid, block, 0, stream>>>(table, TR, N, n_dev, (const T *)X, (const T *)Y,
+                                                                    (const T *)dY, M_rows, C, (T *)dX);
+        WFS_LAUNCH_CHECK();
+        return WFS_OK;
+    });
 }

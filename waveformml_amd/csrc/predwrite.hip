@@ -187,15 +187,12 @@ void launch_feats(const unsigned char *rec, long long n, long long item, long lo
     const long long total = cap * half;
     const int small = total < (1ll << 31) ? 1 : 0;
     const dim3 grid(grid_for(total)), block(256);
-    if (dtype == WFS_F32)
-        k_pp_feats<KIND, A4, float><<<grid, block, 0, stream>>>(rec, n, item, coord_off, feat_off, half, gain, nx, ny, cap,
-                                                                (float *)feats, small);
-    else if (dtype == WFS_BF16)
-        k_pp_feats<KIND, A4, wfs_bf16><<<grid, block, 0, stream>>>(rec, n, item, coord_off, feat_off, half, gain, nx, ny, cap,
-                                                                   (wfs_bf16 *)feats, small);
-    else
-        k_pp_feats<KIND, A4, wfs_f16><<<grid, block, 0, stream>>>(rec, n, item, coord_off, feat_off, half, gain, nx, ny, cap,
-                                                                  (wfs_f16 *)feats, small);
+    wfs_with_dtype(dtype, [&](auto t) -> int {
+        using T = decltype(t);
+        k_pp_feats<KIND, A4, T><<<grid, block, 0, stream>>>(rec, n, item, coord_off, feat_off, half, gain, nx, ny, cap,
+                                                            (T *)feats, small);
+        return WFS_OK;
+    });
 }
 
 template <bool A4>
@@ -205,15 +202,12 @@ void launch_scatter(unsigned char *rec, long long n, long long item, long long m
     const long long total = n * L;
     const int small = total < (1ll << 31) ? 1 : 0;
     const dim3 grid(grid_for(total)), block(256);
-    if (dtype == WFS_F32)
-        k_ps_scatter<A4, float><<<grid, block, 0, stream>>>(rec, n, item, member_off, col0, L, coords, (const float *)src,
-                                                            mode, B, nx, ny, affine, sub, mul, small);
-    else if (dtype == WFS_BF16)
-        k_ps_scatter<A4, wfs_bf16><<<grid, block, 0, stream>>>(rec, n, item, member_off, col0, L, coords,
-                                                               (const wfs_bf16 *)src, mode, B, nx, ny, affine, sub, mul, small);
-    else
-        k_ps_scatter<A4, wfs_f16><<<grid, block, 0, stream>>>(rec, n, item, member_off, col0, L, coords,
-                                                              (const wfs_f16 *)src, mode, B, nx, ny, affine, sub, mul, small);
+    wfs_with_dtype(dtype, [&](auto t) -> int {
+        using T = decltype(t);
+        k_ps_scatter<A4, T><<<grid, block, 0, stream>>>(rec, n, item, member_off, col0, L, coords, (const T *)src, mode, B, nx,
+                                                        ny, affine, sub, mul, small);
+        return WFS_OK;
+    });
 }
 
 }  // namespace

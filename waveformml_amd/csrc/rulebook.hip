@@ -127,15 +127,11 @@ __device__ __forceinline__ int in_key(const Geo &g, const int *x, int b) {
 // info[0] = M, info[1] = duplicate coordinates seen, info[2] = out-of-range index seen
 // Row counts: N is the CAPACITY (array strides, grid size); when n_dev is given the number of valid rows is
 // read from device memory, so that a build never needs the host to know it (HIP-graph capturable steps).
-__device__ __forceinline__ long long valid_rows(long long N, const long long *n_dev) {
-    long long v = n_dev ? *n_dev : N;
-    return v < N ? v : N;
-}
 
 __global__ void k_site_insert(Geo g, int batch, const int *idx, long long N, const long long *n_dev, Table t, int *vals,
                               long long *info) {
     long long j = (long long)blockIdx.x * TB + threadIdx.x;
-    if (j >= valid_rows(N, n_dev)) return;
+    if (j >= wfs_valid_rows(N, n_dev)) return;
     int x[4], b;
     if (!load_row(g, idx, j, x, b, batch)) {
         info[2] = 1;
@@ -186,7 +182,7 @@ __global__ void __launch_bounds__(TB) k_subm_lookup2(Geo g, int batch, const int
                                                      int *__restrict__ nbr_out) {
     const int k = __builtin_amdgcn_readfirstlane(blockIdx.y * 4 + (threadIdx.x >> 6));
     const long long j = (long long)blockIdx.x * 64 + (threadIdx.x & 63);
-    if (k >= g.K || j >= valid_rows(N, n_dev)) return;
+    if (k >= g.K || j >= wfs_valid_rows(N, n_dev)) return;
     int x[4], b;
     bool ok = load_row(g, idx, j, x, b, batch);
     int res = -1;
@@ -211,7 +207,7 @@ __global__ void __launch_bounds__(TB) k_subm_lookup_runs(Geo g, int batch, const
     const int kl = g.ksize[last];
     const int q = __builtin_amdgcn_readfirstlane(blockIdx.y * 4 + (threadIdx.x >> 6));
     const long long j = (long long)blockIdx.x * 64 + (threadIdx.x & 63);
-    if (q * kl >= g.K || j >= valid_rows(N, n_dev)) return;
+    if (q * kl >= g.K || j >= wfs_valid_rows(N, n_dev)) return;
     int x[4], b;
     bool ok = load_row(g, idx, j, x, b, batch);
     // leading offsets of q (row-major over the leading kernel dims), prefix of the key
@@ -251,7 +247,7 @@ __global__ void __launch_bounds__(TB) k_conv_insert2(Geo g, int batch, const int
                                                      int *__restrict__ nbr_out, long long *info) {
     const int k = __builtin_amdgcn_readfirstlane(blockIdx.y * 4 + (threadIdx.x >> 6));
     const long long j = (long long)blockIdx.x * 64 + (threadIdx.x & 63);
-    if (k >= g.K || j >= valid_rows(N, n_dev)) return;
+    if (k >= g.K || j >= wfs_valid_rows(N, n_dev)) return;
     int x[4], b;
     bool ok = load_row(g, idx, j, x, b, batch);
     if (!ok) info[2] = 1;
@@ -276,7 +272,7 @@ __global__ void __launch_bounds__(TB) k_conv_insert_runs(Geo g, int batch, const
     const int kl = g.ksize[last], sl = g.stride[last];
     const int q = __builtin_amdgcn_readfirstlane(blockIdx.y * 4 + (threadIdx.x >> 6));
     const long long j = (long long)blockIdx.x * 64 + (threadIdx.x & 63);
-    if (q * kl >= g.K || j >= valid_rows(N, n_dev)) return;
+    if (q * kl >= g.K || j >= wfs_valid_rows(N, n_dev)) return;
     int x[4], b;
     bool ok = load_row(g, idx, j, x, b, batch);
     if (!ok) info[2] = 1;
@@ -331,7 +327,7 @@ __global__ void __launch_bounds__(TB) k_conv_assign2(Geo g, long long N, const l
     }
     const int k = __builtin_amdgcn_readfirstlane(blockIdx.y * 4 + (threadIdx.x >> 6));
     const long long j = (long long)blockIdx.x * 64 + (threadIdx.x & 63);
-    if (k >= g.K || j >= valid_rows(N, n_dev)) return;
+    if (k >= g.K || j >= wfs_valid_rows(N, n_dev)) return;
     const unsigned m = rowmask[j];
     if (!((m >> k) & 1u)) return;
     const int s = nbr_out[(long long)k * N + j];
@@ -362,7 +358,7 @@ __global__ void __launch_bounds__(TB) k_conv_finalize2(int K, long long N, const
     const long long j = (long long)blockIdx.x * 64 + (threadIdx.x & 63);
     // STICKY: set when M exceeded the capacity, never cleared here (the reader clears it)
     if (overflow && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0 && info[0] > M) *overflow = 1;
-    if (k >= K || j >= valid_rows(N, n_dev)) return;
+    if (k >= K || j >= wfs_valid_rows(N, n_dev)) return;
     int s = nbr_out[(long long)k * N + j];
     if (s < 0) return;
     int id = slot_id[s];
@@ -375,7 +371,7 @@ __global__ void __launch_bounds__(TB) k_conv_finalize2(int K, long long N, const
 __global__ void k_conv_insert(Geo g, int batch, const int *idx, long long N, const long long *n_dev, Table t,
                               unsigned long long *ticket, int *nbr_out, long long *info) {
     long long j = (long long)blockIdx.x * TB + threadIdx.x;
-    if (j >= valid_rows(N, n_dev)) return;
+    if (j >= wfs_valid_rows(N, n_dev)) return;
     int x[4], b;
     bool ok = load_row(g, idx, j, x, b, batch);
     if (!ok) info[2] = 1;
@@ -398,7 +394,7 @@ __global__ void k_conv_rowcount(int K, long long N, const long long *n_dev, cons
                                 const unsigned long long *ticket, int *rowfirst) {
     long long j = (long long)blockIdx.x * TB + threadIdx.x;
     if (j >= N) return;
-    if (j >= valid_rows(N, n_dev)) {       // the scan runs over the capacity
+    if (j >= wfs_valid_rows(N, n_dev)) {       // the scan runs over the capacity
         rowfirst[j] = 0;
         return;
     }
@@ -414,7 +410,7 @@ __global__ void k_conv_assign(Geo g, long long N, const long long *n_dev, long l
                               const unsigned long long *ticket, const int *rowbase, Table t, int *slot_id,
                               int *out_indices, long long *info) {
     long long j = (long long)blockIdx.x * TB + threadIdx.x;
-    if (j >= valid_rows(N, n_dev)) return;
+    if (j >= wfs_valid_rows(N, n_dev)) return;
     int id = rowbase[j];
     for (int k = 0; k < g.K; ++k) {
         int s = nbr_out[(long long)k * N + j];
@@ -440,7 +436,7 @@ __global__ void k_conv_assign(Geo g, long long N, const long long *n_dev, long l
 __global__ void k_conv_finalize(int K, long long N, const long long *n_dev, long long M, int *nbr_out,
                                 const int *slot_id, int *nbr_in) {
     long long j = (long long)blockIdx.x * TB + threadIdx.x;
-    if (j >= valid_rows(N, n_dev)) return;
+    if (j >= wfs_valid_rows(N, n_dev)) return;
     for (int k = 0; k < K; ++k) {
         int s = nbr_out[(long long)k * N + j];
         if (s >= 0) {
@@ -456,7 +452,7 @@ __global__ void k_conv_finalize(int K, long long N, const long long *n_dev, long
 __global__ void k_invert_table(int K, long long N, const long long *n_dev, long long M, const int *nbr_out,
                                int *nbr_in) {
     long long j = (long long)blockIdx.x * TB + threadIdx.x;
-    if (j >= valid_rows(N, n_dev)) return;
+    if (j >= wfs_valid_rows(N, n_dev)) return;
     for (int k = 0; k < K; ++k) {
         int i = nbr_out[(long long)k * N + j];
         if (i >= 0) atomicMax(&nbr_in[(long long)k * M + i], (int)j);
@@ -506,7 +502,7 @@ __device__ __forceinline__ int scan_item(const int *in, long long i, long long n
 
 __global__ void k_scan_blocksum(const int *in, long long n, const long long *n_dev, int popc, int *bsum) {
     long long base = (long long)blockIdx.x * SCAN_TILE + threadIdx.x * SCAN_ITEMS;
-    const long long nv = valid_rows(n, n_dev);
+    const long long nv = wfs_valid_rows(n, n_dev);
     int v = 0;
 #pragma unroll
     for (int i = 0; i < SCAN_ITEMS; ++i) v += scan_item(in, base + i, n, nv, popc);
@@ -532,7 +528,7 @@ __global__ void k_scan_top(int *bsum, long long nb, long long *total, long long 
 }
 __global__ void k_scan_apply(const int *in, long long n, const long long *n_dev, int popc, const int *bsum, int *out) {
     long long base = (long long)blockIdx.x * SCAN_TILE + threadIdx.x * SCAN_ITEMS;
-    const long long nv = valid_rows(n, n_dev);
+    const long long nv = wfs_valid_rows(n, n_dev);
     int vals[SCAN_ITEMS];
     int v = 0;
 #pragma unroll
@@ -568,7 +564,7 @@ __global__ void __launch_bounds__(TB) k_conv_first_bsum(int K, long long N, cons
                                                         const unsigned *__restrict__ ticket,
                                                         unsigned *__restrict__ rowmask, int *__restrict__ bsum) {
     const long long j = (long long)blockIdx.x * TB + threadIdx.x;
-    const long long nv = valid_rows(N, n_dev);
+    const long long nv = wfs_valid_rows(N, n_dev);
     const bool live = j < nv;
     const long long jc = live ? j : 0;
     int s[32];
@@ -616,7 +612,7 @@ __global__ void __launch_bounds__(TB) k_conv_rowbase(long long N, const unsigned
 __global__ void __launch_bounds__(TB) k_flip_rows(int K, long long n, const long long *n_dev, int *__restrict__ t) {
     const long long j = (long long)blockIdx.x * TB + threadIdx.x;
     const int k = blockIdx.y;
-    const long long nv = n_dev ? (*n_dev < n ? *n_dev : n) : n;
+    const long long nv = wfs_valid_rows(n, n_dev);
     if (j >= nv || 2 * k + 1 >= K) return;
     const int a = t[(long long)k * n + j], b = t[(long long)(K - 1 - k) * n + j];
     t[(long long)k * n + j] = b;
@@ -629,7 +625,7 @@ __global__ void k_compact_count(int K, long long N, const long long *n_dev, long
                                 int *tcount) {
     __shared__ int wsum[TB / 64];
     long long j = (long long)blockIdx.x * TB + threadIdx.x;
-    const long long Nv = valid_rows(N, n_dev);
+    const long long Nv = wfs_valid_rows(N, n_dev);
     int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     for (int k = 0; k < K; ++k) {
         bool v = j < Nv && nbr_out[(long long)k * N + j] >= 0;
@@ -663,7 +659,7 @@ __global__ void k_compact_write(int K, long long N, const long long *n_dev, long
                                 const int *tcount, const int *pair_num, int *pairs) {
     __shared__ int wsum[TB / 64];
     long long j = (long long)blockIdx.x * TB + threadIdx.x;
-    const long long Nv = valid_rows(N, n_dev);
+    const long long Nv = wfs_valid_rows(N, n_dev);
     int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     for (int k = 0; k < K; ++k) {
         int o = j < Nv ? nbr_out[(long long)k * N + j] : -1;

@@ -97,7 +97,7 @@ k_mrl_forward(MrlIn in, long long n_chunks, unsigned *__restrict__ ticket, doubl
               float *__restrict__ out, long long *__restrict__ count) {
     __shared__ double sa[MRL_THREADS], sb[MRL_THREADS];
     __shared__ long long sc[MRL_THREADS];
-    const long long nv = valid_rows(in.n_cap, in.n_dev);
+    const long long nv = wfs_valid_rows_nonneg(in.n_cap, in.n_dev);
     const int t = threadIdx.x;
     for (long long ch = blockIdx.x; ch < n_chunks; ch += gridDim.x) {
         double a = 0.0, b = 0.0;
@@ -156,7 +156,7 @@ __global__ void __launch_bounds__(MRL_THREADS)
 k_mrl_backward(MrlIn in, const long long *__restrict__ count, const float *__restrict__ grad, void *__restrict__ dpred) {
     const long long r = (long long)blockIdx.x * MRL_THREADS + threadIdx.x;
     if (r >= in.n_cap) return;
-    const long long nv = valid_rows(in.n_cap, in.n_dev), cnt = *count;
+    const long long nv = wfs_valid_rows_nonneg(in.n_cap, in.n_dev), cnt = *count;
     float v = 0.f;
     if (cnt > 0 && r < nv && mrl_counted(in, r)) {
         const double d = ld_real(in.pred, in.pred_dtype, r) - ld_real(in.target, in.target_dtype, r * in.n_cols + in.col);
@@ -200,7 +200,7 @@ k_segq_rows(const int *__restrict__ coords, const void *__restrict__ results, in
     __shared__ int srows[SEGQ_SLOTS];
     if (threadIdx.x < SEGQ_SLOTS) smax[threadIdx.x] = 0ull, srows[threadIdx.x] = 0;
     __syncthreads();
-    const long long nv = valid_rows(n_cap, n_dev);
+    const long long nv = wfs_valid_rows_nonneg(n_cap, n_dev);
     const long long r = (long long)blockIdx.x * MB + threadIdx.x;
     if (r < n_cap) {
         // a row that is not scored (beyond the valid count or flagged) still gets defined outputs
@@ -285,7 +285,7 @@ k_segq_bins(const void *__restrict__ results, int r_dtype, const void *__restric
             int t_index, const double *__restrict__ error, const int *__restrict__ category, long long n_cap,
             const long long *__restrict__ n_dev, int C, int nb, const double *__restrict__ edges,
             const int *__restrict__ edges_set, long long *__restrict__ hist, long long *__restrict__ hist2d) {
-    const long long nv = valid_rows(n_cap, n_dev);
+    const long long nv = wfs_valid_rows_nonneg(n_cap, n_dev);
     const long long r = (long long)blockIdx.x * MB + threadIdx.x;
     if (r >= nv) return;
     const int c = category[r];

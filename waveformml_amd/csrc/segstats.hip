@@ -113,7 +113,7 @@ __global__ void __launch_bounds__(SB)
 k_seg_z(const int *__restrict__ coords, long long n_cap, const long long *__restrict__ n_dev, int B, Plane pred,
         Plane targ, Plane ene, const float *__restrict__ seg, const int *__restrict__ sample_segs, ZBins Z,
         const int *__restrict__ off, long long *__restrict__ tab, int *__restrict__ flags) {
-    const long long nv = valid_rows(n_cap, n_dev);
+    const long long nv = wfs_valid_rows_nonneg(n_cap, n_dev);
     const long long r = (long long)blockIdx.x * SB + threadIdx.x;
     if (r >= nv) return;
     const RowHead h = row_head(coords, r, off, B, Z.nx, Z.ny, Z.nmult, flags);
@@ -157,7 +157,7 @@ __global__ void __launch_bounds__(SB)
 k_seg_energy(const int *__restrict__ coords, long long n_cap, const long long *__restrict__ n_dev, int B, Plane pred,
              Plane targ, const float *__restrict__ seg, EBins Eb, const int *__restrict__ off,
              long long *__restrict__ tab, int *__restrict__ flags) {
-    const long long nv = valid_rows(n_cap, n_dev);
+    const long long nv = wfs_valid_rows_nonneg(n_cap, n_dev);
     const long long r = (long long)blockIdx.x * SB + threadIdx.x;
     if (r >= nv) return;
     const RowHead h = row_head(coords, r, off, B, Eb.nx, Eb.ny, Eb.nmult, flags);

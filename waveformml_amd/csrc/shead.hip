@@ -28,10 +28,6 @@ namespace {
 constexpr int SH_CELLS = 64;          // cells per block = lanes of a wave
 constexpr int SH_EVENTS = 16;         // events per slice
 
-__device__ __forceinline__ long long valid_rows(long long R, const long long *r_dev) {
-    long long v = r_dev ? *r_dev : R;
-    return v < R ? v : R;
-}
 
 __device__ __forceinline__ void store8(float *p, const float *x) {
     *(float4 *)p = float4{x[0], x[1], x[2], x[3]};
@@ -107,7 +103,7 @@ __global__ void __launch_bounds__(512) k_shead_fwd(const H *__restrict__ X, cons
     const int cell = tile * SH_CELLS + lane;
     const bool in = cell < V;
     const int cc = in ? cell : V - 1;
-    const long long Mv = valid_rows(M, m_dev);
+    const long long Mv = wfs_valid_rows(M, m_dev);
     // every load of the thread is issued before the first use: weights (coalesced over the cells), the slice's map
     // entries, then the rows they name
     float w[O][8];
@@ -192,7 +188,7 @@ __global__ void __launch_bounds__(512) k_shead_bwd(const H *__restrict__ X, cons
     const int cell = tile * SH_CELLS + lane;
     const bool in = cell < V;
     const int cc = in ? cell : V - 1;
-    const long long Mv = valid_rows(M, m_dev);
+    const long long Mv = wfs_valid_rows(M, m_dev);
     float w[O][8];
     if (dX) {
 #pragma unroll
@@ -294,14 +290,6 @@ extern "C" size_t wfs_sparse_head_workspace_bytes(int32_t batch, int64_t V, int3
     return fwd > bwd ? fwd : bwd;
 }
 
-#define WFS_SH_DISPATCH(O, CALL)                      \
-    switch (O) {                                      \
-        case 1: { constexpr int OO = 1; CALL; } break; \
-        case 2: { constexpr int OO = 2; CALL; } break; \
-        case 3: { constexpr int OO = 3; CALL; } break; \
-        default: { constexpr int OO = 4; CALL; } break; \
-    }
-
 extern "C" int wfs_sparse_head_fwd(const void *X, const uint32_t *ticket, const int32_t *slot_id, int64_t M,
                                    const int64_t *m_dev, int32_t batch, int64_t V, int32_t C, const float *W,
                                    const float *bias, int32_t O, float *Y, int32_t dtype, void *workspace,
@@ -314,12 +302,17 @@ extern "C" int wfs_sparse_head_fwd(const void *X, const uint32_t *ticket, const 
     const dim3 grid((unsigned)sh_tiles(V), (unsigned)sh_slices(batch)), block(64 * (C / 8));
     float *part = (float *)workspace;
     const long long *md = (const long long *)m_dev;
-#define WFS_SHF(T)                                                                                                      \
-    WFS_SH_DISPATCH(O, (k_shead_fwd<T, OO><<<grid, block, fwd_lds(C / 8, OO), stream>>>((const T *)X, ticket, slot_id, M, md, \
-                                                                                         batch, (int)V, C, W, part)))
-    if (dtype == WFS_F32) { WFS_SHF(float); } else if (dtype == WFS_BF16) { WFS_SHF(wfs_bf16); } else { WFS_SHF(wfs_f16); }
-#undef WFS_SHF
-    WFS_LAUNCH_CHECK();
+    int rc = wfs_with_dtype(dtype, [&](auto t) -> int {
+        using T = decltype(t);
+        return wfs_with_int<1, 2, 3, 4>(O, [&](auto o) -> int {
+            constexpr int OO = decltype(o)::value;
+            k_shead_fwd<T, OO><<<grid, block, fwd_lds(C / 8, OO), stream>>>((const T *)X, ticket, slot_id, M, md, batch, (int)V,
+                                                                             C, W, part);
+            WFS_LAUNCH_CHECK();
+            return WFS_OK;
+        });
+    });
+    if (rc != WFS_OK) return rc;
     k_shead_sum<<<dim3((unsigned)wfs_cdiv((long long)batch * O, 256)), dim3(256), 0, stream>>>(part, sh_tiles(V), batch, O,
                                                                                                bias, Y);
     WFS_LAUNCH_CHECK();
@@ -334,7 +327,7 @@ extern "C" int wfs_sparse_head_bwd(const void *X, const float *G, const uint32_t
     WFS_REQUIRE(wfs_sparse_head_ok(batch, V, C, O, dtype), WFS_EINVAL, "wfs_sparse_head_bwd: shape not covered (wfs_sparse_head_ok)");
     WFS_REQUIRE(X && G && ticket && slot_id && W, WFS_EINVAL, "NULL device pointer");
     WFS_REQUIRE(!dB || dW, WFS_EINVAL, "dB comes with dW");
-    if (defer) *defer = wfs_dw_job{nullptr, 0, 0, 0, 0, 0, 0, nullptr};
+    if (defer) *defer = wfs_dw_job_none();
     if (!dX && !dW) return WFS_OK;
     float *part = nullptr;
     if (dW) {
@@ -344,12 +337,16 @@ extern "C" int wfs_sparse_head_bwd(const void *X, const float *G, const uint32_t
     }
     const dim3 grid((unsigned)sh_tiles(V), (unsigned)sh_slices(batch)), block(64 * (C / 8));
     const long long *md = (const long long *)m_dev;
-#define WFS_SHB(T)                                                                                                      \
-    WFS_SH_DISPATCH(O, (k_shead_bwd<T, OO><<<grid, block, 0, stream>>>((const T *)X, G, ticket, slot_id, M, md, batch, (int)V, \
-                                                                        C, W, (T *)dX, part, dB)))
-    if (dtype == WFS_F32) { WFS_SHB(float); } else if (dtype == WFS_BF16) { WFS_SHB(wfs_bf16); } else { WFS_SHB(wfs_f16); }
-#undef WFS_SHB
-    WFS_LAUNCH_CHECK();
+    int rc = wfs_with_dtype(dtype, [&](auto t) -> int {
+        using T = decltype(t);
+        return wfs_with_int<1, 2, 3, 4>(O, [&](auto o) -> int {
+            k_shead_bwd<T, decltype(o)::value><<<grid, block, 0, stream>>>((const T *)X, G, ticket, slot_id, M, md, batch,
+                                                                            (int)V, C, W, (T *)dX, part, dB);
+            WFS_LAUNCH_CHECK();
+            return WFS_OK;
+        });
+    });
+    if (rc != WFS_OK) return rc;
     if (!dW) return WFS_OK;
     const long long per = (long long)O * C * V;
     const wfs_dw_job job = {part, sh_slices(batch), per, 1, 1, 1, 0, dW};

@@ -217,31 +217,13 @@ __global__ void __launch_bounds__(TBW) k_tcn_bwd(const T *__restrict__ X, const 
     for (int t = threadIdx.x; t < L; t += nthr) wfs_st(dx + t, G[t]);
 }
 
-// f(Inst<T, K>) for the rows' dtype and the kernel size: what the two entry points instantiate their kernels through
-// (3 dtypes x k = 1 .. 8 each)
-template <typename T_, int K_>
-struct Inst {
-    using T = T_;
-    static constexpr int K = K_;
-};
-template <typename T, typename F>
-int with_k(int k, F &f) {
-    switch (k) {
-        case 1: return f(Inst<T, 1>());
-        case 2: return f(Inst<T, 2>());
-        case 3: return f(Inst<T, 3>());
-        case 4: return f(Inst<T, 4>());
-        case 5: return f(Inst<T, 5>());
-        case 6: return f(Inst<T, 6>());
-        case 7: return f(Inst<T, 7>());
-        default: return f(Inst<T, 8>());
-    }
-}
+// f(T{}, std::integral_constant<int, K>{}) for the rows' dtype and the kernel size: what the two entry points instantiate
+// their kernels through (3 dtypes x k = 1 .. 8 each)
 template <typename F>
 int with_dtype_k(int dtype, int k, F f) {
-    if (dtype == WFS_F32) return with_k<float>(k, f);
-    if (dtype == WFS_BF16) return with_k<wfs_bf16>(k, f);
-    return with_k<wfs_f16>(k, f);
+    return wfs_with_dtype(dtype, [&](auto t) -> int {
+        return wfs_with_int<1, 2, 3, 4, 5, 6, 7, 8>(k, [&](auto k_c) -> int { return f(t, k_c); });
+    });
 }
 
 int check_common(int32_t L, int32_t levels, int32_t k, int32_t dtype, float dropout_p, const int64_t *seed_dev) {
@@ -270,12 +252,12 @@ extern "C" int wfs_tcn_fwd(const void *X, int64_t N, int32_t L, const float *tap
     WFS_REQUIRE(X && Y && taps && bias, WFS_EINVAL, "NULL device pointer");
     const size_t lds = wfs_tcn_lds_bytes(L, levels, 0);
     const dim3 grid((unsigned)N), block(TB);
-    return with_dtype_k(dtype, k, [&](auto inst) {
-        using T = typename decltype(inst)::T;
-        k_tcn_fwd<T, decltype(inst)::K><<<grid, block, lds, stream>>>((const T *)X, N, L, taps, bias, levels, (T *)Y, dropout_p,
-                                                                       seed_dev);
+    return with_dtype_k(dtype, k, [&](auto t, auto k_c) -> int {
+        using T = decltype(t);
+        k_tcn_fwd<T, decltype(k_c)::value><<<grid, block, lds, stream>>>((const T *)X, N, L, taps, bias, levels, (T *)Y,
+                                                                          dropout_p, seed_dev);
         WFS_LAUNCH_CHECK();
-        return (int)WFS_OK;
+        return WFS_OK;
     });
 }
 
@@ -292,9 +274,9 @@ extern "C" int wfs_tcn_bwd(const void *X, const void *dY, int64_t N, int32_t L, 
     WFS_REQUIRE(X && dY && dX && partial && taps && bias, WFS_EINVAL, "NULL device pointer");
     // rows that leave room for one or two blocks per CU get a 16-wave block, short rows keep 4 waves and more blocks
     const dim3 grid((unsigned)N), block(lds > 48 * 1024 ? TBW : TB);
-    return with_dtype_k(dtype, k, [&](auto inst) {
-        using T = typename decltype(inst)::T;
-        constexpr int K = decltype(inst)::K;
+    return with_dtype_k(dtype, k, [&](auto t, auto k_c) -> int {
+        using T = decltype(t);
+        constexpr int K = decltype(k_c)::value;
         static bool attr_done = false;          // one per instantiation (T, K): its first launch raises the LDS limit
         if (!attr_done) {
             WFS_HIP_CHECK(hipFuncSetAttribute((const void *)k_tcn_bwd<T, K>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
@@ -303,7 +285,7 @@ extern "C" int wfs_tcn_bwd(const void *X, const void *dY, int64_t N, int32_t L, 
         k_tcn_bwd<T, K><<<grid, block, lds, stream>>>((const T *)X, (const T *)dY, N, L, taps, bias, levels, (T *)dX, partial,
                                                       dropout_p, seed_dev);
         WFS_LAUNCH_CHECK();
-        return (int)WFS_OK;
+        return WFS_OK;
     });
 }
 

@@ -28,10 +28,6 @@ constexpr int VB = 256;             // 4 waves per block, one 64-sample slice pe
 constexpr int VSCAN = 1024;         // the prefix block
 constexpr int VSEG = 16;            // slices per prefix thread held in registers (12.6 k slices at 256 events, T = 1024)
 
-__device__ __forceinline__ long long valid_rows(long long R, const long long *r_dev) {
-    long long v = r_dev ? *r_dev : R;
-    return v < R ? v : R;
-}
 
 template <typename T>
 __device__ __forceinline__ bool active(const T *row, int T_, int t, float thr) {
@@ -47,7 +43,7 @@ __global__ void __launch_bounds__(VB) k_vox_count(const T *__restrict__ rows, lo
     const long long r = w / S;
     if (r >= n_cap) return;
     int cnt = 0;
-    if (r < valid_rows(n_cap, n_dev))
+    if (r < wfs_valid_rows(n_cap, n_dev))
         cnt = __popcll(__ballot(active(rows + r * 2 * T_, T_, (int)(w - r * S) * WFS_WAVE + lane, thr)));
     if (lane == 0) off[w] = cnt;          // rows beyond the valid count: no voxels, whatever they hold
 }
@@ -91,7 +87,7 @@ __global__ void __launch_bounds__(VSCAN) k_vox_scan(int *__restrict__ off, long 
         total += wsum[w];
     }
     long long run = before + inc - own;
-    const long long nv = valid_rows(n_cap, n_dev);
+    const long long nv = wfs_valid_rows(n_cap, n_dev);
     const long long vc = total < V_cap ? total : V_cap;
     int bad = 0;
     // slice j = (row r, slice c of the row): r and c are stepped, not divided out per slice
@@ -261,13 +257,13 @@ extern "C" int wfs_voxelize_plan(const void *rows, const int32_t *coords, int64_
     const long long *nd = (const long long *)n_dev;
     if (n_cap > 0) {
         const dim3 grid((unsigned)wfs_cdiv(n_cap * wfs_cdiv(T_, WFS_WAVE), VB / WFS_WAVE)), block(VB);
-        if (dtype == WFS_F32)
-            k_vox_count<float><<<grid, block, 0, stream>>>((const float *)rows, n_cap, T_, nd, threshold, row_offsets);
-        else if (dtype == WFS_BF16)
-            k_vox_count<wfs_bf16><<<grid, block, 0, stream>>>((const wfs_bf16 *)rows, n_cap, T_, nd, threshold, row_offsets);
-        else
-            k_vox_count<wfs_f16><<<grid, block, 0, stream>>>((const wfs_f16 *)rows, n_cap, T_, nd, threshold, row_offsets);
-        WFS_LAUNCH_CHECK();
+        const int rc_count = wfs_with_dtype(dtype, [&](auto t) -> int {
+            using T = decltype(t);
+            k_vox_count<T><<<grid, block, 0, stream>>>((const T *)rows, n_cap, T_, nd, threshold, row_offsets);
+            WFS_LAUNCH_CHECK();
+            return WFS_OK;
+        });
+        if (rc_count != WFS_OK) return rc_count;
     }
     k_vox_scan<<<dim3(1), dim3(VSCAN), 0, stream>>>(row_offsets, n_cap, (int)wfs_cdiv(T_, WFS_WAVE), coords, nd, batch_size, V_cap,
                                                     (long long *)v_dev, overflow_dev, event_offsets);
@@ -284,21 +280,16 @@ extern "C" int wfs_voxelize_emit(const void *rows, const void *values, const int
     WFS_REQUIRE(V_cap >= 0 && V_cap < (1ll << 31), WFS_EINVAL, "voxel capacity %lld not in [0, 2^31)", (long long)V_cap);
     if (n_cap == 0 || V_cap == 0) return WFS_OK;
     WFS_REQUIRE(rows && values && coords && row_offsets && indices && feats, WFS_EINVAL, "NULL device pointer");
-    WFS_REQUIRE((uintptr_t)indices % 16 == 0 && (uintptr_t)feats % (2 * (dtype == WFS_F32 ? 4 : 2)) == 0, WFS_EINVAL,
+    WFS_REQUIRE((uintptr_t)indices % 16 == 0 && (uintptr_t)feats % (2 * wfs_dtype_bytes(dtype)) == 0, WFS_EINVAL,
                 "indices must be 16-byte and feats pair aligned");
     const dim3 grid((unsigned)wfs_cdiv(n_cap * wfs_cdiv(T_, WFS_WAVE), VB / WFS_WAVE)), block(VB);
-    if (dtype == WFS_F32)
-        k_vox_emit<float><<<grid, block, 0, stream>>>((const float *)rows, (const float *)values, coords, n_cap, T_,
-                                                      threshold, row_offsets, V_cap, (int4 *)indices, (float *)feats);
-    else if (dtype == WFS_BF16)
-        k_vox_emit<wfs_bf16><<<grid, block, 0, stream>>>((const wfs_bf16 *)rows, (const wfs_bf16 *)values, coords, n_cap,
-                                                         T_, threshold, row_offsets, V_cap, (int4 *)indices,
-                                                         (wfs_bf16 *)feats);
-    else
-        k_vox_emit<wfs_f16><<<grid, block, 0, stream>>>((const wfs_f16 *)rows, (const wfs_f16 *)values, coords, n_cap, T_,
-                                                        threshold, row_offsets, V_cap, (int4 *)indices, (wfs_f16 *)feats);
-    WFS_LAUNCH_CHECK();
-    return WFS_OK;
+    return wfs_with_dtype(dtype, [&](auto t) -> int {
+        using T = decltype(t);
+        k_vox_emit<T><<<grid, block, 0, stream>>>((const T *)rows, (const T *)values, coords, n_cap, T_, threshold,
+                                                  row_offsets, V_cap, (int4 *)indices, (T *)feats);
+        WFS_LAUNCH_CHECK();
+        return WFS_OK;
+    });
 }
 
 extern "C" int wfs_voxelize_bwd(const void *dfeat, const int32_t *indices, const int32_t *row_offsets, int64_t n_cap,
@@ -310,7 +301,7 @@ extern "C" int wfs_voxelize_bwd(const void *dfeat, const int32_t *indices, const
     if (n_cap == 0) return WFS_OK;
     WFS_REQUIRE(row_offsets && dY && (V_cap == 0 || (dfeat && indices)), WFS_EINVAL, "NULL device pointer");
     WFS_REQUIRE((uintptr_t)indices % 16 == 0, WFS_EINVAL, "indices must be 16-byte aligned");
-    if (dtype == WFS_F32) return launch_bwd<float>(dfeat, indices, row_offsets, n_cap, T_, V_cap, dY, stream);
-    if (dtype == WFS_BF16) return launch_bwd<wfs_bf16>(dfeat, indices, row_offsets, n_cap, T_, V_cap, dY, stream);
-    return launch_bwd<wfs_f16>(dfeat, indices, row_offsets, n_cap, T_, V_cap, dY, stream);
+    return wfs_with_dtype(dtype, [&](auto t) -> int {
+        return launch_bwd<decltype(t)>(dfeat, indices, row_offsets, n_cap, T_, V_cap, dY, stream);
+    });
 }

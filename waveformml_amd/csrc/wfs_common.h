@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <type_traits>
+
 #include "../../include/wfsparse.h"
 
 #define WFS_WAVE 64
@@ -92,6 +94,66 @@ __device__ __forceinline__ float wfs_round_to(float v) {
     return wfs_ld(&t);
 }
 static inline bool wfs_dtype_ok(int dtype) { return dtype == WFS_F32 || dtype == WFS_BF16 || dtype == WFS_F16; }
+static inline int wfs_dtype_bytes(int dtype) { return dtype == WFS_F32 ? 4 : 2; }
+// "no reduction was deferred": what an entry point leaves in *defer before it decides otherwise
+static inline wfs_dw_job wfs_dw_job_none() { return wfs_dw_job{}; }
+
+// What a host-side column map (kmap_host[k] = table column used for filter offset k, NULL = none) amounts to.  The fast
+// kernels know two maps: the identity, and the SubM mirror k -> K-1-k.  Identity wins where both hold (K == 1).
+enum { WFS_KMAP_IDENTITY = 0, WFS_KMAP_MIRROR = 1, WFS_KMAP_OTHER = 2 };
+static inline int wfs_kmap_kind(const int32_t *kmap_host, int K) {
+    bool is_ident = true, is_mirror = true;
+    for (int k = 0; k < K && kmap_host; ++k) {
+        is_ident = is_ident && kmap_host[k] == k;
+        is_mirror = is_mirror && kmap_host[k] == K - 1 - k;
+    }
+    return is_ident ? WFS_KMAP_IDENTITY : (is_mirror ? WFS_KMAP_MIRROR : WFS_KMAP_OTHER);
+}
+
+// Run-time value -> template argument.  f is a generic lambda that returns the int status, so WFS_REQUIRE and
+// WFS_LAUNCH_CHECK work inside it:
+//     return wfs_with_dtype(dtype, [&](auto t) -> int {
+//         using T = decltype(t);
+//         k<T><<<grid, block, 0, stream>>>((const T *)X, ...);
+//         WFS_LAUNCH_CHECK();
+//         return WFS_OK;
+//     });
+// wfs_with_dtype: f(float{}) / f(wfs_bf16{}) / f(wfs_f16{}); any code other than WFS_F32 and WFS_BF16 takes the fp16
+// branch, so the entry points check wfs_dtype_ok themselves.  wfs_with_h16: the same for 16-bit-only launchers.
+template <typename F>
+static inline int wfs_with_dtype(int dtype, F &&f) {
+    if (dtype == WFS_F32) return f(float{});
+    if (dtype == WFS_BF16) return f(wfs_bf16{});
+    return f(wfs_f16{});
+}
+template <typename F>
+static inline int wfs_with_h16(int dtype, F &&f) {
+    if (dtype == WFS_BF16) return f(wfs_bf16{});
+    return f(wfs_f16{});
+}
+// wfs_with_int<V0, V1, ...>: f(std::integral_constant<int, Vi>{}) for the Vi that equals v; any other v takes the LAST
+// listed value (the `default:` of the switch this replaces).  Only the listed values are instantiated.
+template <int V0, int... Vs, typename F>
+static inline int wfs_with_int(int v, F &&f) {
+    if constexpr (sizeof...(Vs) == 0) {
+        return f(std::integral_constant<int, V0>{});
+    } else {
+        if (v == V0) return f(std::integral_constant<int, V0>{});
+        return wfs_with_int<Vs...>(v, f);
+    }
+}
+
+// The rows a kernel works on: the capacity its buffers were sized for, cut down to the device-side count where the
+// caller passes one (static shapes under graph capture).  The _nonneg form also holds a negative count at 0.
+__device__ __forceinline__ long long wfs_valid_rows(long long cap, const long long *dev) {
+    long long v = dev ? *dev : cap;
+    return v < cap ? v : cap;
+}
+__device__ __forceinline__ long long wfs_valid_rows_nonneg(long long cap, const long long *dev) {
+    long long v = dev ? *dev : cap;
+    v = v < cap ? v : cap;
+    return v > 0 ? v : 0;
+}
 
 // event timing (opt-in; see wfs_timing_enable)
 struct WfsTimerScope {

@@ -5,11 +5,6 @@
 
 constexpr int WFS_EVOFF_THREADS = 256;
 
-__device__ __forceinline__ long long valid_rows(long long R, const long long *r_dev) {
-    long long v = r_dev ? *r_dev : R;
-    v = v < R ? v : R;
-    return v > 0 ? v : 0;
-}
 
 // one thread per row; off [E + 1].  An event without rows gets the offset of the next event that has some (a run of
 // length 0).  flags bit 1: event column not sorted / outside [0, E); the offsets of such a batch are not meaningful (but
@@ -17,7 +12,7 @@ __device__ __forceinline__ long long valid_rows(long long R, const long long *r_
 __global__ void __launch_bounds__(WFS_EVOFF_THREADS)
 k_eval_offsets(const int *__restrict__ coords, long long n_cap, const long long *__restrict__ n_dev, int E,
                int *__restrict__ off, int *__restrict__ flags) {
-    const long long nv = valid_rows(n_cap, n_dev);
+    const long long nv = wfs_valid_rows_nonneg(n_cap, n_dev);
     const long long r = (long long)blockIdx.x * WFS_EVOFF_THREADS + threadIdx.x;
     if (nv == 0) {
         if (r == 0)

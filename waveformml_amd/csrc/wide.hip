@@ -486,7 +486,6 @@ __global__ void __launch_bounds__(256) k_sum_rows(const int *__restrict__ table,
     }
 }
 
-inline int esize(int dtype) { return dtype == WFS_F32 ? 4 : 2; }
 inline int padc(int c, int es) {                   // channel count rounded up to whole 16-byte pieces
     const int q = 16 / es;
     return (c + q - 1) / q * q;
@@ -618,7 +617,7 @@ int pad_f32(const float *src, long long rows, int C, int Cp, void *dst, int dtyp
 // rows of the row type -> 16-byte aligned, zero-padded rows, gathered through the table when given
 int pad_rows(const int *table, const KMapW &km, int K, int identity_k, long long R, const long long *r_dev,
              const void *src, long long src_rows, int C, int Cp, void *dst, int dtype, hipStream_t stream) {
-    const long long n = R * K * (Cp / (16 / esize(dtype)));
+    const long long n = R * K * (Cp / (16 / wfs_dtype_bytes(dtype)));
     if (n == 0) return WFS_OK;
     if (dtype == WFS_F32)
         k_pad_rows32<<<dim3((unsigned)wfs_cdiv(n, 256)), 256, 0, stream>>>(table, km, K, identity_k, R, r_dev,
@@ -671,7 +670,7 @@ WidePlan conv_plan(int K, long long R, long long X_rows, int Cx, int Cy, int Cw_
 extern "C" size_t wfs_wide_conv_workspace_bytes(int32_t K, int64_t R, int64_t X_rows, int32_t Cx, int32_t Cy,
                                                 int32_t has_table, int32_t dtype) {
     // the filter is [Cx][Cy] for the forward product and [Cy][Cx] for dX: padded differently, take the larger
-    const int es = esize(dtype);
+    const int es = wfs_dtype_bytes(dtype);
     const WidePlan p = conv_plan(K, R, X_rows, Cx, Cy, Cx, Cy, has_table != 0, es);
     const WidePlan q = conv_plan(K, R, X_rows, Cx, Cy, Cy, Cx, has_table != 0, es);
     return (p.w_bytes > q.w_bytes ? p.w_bytes : q.w_bytes) + p.rows_bytes + p.t_bytes + 1024;
@@ -695,7 +694,7 @@ extern "C" int wfs_wide_conv_ok(int32_t K, int64_t R, int64_t X_rows, int32_t Cx
 }
 
 extern "C" size_t wfs_wide_filters_bytes(int32_t K, int32_t Cw_in, int32_t Cw_out, int32_t dtype) {
-    const int es = esize(dtype);
+    const int es = wfs_dtype_bytes(dtype);
     return wfs_align_up((size_t)K * Cw_in * padc(Cw_out, es) * es, 256);
 }
 
@@ -704,7 +703,7 @@ extern "C" int wfs_wide_filters(const float *W, int32_t K, int32_t Cw_in, int32_
     WFS_REQUIRE(wfs_dtype_ok(dtype), WFS_EINVAL, "bad dtype %d", dtype);
     WFS_REQUIRE(K >= 1 && Cw_in >= 1 && Cw_out >= 1 && W && Wp, WFS_EINVAL, "bad filter block");
     WFS_REQUIRE(((uintptr_t)Wp & 15) == 0, WFS_EINVAL, "the filter copy must be 16-byte aligned");
-    return pad_f32(W, (long long)K * Cw_in, Cw_out, padc(Cw_out, esize(dtype)), Wp, dtype, (hipStream_t)stream);
+    return pad_f32(W, (long long)K * Cw_in, Cw_out, padc(Cw_out, wfs_dtype_bytes(dtype)), Wp, dtype, (hipStream_t)stream);
 }
 
 extern "C" int wfs_wide_gather_conv(const int32_t *table, const int32_t *kmap_host, int32_t K, int32_t identity_k,
@@ -732,7 +731,7 @@ extern "C" int wfs_wide_gather_conv(const int32_t *table, const int32_t *kmap_ho
         km.v[k] = kmap_host ? kmap_host[k] : k;
         WFS_REQUIRE(km.v[k] >= 0 && km.v[k] < K, WFS_EINVAL, "kmap[%d] out of range", k);
     }
-    const int es = esize(dtype);
+    const int es = wfs_dtype_bytes(dtype);
     const WidePlan p = conv_plan(K, R, X_rows, Cx, Cy, Cw_in, Cw_out, table != nullptr, es);
     WFS_REQUIRE(workspace_bytes >= p.w_bytes + p.rows_bytes + p.t_bytes, WFS_EWORKSPACE, "workspace %zu < %zu",
                 workspace_bytes, p.w_bytes + p.rows_bytes + p.t_bytes);
@@ -806,7 +805,7 @@ static int dw_split(int K, long long R, int Cs, int Cg, int es, int *kchunk) {
 }
 
 size_t wfs_wide_dw_workspace(int K, long long R, int Cs, int Cg, int dtype) {
-    const int es = esize(dtype);
+    const int es = wfs_dtype_bytes(dtype);
     int kchunk;
     const int ks = dw_split(K, R, Cs, Cg, es, &kchunk);
     return wfs_align_up((size_t)R * padc(Cs, es) * es, 256) + wfs_align_up((size_t)R * K * padc(Cg, es) * es, 256) +
@@ -830,7 +829,7 @@ static int rows_product(const void *A, long long lda, long long sA, int M, const
     g.Ks = (int)R;
     g.k_dev = r_dev;
     g.nseg_total = nz, g.nseg = 1, g.nz = nz;
-    g.ksplit = plan_ksplit(wfs_cdiv(M, GT) * wfs_cdiv(N, GT) * nz, (int)R, esize(dtype), &g.kchunk);
+    g.ksplit = plan_ksplit(wfs_cdiv(M, GT) * wfs_cdiv(N, GT) * nz, (int)R, wfs_dtype_bytes(dtype), &g.kchunk);
     g.ldc = N;
     g.zC = (long long)M * N;
     if (g.ksplit == 1) {
@@ -856,7 +855,7 @@ int wfs_launch_wide_dw(const int *table, const int *kmap_host, int K, int identi
     KMapW km;
     for (int k = 0; k < K; ++k) km.v[k] = kmap_host ? kmap_host[k] : k;
     Carver cv{(unsigned char *)workspace, workspace_bytes};
-    const int es = esize(dtype);
+    const int es = wfs_dtype_bytes(dtype);
     const int Csp = padc(Cs, es), Cgp = padc(Cg, es);
     int kchunk;
     const int ks = dw_split(K, R, Cs, Cg, es, &kchunk);
@@ -887,7 +886,7 @@ static int lin_split(long long B, int I, int O, int es, int *kchunk) {
 }
 
 extern "C" size_t wfs_wide_linear_workspace_bytes(int64_t B, int32_t I, int32_t O, int32_t dtype) {
-    const int es = esize(dtype);
+    const int es = wfs_dtype_bytes(dtype);
     int kchunk;
     const int ks = lin_split(B, I, O, es, &kchunk);
     const size_t x = wfs_align_up((size_t)B * padc(I, es) * es, 256), w = wfs_align_up((size_t)O * padc(I, es) * es, 256);
@@ -914,7 +913,7 @@ extern "C" int wfs_wide_linear_fwd(const void *X, int64_t B, int32_t I, const fl
     WFS_REQUIRE(workspace_bytes >= wfs_wide_linear_workspace_bytes(B, I, O, dtype), WFS_EWORKSPACE, "workspace %zu < %zu",
                 workspace_bytes, wfs_wide_linear_workspace_bytes(B, I, O, dtype));
     WFS_REQUIRE(((uintptr_t)workspace & 15) == 0, WFS_EINVAL, "workspace must be 16-byte aligned");
-    const int es = esize(dtype);
+    const int es = wfs_dtype_bytes(dtype);
     const int Ip = padc(I, es), Op = padc(O, es), Of = padc(O, 4);
     Carver cv{(unsigned char *)workspace, workspace_bytes};
     void *Xp = cv.take((size_t)B * Ip * es);
@@ -958,7 +957,7 @@ extern "C" int wfs_wide_linear_bwd(const void *X, const float *dY, int64_t B, in
     WFS_REQUIRE(workspace_bytes >= wfs_wide_linear_workspace_bytes(B, I, O, dtype), WFS_EWORKSPACE, "workspace %zu < %zu",
                 workspace_bytes, wfs_wide_linear_workspace_bytes(B, I, O, dtype));
     WFS_REQUIRE(((uintptr_t)workspace & 15) == 0, WFS_EINVAL, "workspace must be 16-byte aligned");
-    const int es = esize(dtype);
+    const int es = wfs_dtype_bytes(dtype);
     const int Ip = padc(I, es), Op = padc(O, es);
     Carver cv{(unsigned char *)workspace, workspace_bytes};
     void *Xp = cv.take((size_t)B * Ip * es);
