@@ -1025,6 +1025,66 @@ int wfs_segq_error_accumulate(const void *results, int32_t results_dtype, const 
                               int64_t *slot_scratch, double *edges, int32_t *edges_set, int32_t *error_flags,
                               int64_t *error_hist, int64_t *error_2d, void *stream);
 
+/* the real-data z evaluator (csrc/zreal.hip) --------------------------------------------------------------
+ * The reference's ZEvaluatorRealWFNorm.add (src/evaluation/ZEvaluator.py:620-670, with WaveformEvaluator.analyze_wf_z and
+ * RealDataEvaluator.add) on the device.  Additions only: WFS_ABI_VERSION stays.  Raw pointers, an explicit stream, the
+ * valid row count in device memory (n_dev, NULL = all), STICKY flags, no read-back, integer atomics only.
+ *
+ * wfs_align_pulses (one launch, one wavefront per row): align_wfs(n_before = 1) of src/utils/WaveformUtils.py.
+ *   feats       [n_cap, 2 L] of dtype: the left PMT's L samples, then the right PMT's; 1 <= L <= 512
+ *   samples     float [2, P, n_cap] (side, sample, row): the params of wfs_metric_pairs_accumulate_real per side;
+ *               1 <= P <= 16.  Sample k of a side is row[k + start]; samples before the row's start or beyond its end are
+ *               0 (the reference indexes past the row for a peak in the last samples)
+ *   start       int32 [n_cap, 2] = round_half_even(peak + tx) - 1 per side, -1 where the pulse starts at sample 0.
+ *               find_peak: the plateau-centred local maxima, the first one strictly above the running best, index 0 if
+ *               none beats sample 0; calc_crossing(-0.5): down the rising edge to half height, linear interpolation, 0
+ *               where the result leaves the row.  fp64 arithmetic on the stored values.  Rows beyond the valid count:
+ *               zeros, never read.
+ * wfs_zreal_row_stats (two launches: event offsets, then one thread per row):
+ *   pred, targ  dense maps [B, P, nx, ny] given as base, dtype, batch stride, plane stride (in elements) and plane
+ *               indices: the prediction plane, and the target's z, energy and PSD planes
+ *   pid         int32 / int64 [n_cap] or NULL; mapped 1 | 4 | 6, 258 | 256 | 512 -> 0 | 1 | 2 | 3 | 4, any other value
+ *               stays as it is; without pid every row is class 0
+ *   outputs     per row: z_pred, z_true, energy (the maps' elements, widened), mae = |pred - z| in fp64 (0 where the
+ *               target is exactly 0), dev_mm = |(z - 0.5) z_scale - (pred - 0.5) z_scale|, se (seg_status == 0.5),
+ *               params float [4, n_cap] = E, PSD, the number of single-ended rows of the row's event, z;
+ *               class_category = the class on a single-ended row with pid whose class lies in [0, n_classes), else -1;
+ *               sample_category = slice * n_classes + class with the z slice of analyze_wf_z (12 slices of z in mm:
+ *               <= -600 | nine of 120 mm, open below | (480, 600) | >= 600), and 12 * n_classes for a valid row in no
+ *               (slice, class) cell.  Rows beyond the valid count and flagged rows: zeros and -1.
+ *   flags       int32 [1], STICKY: 1 event column unsorted / out of range, 2 segment outside [nx, ny], 4 a single-ended
+ *               row's class index outside [0, n_classes) (left out of the class tables)
+ * wfs_zreal_baseline (one launch, one lane per event, after wfs_zreal_row_stats' offsets): z_basic_prediction_dense
+ *   (truth_is_cal = True) on the map that is 0.5 on single-ended segments and z_true elsewhere, per row: a row at 0.5
+ *   becomes the mean of the rows of its event on the four DIAGONAL neighbour segments that are not 0.5, rows ahead first,
+ *   then rows behind down to row 1 of the batch (row 0 is never a source), an fp64 sum stored once to fp32.  In place and
+ *   in row order: an averaged row feeds later rows.  Segments are taken to be unique within an event.
+ * wfs_zreal_accumulate (one launch, one thread per row, after the same offsets): z_deviation_with_E_full_correlation.
+ *   pred_rows   float [n_cap]: z_pred, or the baseline
+ *   tables      int64 [wfs_zreal_table_ints], persistent, (count table, then sum table of round(dev * WFS_SEG_FIXED_ONE))
+ *               for seg_mult_zmae [nx, ny, n_mult + 1], z_mult_single, z_mult_dual [n_z + 2, n_mult + 1], z_E_single,
+ *               z_E_dual [n_z + 2, n_E + 2], E_mult_single, E_mult_dual [n_E + 2, n_mult + 1], in this order.  A
+ *               single-ended segment bins 588 -/+ true z by blind_left; a double-ended one is entered at both distances;
+ *               a dead one (status 1) only enters E_mult_*; "single" is status > 0.
+ *   flags       STICKY: 1, 2 as above, 8 a deviation without a fixed-point image (NaN: the row is left out) */
+int wfs_align_pulses(const void *feats, int32_t dtype, int64_t n_cap, const int64_t *n_dev, int32_t L, int32_t P,
+                     float *samples, int32_t *start, void *stream);
+int wfs_zreal_row_stats(const int32_t *coords, const void *pred, int32_t pred_dtype, int64_t pred_bs, int64_t pred_ps,
+                        int32_t pred_plane, const void *targ, int32_t targ_dtype, int64_t targ_bs, int64_t targ_ps,
+                        int32_t z_plane, int32_t e_plane, int32_t psd_plane, const void *pid, int32_t pid_int64,
+                        int64_t n_cap, const int64_t *n_dev, int32_t B, const float *seg_status, int32_t nx, int32_t ny,
+                        int32_t n_classes, double z_scale, int32_t *offsets, float *z_pred, float *z_true, float *energy,
+                        float *mae, float *dev_mm, float *params, int32_t *class_category, int32_t *sample_category,
+                        int32_t *se, int32_t *flags, void *stream);
+int wfs_zreal_baseline(const int32_t *coords, int64_t n_cap, const int64_t *n_dev, int32_t B, const int32_t *offsets,
+                       const float *z_true, const float *seg_status, int32_t nx, int32_t ny, float *baseline,
+                       void *stream);
+size_t wfs_zreal_table_ints(int32_t nx, int32_t ny, int32_t n_mult, int32_t n_z, int32_t n_E);
+int wfs_zreal_accumulate(const int32_t *coords, int64_t n_cap, const int64_t *n_dev, int32_t B, const int32_t *offsets,
+                         const float *pred_rows, const float *z_true, const float *energy, const float *seg_status,
+                         const int32_t *blind_left, int32_t nx, int32_t ny, int32_t n_mult, int32_t n_z, double zrange,
+                         double E_low, double E_high, int32_t n_E, int64_t *tables, int32_t *flags, void *stream);
+
 /* ---- prediction writers (csrc/predwrite.hip; reference src/datasets/PredictionWriter.py swap_values) ----------------
  * A chunk of a table travels as RAW compound records uint8 [N, item_size] (include/wfh5w.h); the two entry points turn
  * them into the net's input and put the net's output back into them, on the device.

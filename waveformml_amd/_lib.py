@@ -201,6 +201,13 @@ SIGNATURES = {
                                           _i32, _i32, _i32, _i32] + [_vp] * 11),
     "wfs_segq_error_accumulate": (ctypes.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _i64, _vp, _i32, _i32, _i32]
                                   + [_vp] * 7),
+    "wfs_align_pulses": (ctypes.c_int, [_vp, _i32, _i64, _vp, _i32, _i32, _vp, _vp, _vp]),
+    "wfs_zreal_row_stats": (ctypes.c_int, [_vp, _vp, _i32, _i64, _i64, _i32, _vp, _i32, _i64, _i64, _i32, _i32, _i32, _vp,
+                                           _i32, _i64, _vp, _i32, _vp, _i32, _i32, _i32, _dbl] + [_vp] * 12),
+    "wfs_zreal_baseline": (ctypes.c_int, [_vp, _i64, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp]),
+    "wfs_zreal_table_ints": (_sz, [_i32, _i32, _i32, _i32, _i32]),
+    "wfs_zreal_accumulate": (ctypes.c_int, [_vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32,
+                                            _dbl, _dbl, _dbl, _i32, _vp, _vp, _vp]),
     "wfs_predict_workspace_ints": (_sz, [_i64]),
     "wfs_predict_prepare": (ctypes.c_int, [_vp, _i64, _i64, _i64, _i64, _i32, _i32, _vp, _i32, _i32, _i64, _vp, _vp, _i32,
                                            _vp, _vp, _sz, _vp]),

@@ -1,0 +1,44 @@
+// wfs_segtables.h -- what the per-segment evaluation kernels share (segstats.hip, zreal.hip): a plane of a dense
+// [B, P, nx, ny] map, and the (count, fixed-point sum) cells of their int64 tables.  Included into each file's anonymous
+// namespace.
+#pragma once
+#include "wfs_common.h"
+
+constexpr double FIX_ONE = 4294967296.0;     // 2^32, WFS_SEG_FIXED_ONE
+
+struct Plane {                               // one [B, nx, ny] plane of a [B, P, nx, ny] tensor
+    const void *base;
+    long long batch_stride, offset;          // in elements; offset = plane * plane stride
+    int dtype;
+};
+
+__device__ __forceinline__ float ld_plane(const Plane &m, long long e, int cell) {
+    const long long i = e * m.batch_stride + m.offset + cell;
+    if (m.dtype == WFS_F32) return wfs_ld((const float *)m.base + i);
+    if (m.dtype == WFS_BF16) return wfs_ld((const wfs_bf16 *)m.base + i);
+    return wfs_ld((const wfs_f16 *)m.base + i);
+}
+
+__device__ __forceinline__ void add_count(long long *p) {
+    atomicAdd(reinterpret_cast<unsigned long long *>(p), 1ull);
+}
+// the fixed-point image of dev, or false (flag 8)
+__device__ __forceinline__ bool fixed_image(double dev, long long *out, int *flags) {
+    const double s = __dmul_rn(dev, FIX_ONE);
+    if (!(fabs(s) < 4611686018427387904.0)) {                 // 2^62; also catches NaN
+        atomicOr(flags, 8);
+        return false;
+    }
+    *out = __double2ll_rn(s);
+    return true;
+}
+__device__ __forceinline__ void add_fixed(long long *p, long long v, int *flags) {
+    const long long old = (long long)atomicAdd(reinterpret_cast<unsigned long long *>(p), (unsigned long long)v);
+    const long long now = (long long)((unsigned long long)old + (unsigned long long)v);
+    if (((old ^ now) & (v ^ now)) < 0) atomicOr(flags, 8);   // the cell's sum wrapped
+}
+// increment_metric_mult_SE's single / dual pair: tab = [count | sum] of one table of `cells` cells
+__device__ __forceinline__ void add_cell(long long *tab, int cells, int cell, long long v, int *flags) {
+    add_count(tab + cell);
+    add_fixed(tab + cells + cell, v, flags);
+}

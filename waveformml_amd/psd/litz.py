@@ -6,7 +6,7 @@ the number of rows (``net_config.SELoss``: of the single-ended segments only, ps
 
 As psd/lit.LitPSD these are plain ``nn.Module``s with Lightning's step methods (Lightning is not installable offline).
 The evaluators the reference's ``test_step`` feeds (ZEvaluatorWF, EZEvaluatorWF without a calibration group) are
-psd/segment_evaluator.py; ``test_step`` leaves what it would hand them in ``last_test_outputs`` and
+psd/segment_evaluator.py, and for ``LitZ`` with phys test targets (``test_has_phys``) psd/real_z_evaluator.py; ``test_step`` leaves what it would hand them in ``last_test_outputs`` and
 psd/evaluate.segment_test_loop does the hand-over.  Their plots and the calibration-database variants are out of scope.
 """
 import logging
@@ -15,8 +15,26 @@ import torch
 from torch import nn
 
 from .config import DictionaryUtility, ModuleUtility
+from .pid_evaluator import Z_INDEX
 from .segments import SE_DEAD_PMTS, segment_status, single_ended_mask
 from .znet import SingleEndedEZConv, SingleEndedZConv
+
+
+def test_has_phys(config):
+    """The reference's ``LitZ.test_has_phys`` (LitZ.py:34-37): the test dataset's label is the whole ``"phys"`` row,
+    without a ``label_index`` that picks one column of it."""
+    params = getattr(config.dataset_config, "test_dataset_params", None)
+    return params is not None and getattr(params, "label_name", None) == "phys" and not hasattr(params, "label_index")
+
+
+def real_evaluator_params(config, params):
+    """``evaluation_config`` as keyword arguments with ``test_dataset_params.additional_fields`` merged under it as
+    ``additional_field_names`` (LitZ.py:43-48)."""
+    params = dict(params)
+    test_params = getattr(config.dataset_config, "test_dataset_params", None)
+    if test_params is not None and hasattr(test_params, "additional_fields"):
+        params["additional_field_names"] = list(test_params.additional_fields)
+    return params
 
 
 class LitSegmentBase(nn.Module):
@@ -116,6 +134,11 @@ class LitSegmentBase(nn.Module):
 class LitZ(LitSegmentBase):
     model_class = SingleEndedZConv
 
+    def __init__(self, config, trial=None):
+        super().__init__(config, trial)
+        # reference LitZ.__init__, :34-37: real detector data carries the seven phys planes as test targets
+        self.test_has_phys = test_has_phys(config)
+
     # reference LitZ._process_batch, :89-108
     def _process_batch(self, batch, target_index=None):
         (c, f), target = batch
@@ -139,12 +162,20 @@ class LitZ(LitSegmentBase):
         return loss
 
     def _make_evaluator(self, device, params):
+        if self.test_has_phys:
+            from .real_z_evaluator import ZEvaluatorRealWFNorm
+            return ZEvaluatorRealWFNorm(device, **real_evaluator_params(self.config, params))
         from .segment_evaluator import ZEvaluator
         return ZEvaluator(device, **params)
 
     def test_step(self, batch, batch_idx):
-        loss, predictions, target_tensor, c, f, _ = self._process_batch(batch)
-        self.last_test_outputs = (predictions.detach(), target_tensor.detach(), c, f)
+        if self.test_has_phys:
+            # reference LitZ.test_step, :134-139: column z_index of the phys target is scored
+            loss, predictions, target_tensor, c, f, additional_fields = self._process_batch(batch, target_index=Z_INDEX)
+            self.last_test_outputs = (predictions.detach(), target_tensor.detach(), c, f, additional_fields)
+        else:
+            loss, predictions, target_tensor, c, f, _ = self._process_batch(batch)
+            self.last_test_outputs = (predictions.detach(), target_tensor.detach(), c, f)
         results = {"test_loss": loss}
         self.log_dict(results, on_epoch=True, logger=True)
         return results

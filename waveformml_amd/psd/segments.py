@@ -24,6 +24,16 @@ def segment_status(dead_pmts=SE_DEAD_PMTS, nx=NX, ny=NY):
     return status
 
 
+def blind_left(dead_pmts=SE_DEAD_PMTS, nx=NX, ny=NY):
+    """``SingleEndedEvaluator.blind_detl``: 1 where the segment's end-0 PMT is dead, int32 [nx, ny]."""
+    blind = np.zeros((nx, ny), dtype=np.int32)
+    for pmt in dead_pmts:
+        if pmt % 2 == 0:
+            seg = pmt // 2
+            blind[seg % nx, seg // nx] = 1
+    return blind
+
+
 def single_ended_mask(status):
     """[1, 1, nx, ny] float mask: 1 where exactly one end is live."""
     st = torch.as_tensor(status)
