@@ -25,7 +25,9 @@
 namespace {
 
 #include "wfs_evoffsets.h"
+#include "wfs_segrows.h"
 #include "wfs_evalbins.h"
+#include "wfs_segtables.h"
 
 constexpr int MB = WFS_EVOFF_THREADS;
 constexpr int MP_MAX = 16;                    // WFS_METRIC_PAIRS_MAX
@@ -148,27 +150,16 @@ k_pid_rows(const int *__restrict__ coords, const long long *__restrict__ pred, c
     int o_acc = 0, o_mult = 0, o_se = 0, o_nse = 0, o_cat = -1;
     float o_par[4] = {0.f, 0.f, 0.f, 0.f};
     if (r < nv) {
-        const int x = coords[r * 3], y = coords[r * 3 + 1], e = coords[r * 3 + 2];
+        const SegRow h = seg_row(coords, r, nv, off, E, pp.nx, pp.ny, flags);
         const long long p = pred[r], t = targ[r];
-        if (e < 0 || e >= E) {
-            atomicOr(flags, 1);               // k_eval_offsets has set it already
-        } else if (x < 0 || x >= pp.nx || y < 0 || y >= pp.ny) {
-            atomicOr(flags, 2);               // a segment outside the detector
-        } else if (p < 0 || p >= PID_CLASSES || t < 0 || t >= PID_CLASSES) {
+        const bool classes_ok = p >= 0 && p < PID_CLASSES && t >= 0 && t < PID_CLASSES;
+        if (h.ok && !classes_ok) {
             atomicOr(flags, 4);               // a class outside PID_MAPPED_NAMES
-        } else {
-            long long b = off[e], en = off[e + 1];
-            b = b < 0 ? 0 : (b > nv ? nv : b);
-            en = en < 0 ? 0 : (en > nv ? nv : en);
-            if (en < b) en = b;               // only with a flagged (unsorted) event column
-            o_mult = (int)(en - b);
-            for (long long q = b; q < en; ++q) {
-                const int qx = coords[q * 3], qy = coords[q * 3 + 1];
-                // a row outside the grid raises flag 2 itself
-                if (qx >= 0 && qx < pp.nx && qy >= 0 && qy < pp.ny && seg[qx * pp.ny + qy] == 0.5f) ++o_nse;
-            }
+        } else if (h.ok) {
+            o_mult = (int)(h.last - h.first);
+            o_nse = count_single_ended(coords, h.first, h.last, seg, pp.nx, pp.ny);
             o_acc = p == t ? 1 : 0;
-            o_se = seg[x * pp.ny + y] == 0.5f ? 1 : 0;
+            o_se = seg[h.cell] == 0.5f ? 1 : 0;
             const T *row = phys + r * pp.n_phys;
             o_par[0] = wfs_ld(row + pp.e_index);
             o_par[1] = wfs_ld(row + pp.psd_index);
@@ -281,8 +272,7 @@ extern "C" int wfs_pid_row_stats(const int32_t *coords, const int64_t *predictio
                                  int32_t *n_se, float *params, int32_t *category, int64_t *tables, int32_t *flags,
                                  void *stream) {
     WFS_REQUIRE(wfs_dtype_ok(dtype), WFS_EINVAL, "wfs_pid_row_stats: unknown dtype %d", dtype);
-    WFS_REQUIRE(E >= 1 && n_cap >= 0 && n_cap < (1ll << 31) && nx >= 1 && ny >= 1, WFS_EINVAL,
-                "wfs_pid_row_stats: E = %d, n_cap = %lld, grid %d x %d", E, (long long)n_cap, nx, ny);
+    WFS_REQUIRE_EVAL_BATCH("wfs_pid_row_stats: E", E, n_cap, nx, ny);
     WFS_REQUIRE(n_phys >= 1 && e_index >= 0 && e_index < n_phys && psd_index >= 0 && psd_index < n_phys && z_index >= 0 &&
                     z_index < n_phys,
                 WFS_EINVAL, "wfs_pid_row_stats: column indices %d, %d, %d outside [0, %d)", e_index, psd_index, z_index,
@@ -295,8 +285,7 @@ extern "C" int wfs_pid_row_stats(const int32_t *coords, const int64_t *predictio
     hipStream_t s = (hipStream_t)stream;
     if (n_cap == 0) return WFS_OK;
     const unsigned rb = (unsigned)wfs_cdiv(n_cap, MB);
-    k_eval_offsets<<<rb, MB, 0, s>>>(coords, n_cap, (const long long *)n_dev, E, offsets, flags);
-    WFS_LAUNCH_CHECK();
+    if (const int rc = launch_eval_offsets(coords, n_cap, (const long long *)n_dev, E, offsets, flags, s)) return rc;
     const PidPlan pp = {nx, ny, n_phys, e_index, psd_index, z_index, n_confusion, n_se_max, e_high};
     return wfs_with_dtype(dtype, [&](auto t) -> int {
         using TYPE = decltype(t);
@@ -333,23 +322,7 @@ constexpr int MPR_LDS_CELLS = 1024;           // cells of the 1-D image (5 x 8 K
 #endif
 constexpr int MPR_SLICE = MPR_SLICE_ROWS * MB;
 constexpr int TENSOR_DET_ROW = 14;            // det == 2 * (14 * j + i) + k
-constexpr double FIX_ONE = 4294967296.0;      // 2^32
-
-// the fixed-point image of a result; false (flag 8) for a result that has none: not finite, or |r| >= 2^15
-__device__ __forceinline__ bool real_image(float r, long long *v, int *flags) {
-    if (!(fabsf(r) < 32768.f)) {              // also catches NaN
-        atomicOr(flags, 8);
-        return false;
-    }
-    *v = __double2ll_rn(__dmul_rn((double)r, FIX_ONE));
-    return true;
-}
-// a cell's S: flag 16 when the sum leaves int64
-__device__ __forceinline__ void add_fixed(long long *p, long long v, int *flags) {
-    const long long old = (long long)atomicAdd(reinterpret_cast<unsigned long long *>(p), (unsigned long long)v);
-    const long long now = (long long)((unsigned long long)old + (unsigned long long)v);
-    if (((old ^ now) & (v ^ now)) < 0) atomicOr(flags, 16);
-}
+constexpr int MPR_WRAP = 16;                  // flag: a cell's S left int64 (add_fixed, wfs_segtables.h)
 
 template <bool LDS1D>
 __global__ void __launch_bounds__(MB)
@@ -411,7 +384,7 @@ k_metric_pairs_real(const float *__restrict__ params, const float *__restrict__ 
                     long long *t = tab + pl.off1[i] + (long long)cat * ni + bi;
                     add64(t, 1);
                     if (v != 0) {
-                        add_fixed(t + sz, v, flags);
+                        add_fixed(t + sz, v, flags, MPR_WRAP);
 #pragma unroll
                         for (int k = 0; k < 3; ++k)
                             if (q[k] != 0) add64(t + (2 + k) * sz, q[k]);
@@ -423,7 +396,7 @@ k_metric_pairs_real(const float *__restrict__ params, const float *__restrict__ 
                     const long long cells = (long long)C * ni * nj;
                     long long *t = t2 + ((long long)cat * ni + bi) * nj + MPR_BIN(j);
                     add64(t, 1);
-                    if (v != 0) add_fixed(t + cells, v, flags);
+                    if (v != 0) add_fixed(t + cells, v, flags, MPR_WRAP);
                     t2 += 2 * cells;
                 }
             }
@@ -441,7 +414,7 @@ k_metric_pairs_real(const float *__restrict__ params, const float *__restrict__ 
                 const long long sz = (long long)C * (pl.nb[i] + 2);
                 long long *t = tab + pl.off1[i] + which * sz + (cell - pl.img[i]);
                 if (which == 1)
-                    add_fixed(t, v, flags);
+                    add_fixed(t, v, flags, MPR_WRAP);
                 else
                     add64(t, v);
             }
@@ -492,7 +465,7 @@ k_tensor_rows(const CT *__restrict__ c, int c_cols, const T *__restrict__ target
     if (!real_image(results[r], &v, flags)) return;
     const long long cells = (long long)nx * ny * 2, cell = (x * ny + y) * 2 + side;
     add64(det + cell, 1);
-    if (v != 0) add_fixed(det + cells + cell, v, flags);
+    if (v != 0) add_fixed(det + cells + cell, v, flags, MPR_WRAP);
 }
 
 }  // namespace

@@ -35,10 +35,12 @@
 //                    through bin_direct (wfs_evalbins.h) as int64 counts.
 #include "wfs_common.h"
 #include "wfs_erroredges.h"
+#include "wfs_rows.h"                         // ldt / stt: rows of a runtime dtype
 
 namespace {
 
 #include "wfs_evoffsets.h"
+#include "wfs_segrows.h"
 #include "wfs_evalbins.h"
 
 constexpr int MB = WFS_EVOFF_THREADS;
@@ -48,20 +50,6 @@ constexpr int MRL_CHUNK = MRL_THREADS * MRL_ROWS;
 constexpr int MRL_MAX_BLOCKS = 256;
 constexpr int MRL_HEAD = 16;                  // workspace: the ticket (and padding), then 3 x 8 bytes per chunk
 constexpr int SEGQ_SLOTS = 6, SEGQ_CLASSES = 5;
-
-__device__ __forceinline__ double ld_real(const void *p, int dtype, long long i) {
-    if (dtype == WFS_F32) return (double)static_cast<const float *>(p)[i];
-    if (dtype == WFS_BF16) return (double)wfs_ld(static_cast<const wfs_bf16 *>(p) + i);
-    return (double)wfs_ld(static_cast<const wfs_f16 *>(p) + i);
-}
-__device__ __forceinline__ void st_real(void *p, int dtype, long long i, float v) {
-    if (dtype == WFS_F32)
-        static_cast<float *>(p)[i] = v;
-    else if (dtype == WFS_BF16)
-        wfs_st(static_cast<wfs_bf16 *>(p) + i, v);
-    else
-        wfs_st(static_cast<wfs_f16 *>(p) + i, v);
-}
 
 struct MrlIn {
     const void *pred, *target;
@@ -106,8 +94,8 @@ k_mrl_forward(MrlIn in, long long n_chunks, unsigned *__restrict__ ticket, doubl
         for (int j = 0; j < MRL_ROWS; ++j) {
             const long long r = ch * MRL_CHUNK + (long long)j * MRL_THREADS + t;
             if (r < nv && mrl_counted(in, r)) {
-                const double d = ld_real(in.pred, in.pred_dtype, r) -
-                                 ld_real(in.target, in.target_dtype, r * in.n_cols + in.col);
+                const double d = (double)ldt(in.pred, r, in.pred_dtype) -
+                                 (double)ldt(in.target, r * in.n_cols + in.col, in.target_dtype);
                 const double q = d * d;
                 a += in.kind == WFS_LOSS_L1 ? fabs(d) : q;
                 b += q;
@@ -159,11 +147,12 @@ k_mrl_backward(MrlIn in, const long long *__restrict__ count, const float *__res
     const long long nv = wfs_valid_rows_nonneg(in.n_cap, in.n_dev), cnt = *count;
     float v = 0.f;
     if (cnt > 0 && r < nv && mrl_counted(in, r)) {
-        const double d = ld_real(in.pred, in.pred_dtype, r) - ld_real(in.target, in.target_dtype, r * in.n_cols + in.col);
+        const double d = (double)ldt(in.pred, r, in.pred_dtype) -
+                         (double)ldt(in.target, r * in.n_cols + in.col, in.target_dtype);
         const double s = in.kind == WFS_LOSS_L1 ? (d > 0.0 ? 1.0 : (d < 0.0 ? -1.0 : (d == d ? 0.0 : d))) : 2.0 * d;
         v = (float)((double)*grad * s / (double)cnt);
     }
-    st_real(dpred, in.pred_dtype, r, v);
+    stt(dpred, r, in.pred_dtype, v);
 }
 
 bool mrl_args(const void *pred, int32_t pred_dtype, const void *target, int32_t target_dtype, int32_t n_cols, int32_t col,
@@ -182,12 +171,6 @@ bool mrl_args(const void *pred, int32_t pred_dtype, const void *target, int32_t 
 struct SegqPlan {
     int nx, ny, n_phys, e_index, psd_index, z_index, t_index, has_pid, pid_int64;
 };
-
-// class_PIDs in order: the slot of a PID and the slot's class
-__device__ __forceinline__ int segq_slot(long long pid) {
-    return pid == 1 ? 0 : pid == 4 ? 1 : pid == 6 ? 2 : pid == 258 ? 3 : pid == 256 ? 4 : pid == 512 ? 5 : -1;
-}
-__device__ __forceinline__ int segq_class(int slot) { return slot < 3 ? slot : slot - 1; }
 
 __global__ void __launch_bounds__(MB)
 k_segq_rows(const int *__restrict__ coords, const void *__restrict__ results, int r_dtype, const void *__restrict__ target,
@@ -208,30 +191,20 @@ k_segq_rows(const int *__restrict__ coords, const void *__restrict__ results, in
         float o_par[4] = {0.f, 0.f, 0.f, 0.f}, o_mae = 0.f;
         double o_err = 0.0;
         if (r < nv) {
-            const int x = coords[r * 3], y = coords[r * 3 + 1], e = coords[r * 3 + 2];
-            if (e < 0 || e >= E) {
-                atomicOr(flags, 1);           // k_eval_offsets has set it already
-            } else if (x < 0 || x >= pp.nx || y < 0 || y >= pp.ny) {
-                atomicOr(flags, 2);           // a segment outside the detector
-            } else {
-                long long b = off[e], en = off[e + 1];
-                b = b < 0 ? 0 : (b > nv ? nv : b);
-                en = en < 0 ? 0 : (en > nv ? nv : en);
-                if (en < b) en = b;           // only with a flagged (unsorted) event column
-                o_mult = (int)(en - b);
-                o_se = seg[x * pp.ny + y] == 0.5f ? 1 : 0;
+            const SegRow h = seg_row(coords, r, nv, off, E, pp.nx, pp.ny, flags);
+            if (h.ok) {
+                o_mult = (int)(h.last - h.first);
+                o_se = seg[h.cell] == 0.5f ? 1 : 0;
                 const long long row = r * pp.n_phys;
-                o_err = ld_real(results, r_dtype, r) - ld_real(target, t_dtype, row + pp.t_index);
+                o_err = (double)ldt(results, r, r_dtype) - (double)ldt(target, row + pp.t_index, t_dtype);
                 o_mae = (float)fabs(o_err);
-                o_par[0] = (float)ld_real(target, t_dtype, row + pp.e_index);
-                o_par[1] = (float)ld_real(target, t_dtype, row + pp.psd_index);
+                o_par[0] = ldt(target, row + pp.e_index, t_dtype);
+                o_par[1] = ldt(target, row + pp.psd_index, t_dtype);
                 o_par[2] = (float)o_mult;
-                o_par[3] = (float)ld_real(target, t_dtype, row + pp.z_index);
+                o_par[3] = ldt(target, row + pp.z_index, t_dtype);
                 if (pp.has_pid) {
-                    const long long id = pp.pid_int64 ? static_cast<const long long *>(pid)[r]
-                                                      : (long long)static_cast<const int *>(pid)[r];
-                    const int s = segq_slot(id);
-                    if (s >= 0 && o_se) o_slot = s, o_cat = segq_class(s);
+                    const int s = pid_slot(ld_pid(pid, pp.pid_int64, r));
+                    if (s >= 0 && o_se) o_slot = s, o_cat = pid_slot_class(s);
                 } else {
                     o_slot = 0, o_cat = 0;    // the single class "all": every valid row, no single-ended mask
                 }
@@ -265,7 +238,7 @@ k_segq_edges(int C, int has_pid, int nb, unsigned long long *__restrict__ slot_m
     const int c = threadIdx.x;
     if (c < C && !edges_set[c]) {
         for (int s = 0; s < SEGQ_SLOTS; ++s) {
-            if ((has_pid ? segq_class(s) : 0) != c || slot_rows[s] <= 0) continue;   // without PID: slot 0, class 0 only
+            if ((has_pid ? pid_slot_class(s) : 0) != c || slot_rows[s] <= 0) continue;   // without PID: slot 0, class 0 only
             double first, last;
             if (error_edge_range(__longlong_as_double((long long)slot_max[s]), nb, &first, &last)) {
                 edges[2 * c] = first, edges[2 * c + 1] = last;
@@ -292,8 +265,8 @@ k_segq_bins(const void *__restrict__ results, int r_dtype, const void *__restric
     if (c < 0 || c >= C || !edges_set[c]) return;
     const int n2 = nb + 2;
     add64(hist + (long long)c * n2 + bin_direct(error[r], edges[2 * c], edges[2 * c + 1], nb), 1);
-    const int bx = bin_direct(ld_real(target, t_dtype, r * n_phys + t_index), 0.0, 1.0, nb);
-    const int by = bin_direct(ld_real(results, r_dtype, r), 0.0, 1.0, nb);
+    const int bx = bin_direct((double)ldt(target, r * n_phys + t_index, t_dtype), 0.0, 1.0, nb);
+    const int by = bin_direct((double)ldt(results, r, r_dtype), 0.0, 1.0, nb);
     add64(hist2d + ((long long)c * n2 + bx) * n2 + by, 1);
 }
 
@@ -363,8 +336,7 @@ extern "C" int wfs_segq_row_stats(const int32_t *coords, const void *results, in
                                   void *stream) {
     WFS_REQUIRE(wfs_dtype_ok(results_dtype) && wfs_dtype_ok(target_dtype), WFS_EINVAL,
                 "wfs_segq_row_stats: unknown dtype %d / %d", results_dtype, target_dtype);
-    WFS_REQUIRE(E >= 1 && n_cap >= 0 && n_cap < (1ll << 31) && nx >= 1 && ny >= 1, WFS_EINVAL,
-                "wfs_segq_row_stats: E = %d, n_cap = %lld, grid %d x %d", E, (long long)n_cap, nx, ny);
+    WFS_REQUIRE_EVAL_BATCH("wfs_segq_row_stats: E", E, n_cap, nx, ny);
     WFS_REQUIRE(n_phys >= 1 && e_index >= 0 && e_index < n_phys && psd_index >= 0 && psd_index < n_phys && z_index >= 0 &&
                     z_index < n_phys && target_index >= 0 && target_index < n_phys,
                 WFS_EINVAL, "wfs_segq_row_stats: column indices %d, %d, %d, %d outside [0, %d)", e_index, psd_index,
@@ -376,8 +348,7 @@ extern "C" int wfs_segq_row_stats(const int32_t *coords, const void *results, in
     if (n_cap == 0) return WFS_OK;
     hipStream_t s = (hipStream_t)stream;
     const unsigned rb = (unsigned)wfs_cdiv(n_cap, MB);
-    k_eval_offsets<<<rb, MB, 0, s>>>(coords, n_cap, (const long long *)n_dev, E, offsets, flags);
-    WFS_LAUNCH_CHECK();
+    if (const int rc = launch_eval_offsets(coords, n_cap, (const long long *)n_dev, E, offsets, flags, s)) return rc;
     const SegqPlan pp = {nx, ny, n_phys, e_index, psd_index, z_index, target_index, pid ? 1 : 0, pid_int64};
     k_segq_rows<<<rb, MB, 0, s>>>(coords, results, results_dtype, target, target_dtype, pid, n_cap,
                                   (const long long *)n_dev, E, seg_status, pp, offsets, mae, error, multiplicity, se, params,

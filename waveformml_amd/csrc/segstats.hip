@@ -19,18 +19,11 @@
 namespace {
 
 #include "wfs_evoffsets.h"
+#include "wfs_segrows.h"
+#include "wfs_evalbins.h"
 #include "wfs_segtables.h"
 
 constexpr int SB = WFS_EVOFF_THREADS;
-// get_bin_index(val, low, high, width, nb): underflow in bin 0, >= high in bin nb + 1, else the first j with
-// j * width + low > val
-__device__ __forceinline__ int bin_walk(double v, double low, double high, double w, int nb) {
-    if (v < low) return 0;
-    if (v >= high) return nb + 1;
-    for (int j = 1; j <= nb; ++j)
-        if (__dadd_rn(__dmul_rn((double)j, w), low) > v) return j;
-    return 0;
-}
 // z_deviation's own walk: the first k with k * (zrange / nz) - zrange / 2 > true_z
 __device__ __forceinline__ int bin_z(double z, double zrange, int nz) {
     const double half = zrange / 2., w = zrange / nz;
@@ -40,30 +33,10 @@ __device__ __forceinline__ int bin_z(double z, double zrange, int nz) {
         if (__dsub_rn(__dmul_rn((double)k, w), half) > z) return k;
     return 0;
 }
-
-struct RowHead {
-    int x, y, e, col;
-    bool ok;
-};
-// coordinates, bounds and the multiplicity column of row r
-__device__ __forceinline__ RowHead row_head(const int *coords, long long r, const int *off, int B, int nx, int ny,
-                                            int nmult, int *flags) {
-    RowHead h;
-    h.x = coords[r * 3], h.y = coords[r * 3 + 1], h.e = coords[r * 3 + 2];
-    h.ok = false;
-    h.col = nmult;
-    if (h.e < 0 || h.e >= B) {
-        atomicOr(flags, 1);                  // k_eval_offsets has set it already
-        return h;
-    }
-    if (h.x < 0 || h.x >= nx || h.y < 0 || h.y >= ny) {
-        atomicOr(flags, 2);                  // a segment outside the detector
-        return h;
-    }
-    const int mult = off[h.e + 1] - off[h.e];
-    if (0 < mult && mult <= nmult) h.col = mult - 1;
-    h.ok = true;
-    return h;
+// the multiplicity column of a row: the length of its event's run, beyond nmult (and a run of 0) in the last column
+__device__ __forceinline__ int mult_col(const SegRow &h, int nmult) {
+    const int mult = (int)(h.last - h.first);
+    return 0 < mult && mult <= nmult ? mult - 1 : nmult;
 }
 
 struct ZBins {
@@ -78,9 +51,9 @@ k_seg_z(const int *__restrict__ coords, long long n_cap, const long long *__rest
     const long long nv = wfs_valid_rows_nonneg(n_cap, n_dev);
     const long long r = (long long)blockIdx.x * SB + threadIdx.x;
     if (r >= nv) return;
-    const RowHead h = row_head(coords, r, off, B, Z.nx, Z.ny, Z.nmult, flags);
+    const SegRow h = seg_row(coords, r, nv, off, B, Z.nx, Z.ny, flags);
     if (!h.ok) return;
-    const int cell = h.x * Z.ny + h.y, nm1 = Z.nmult + 1;
+    const int cell = h.cell, col = mult_col(h, Z.nmult), nm1 = Z.nmult + 1;
     const double p = (double)ld_plane(pred, h.e, cell), t = (double)ld_plane(targ, h.e, cell);
     // table order: wfs_seg_z_table_ints
     const int seg_cells = Z.nx * Z.ny * nm1, bin_cells = (Z.nz + 2) * nm1;
@@ -90,13 +63,13 @@ k_seg_z(const int *__restrict__ coords, long long n_cap, const long long *__rest
     long long v;
     if (fixed_image(fabs(__dsub_rn(p, t)), &v, flags)) {
         const int zb = bin_z(__dmul_rn(__dsub_rn(t, 0.5), Z.zrange), Z.zrange, Z.nz);
-        add_cell(t_seg, seg_cells, cell * nm1 + h.col, v, flags);
-        add_cell(single ? t_zs : t_zd, bin_cells, zb * nm1 + h.col, v, flags);
+        add_cell(t_seg, seg_cells, cell * nm1 + col, v, flags);
+        add_cell(single ? t_zs : t_zd, bin_cells, zb * nm1 + col, v, flags);
         if (ene.base) {
             // the reference scales the energy map on the host, float32 * E_scale in float32, before the walk sees it
             const double E = (double)__fmul_rn(ld_plane(ene, h.e, cell), (float)Z.E_scale);
-            const int eb = bin_walk(E, Z.E_low, Z.E_high, (Z.E_high - Z.E_low) / Z.nz, Z.nz);
-            add_cell(single ? t_es : t_ed, bin_cells, eb * nm1 + h.col, v, flags);
+            const int eb = bin_metric(E, Z.E_low, Z.E_high, Z.nz);
+            add_cell(single ? t_es : t_ed, bin_cells, eb * nm1 + col, v, flags);
         }
     }
     // z_error: only rows on a sample segment (the first that matches, as sample_index)
@@ -104,8 +77,8 @@ k_seg_z(const int *__restrict__ coords, long long n_cap, const long long *__rest
         if (sample_segs[2 * s] == h.x && sample_segs[2 * s + 1] == h.y) {
             const double err = __dmul_rn(__dsub_rn(p, t), Z.zrange);
             // NaN compares false everywhere: the reference's walk leaves it in bin 0, and so does this one
-            const int b = bin_walk(err, Z.err_low, Z.err_high, (Z.err_high - Z.err_low) / Z.n_err, Z.n_err);
-            add_count(t_hist + ((long long)s * nm1 + h.col) * (Z.n_err + 2) + b);
+            const int b = bin_metric(err, Z.err_low, Z.err_high, Z.n_err);
+            add64(t_hist + ((long long)s * nm1 + col) * (Z.n_err + 2) + b, 1);
             break;
         }
 }
@@ -122,9 +95,9 @@ k_seg_energy(const int *__restrict__ coords, long long n_cap, const long long *_
     const long long nv = wfs_valid_rows_nonneg(n_cap, n_dev);
     const long long r = (long long)blockIdx.x * SB + threadIdx.x;
     if (r >= nv) return;
-    const RowHead h = row_head(coords, r, off, B, Eb.nx, Eb.ny, Eb.nmult, flags);
+    const SegRow h = seg_row(coords, r, nv, off, B, Eb.nx, Eb.ny, flags);
     if (!h.ok) return;
-    const int cell = h.x * Eb.ny + h.y, nm1 = Eb.nmult + 1;
+    const int cell = h.cell, col = mult_col(h, Eb.nmult), nm1 = Eb.nmult + 1;
     const double p = (double)ld_plane(pred, h.e, cell), t = (double)ld_plane(targ, h.e, cell);
     if (t == 0.0) {
         atomicOr(flags, 4);                  // the reference divides by it (numba raises, plain Python gives inf)
@@ -132,16 +105,12 @@ k_seg_energy(const int *__restrict__ coords, long long n_cap, const long long *_
     }
     long long v;
     if (!fixed_image(fabs(__dsub_rn(p, t)) / t, &v, flags)) return;
-    const int eb = bin_walk(__dmul_rn(t, Eb.E_scale), Eb.E_low, Eb.E_high, (Eb.E_high - Eb.E_low) / Eb.nE, Eb.nE);
+    const int eb = bin_metric(__dmul_rn(t, Eb.E_scale), Eb.E_low, Eb.E_high, Eb.nE);
     // table order: wfs_seg_energy_table_ints
     const int seg_cells = Eb.nx * Eb.ny * nm1, bin_cells = (Eb.nE + 2) * nm1;
     long long *t_seg = tab, *t_es = t_seg + 2 * seg_cells, *t_ed = t_es + 2 * bin_cells;
-    add_cell(t_seg, seg_cells, cell * nm1 + h.col, v, flags);
-    add_cell(seg[cell] > 0.f ? t_es : t_ed, bin_cells, eb * nm1 + h.col, v, flags);
-}
-
-bool plane_ok(const void *base, int dtype, long long bs, long long ps, int plane) {
-    return base && wfs_dtype_ok(dtype) && bs >= 0 && ps >= 0 && plane >= 0;
+    add_cell(t_seg, seg_cells, cell * nm1 + col, v, flags);
+    add_cell(seg[cell] > 0.f ? t_es : t_ed, bin_cells, eb * nm1 + col, v, flags);
 }
 
 }  // namespace
@@ -166,8 +135,7 @@ extern "C" int wfs_seg_z_accumulate(const int32_t *coords, int64_t n_cap, const 
                                     double zrange, int32_t n_err, double err_low, double err_high, double E_low,
                                     double E_high, double E_scale, int32_t *offsets, int64_t *tables, int32_t *flags,
                                     void *stream) {
-    WFS_REQUIRE(B >= 1 && n_cap >= 0 && n_cap < (1ll << 31) && nx >= 1 && ny >= 1, WFS_EINVAL,
-                "wfs_seg_z_accumulate: B = %d, n_cap = %lld, grid %d x %d", B, (long long)n_cap, nx, ny);
+    WFS_REQUIRE_EVAL_BATCH("wfs_seg_z_accumulate: B", B, n_cap, nx, ny);
     WFS_REQUIRE(nmult >= 1 && nz >= 1 && n_err >= 1 && n_sample >= 0 && err_high > err_low && zrange > 0, WFS_EINVAL,
                 "wfs_seg_z_accumulate: bad bin parameters");
     WFS_REQUIRE(coords && seg_status && (sample_segs || n_sample == 0) && offsets && tables && flags, WFS_EINVAL,
@@ -177,10 +145,9 @@ extern "C" int wfs_seg_z_accumulate(const int32_t *coords, int64_t n_cap, const 
                     (!energy || (plane_ok(energy, e_dtype, e_bs, e_ps, e_plane) && E_high > E_low)),
                 WFS_EINVAL, "wfs_seg_z_accumulate: bad map (NULL, unknown dtype or negative stride / plane)");
     hipStream_t s = (hipStream_t)stream;
-    const unsigned rb = (unsigned)(n_cap > 0 ? wfs_cdiv(n_cap, SB) : 1);
-    k_eval_offsets<<<rb, SB, 0, s>>>(coords, n_cap, (const long long *)n_dev, B, offsets, flags);
-    WFS_LAUNCH_CHECK();
+    if (const int rc = launch_eval_offsets(coords, n_cap, (const long long *)n_dev, B, offsets, flags, s)) return rc;
     if (n_cap == 0) return WFS_OK;
+    const unsigned rb = (unsigned)wfs_cdiv(n_cap, SB);
     const Plane P = {pred, pred_bs, pred_ps * pred_plane, pred_dtype};
     const Plane T = {targ, targ_bs, targ_ps * targ_plane, targ_dtype};
     const Plane En = {energy, e_bs, energy ? e_ps * e_plane : 0, energy ? e_dtype : WFS_F32};
@@ -198,8 +165,7 @@ extern "C" int wfs_seg_energy_accumulate(const int32_t *coords, int64_t n_cap, c
                                          int32_t ny, int32_t nmult, int32_t nE, double E_low, double E_high,
                                          double E_scale, int32_t *offsets, int64_t *tables, int32_t *flags,
                                          void *stream) {
-    WFS_REQUIRE(B >= 1 && n_cap >= 0 && n_cap < (1ll << 31) && nx >= 1 && ny >= 1, WFS_EINVAL,
-                "wfs_seg_energy_accumulate: B = %d, n_cap = %lld, grid %d x %d", B, (long long)n_cap, nx, ny);
+    WFS_REQUIRE_EVAL_BATCH("wfs_seg_energy_accumulate: B", B, n_cap, nx, ny);
     WFS_REQUIRE(nmult >= 1 && nE >= 1 && E_high > E_low, WFS_EINVAL, "wfs_seg_energy_accumulate: bad bin parameters");
     WFS_REQUIRE(coords && seg_status && offsets && tables && flags, WFS_EINVAL,
                 "wfs_seg_energy_accumulate: NULL argument");
@@ -207,10 +173,9 @@ extern "C" int wfs_seg_energy_accumulate(const int32_t *coords, int64_t n_cap, c
                     plane_ok(targ, targ_dtype, targ_bs, targ_ps, targ_plane),
                 WFS_EINVAL, "wfs_seg_energy_accumulate: bad map (NULL, unknown dtype or negative stride / plane)");
     hipStream_t s = (hipStream_t)stream;
-    const unsigned rb = (unsigned)(n_cap > 0 ? wfs_cdiv(n_cap, SB) : 1);
-    k_eval_offsets<<<rb, SB, 0, s>>>(coords, n_cap, (const long long *)n_dev, B, offsets, flags);
-    WFS_LAUNCH_CHECK();
+    if (const int rc = launch_eval_offsets(coords, n_cap, (const long long *)n_dev, B, offsets, flags, s)) return rc;
     if (n_cap == 0) return WFS_OK;
+    const unsigned rb = (unsigned)wfs_cdiv(n_cap, SB);
     const Plane P = {pred, pred_bs, pred_ps * pred_plane, pred_dtype};
     const Plane T = {targ, targ_bs, targ_ps * targ_plane, targ_dtype};
     const EBins Eb = {nx, ny, nmult, nE, E_low, E_high, E_scale};

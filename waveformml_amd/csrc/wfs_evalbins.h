@@ -1,5 +1,5 @@
-// wfs_evalbins.h -- the bin walks and the int64 add of the evaluation tables (evalstats.hip, metricpairs.hip, zreal.hip).
-// Included into each file's anonymous namespace.  Edges follow the reference literally: the first j with
+// wfs_evalbins.h -- the bin walks and the int64 add of the evaluation tables (evalstats.hip, segstats.hip, metricpairs.hip,
+// segquant.hip, zreal.hip).  Included into each file's anonymous namespace.  Edges follow the reference literally: the first j with
 // j * width + low > value, a rounded product and a rounded sum (no fma).
 #pragma once
 #include "wfs_common.h"

@@ -30,6 +30,7 @@
 namespace {
 
 #include "wfs_evoffsets.h"
+#include "wfs_segrows.h"
 #include "wfs_evalbins.h"
 #include "wfs_segtables.h"
 
@@ -132,11 +133,6 @@ struct ZrPlan {
     double z_scale;
 };
 
-// convert_PID(PID, PID_MAP): a PID the map does not name stays as it is
-__device__ __forceinline__ long long zr_pid_class(long long pid) {
-    return pid == 1 ? 0 : pid == 4 ? 1 : pid == 6 ? 2 : pid == 256 ? 3 : pid == 258 ? 2 : pid == 512 ? 4 : pid;
-}
-
 // analyze_wf_z's slices of z in mm (inc = 1200 / NUM_Z_BINS = 120): 0: z <= -600; i = 1 .. 9: -600 + (i - 1) inc < z <=
 // -600 + i inc; 10: 480 < z < 600; 11: z >= 600; a NaN is in none (-1)
 __device__ __forceinline__ int zr_slice(double z) {
@@ -146,14 +142,6 @@ __device__ __forceinline__ int zr_slice(double z) {
     for (int i = 1; i <= 9; ++i)
         if (z > -600. + (i - 1) * 120. && z <= -600. + i * 120.) return i;
     return -1;
-}
-
-// clamped row range of event e
-__device__ __forceinline__ void zr_event_rows(const int *off, int e, long long nv, long long *b, long long *en) {
-    long long lo = off[e], hi = off[e + 1];
-    lo = lo < 0 ? 0 : (lo > nv ? nv : lo);
-    hi = hi < 0 ? 0 : (hi > nv ? nv : hi);
-    *b = lo, *en = hi < lo ? lo : hi;         // hi < lo only with a flagged (unsorted) event column
 }
 
 __global__ void __launch_bounds__(ZB)
@@ -169,20 +157,10 @@ k_zreal_rows(const int *__restrict__ coords, Plane pred, Plane tz, Plane te, Pla
     float o_zp = 0.f, o_zt = 0.f, o_en = 0.f, o_mae = 0.f, o_dmm = 0.f, o_par[4] = {0.f, 0.f, 0.f, 0.f};
     int o_cls = -1, o_smp = -1, o_se = 0;
     if (r < nv) {
-        const int x = coords[r * 3], y = coords[r * 3 + 1], e = coords[r * 3 + 2];
-        if (e < 0 || e >= B) {
-            atomicOr(flags, 1);               // k_eval_offsets has set it already
-        } else if (x < 0 || x >= pp.nx || y < 0 || y >= pp.ny) {
-            atomicOr(flags, 2);               // a segment outside the detector
-        } else {
-            const int cell = x * pp.ny + y;
-            long long b, last;
-            zr_event_rows(off, e, nv, &b, &last);
-            int n_se = 0;                     // the multiplicity coo[SE_inds] shows: the event's single-ended rows
-            for (long long q = b; q < last; ++q) {
-                const int qx = coords[q * 3], qy = coords[q * 3 + 1];
-                if (qx >= 0 && qx < pp.nx && qy >= 0 && qy < pp.ny && seg[qx * pp.ny + qy] == 0.5f) ++n_se;
-            }
+        const SegRow h = seg_row(coords, r, nv, off, B, pp.nx, pp.ny, flags);
+        if (h.ok) {
+            const int e = h.e, cell = h.cell;
+            const int n_se = count_single_ended(coords, h.first, h.last, seg, pp.nx, pp.ny);
             o_se = seg[cell] == 0.5f ? 1 : 0;
             o_zp = ld_plane(pred, e, cell), o_zt = ld_plane(tz, e, cell), o_en = ld_plane(te, e, cell);
             const double p = (double)o_zp, t = (double)o_zt;
@@ -191,9 +169,7 @@ k_zreal_rows(const int *__restrict__ coords, Plane pred, Plane tz, Plane te, Pla
             o_dmm = (float)fabs(__dsub_rn(z, zq));
             o_par[0] = o_en, o_par[1] = ld_plane(tp, e, cell), o_par[2] = (float)n_se, o_par[3] = o_zt;
             long long cls = 0;
-            if (pp.has_pid)
-                cls = zr_pid_class(pp.pid_int64 ? static_cast<const long long *>(pid)[r]
-                                                : (long long)static_cast<const int *>(pid)[r]);
+            if (pp.has_pid) cls = pid_class(ld_pid(pid, pp.pid_int64, r));
             const bool in_classes = cls >= 0 && cls < pp.n_classes;
             if (pp.has_pid && o_se) {
                 if (in_classes)
@@ -219,7 +195,7 @@ k_zreal_baseline(const int *__restrict__ coords, long long n_cap, const long lon
     const int e = blockIdx.x * ZB + threadIdx.x;
     if (e >= B) return;
     long long b, last;
-    zr_event_rows(off, e, nv, &b, &last);
+    event_run(off, e, nv, &b, &last);
     // the map ZEvaluatorRealWFNorm.add builds, and the look-ahead count of rows that can serve as a source
     int n = 0;
     for (long long r = b; r < last; ++r) {
@@ -260,20 +236,11 @@ k_zreal_acc(const int *__restrict__ coords, long long n_cap, const long long *__
     const long long nv = wfs_valid_rows_nonneg(n_cap, n_dev);
     const long long r = (long long)blockIdx.x * ZB + threadIdx.x;
     if (r >= nv) return;
-    const int x = coords[r * 3], y = coords[r * 3 + 1], e = coords[r * 3 + 2];
-    if (e < 0 || e >= B) {
-        atomicOr(flags, 1);
-        return;
-    }
-    if (x < 0 || x >= Z.nx || y < 0 || y >= Z.ny) {
-        atomicOr(flags, 2);
-        return;
-    }
-    long long b, last;
-    zr_event_rows(off, e, nv, &b, &last);
-    const int mult = (int)(last - b);
+    const SegRow h = seg_row(coords, r, nv, off, B, Z.nx, Z.ny, flags);
+    if (!h.ok) return;
+    const int mult = (int)(h.last - h.first);
     if (mult < 1) return;                     // only with a flagged (unsorted) event column
-    const int cell = x * Z.ny + y, nm1 = Z.nmult + 1, nzb = Z.nz + 2, neb = Z.nE + 2;
+    const int cell = h.cell, nm1 = Z.nmult + 1, nzb = Z.nz + 2, neb = Z.nE + 2;
     const double p = (double)pred[r], t = (double)zt[r];
     long long v;
     if (!fixed_image(fabs(__dsub_rn(p, t)), &v, flags)) return;          // a NaN row is left out of every table
@@ -299,10 +266,6 @@ k_zreal_acc(const int *__restrict__ coords, long long n_cap, const long long *__
         }
     }
     add_cell(single ? t_ems : t_emd, c_em, eb * nm1 + col, v, flags);
-}
-
-bool zr_plane_ok(const void *base, int dtype, long long bs, long long ps, int plane) {
-    return base && wfs_dtype_ok(dtype) && bs >= 0 && ps >= 0 && plane >= 0;
 }
 
 }  // namespace
@@ -335,8 +298,8 @@ extern "C" int wfs_zreal_row_stats(const int32_t *coords, const void *pred, int3
     WFS_REQUIRE(B >= 1 && n_cap >= 0 && n_cap < (1ll << 31) && nx >= 1 && ny >= 1 && n_classes >= 1, WFS_EINVAL,
                 "wfs_zreal_row_stats: B = %d, n_cap = %lld, grid %d x %d, %d classes", B, (long long)n_cap, nx, ny,
                 n_classes);
-    WFS_REQUIRE(zr_plane_ok(pred, pred_dtype, pred_bs, pred_ps, pred_plane) &&
-                    zr_plane_ok(targ, targ_dtype, targ_bs, targ_ps, z_plane) && e_plane >= 0 && psd_plane >= 0,
+    WFS_REQUIRE(plane_ok(pred, pred_dtype, pred_bs, pred_ps, pred_plane) &&
+                    plane_ok(targ, targ_dtype, targ_bs, targ_ps, z_plane) && e_plane >= 0 && psd_plane >= 0,
                 WFS_EINVAL, "wfs_zreal_row_stats: bad map (NULL, unknown dtype or negative stride / plane)");
     WFS_REQUIRE(seg_status && offsets && flags && (pid_int64 == 0 || pid_int64 == 1) &&
                     (n_cap == 0 || (coords && z_pred && z_true && energy && mae && dev_mm && params && class_category &&
@@ -345,8 +308,7 @@ extern "C" int wfs_zreal_row_stats(const int32_t *coords, const void *pred, int3
     if (n_cap == 0) return WFS_OK;
     hipStream_t s = (hipStream_t)stream;
     const unsigned rb = (unsigned)wfs_cdiv(n_cap, ZB);
-    k_eval_offsets<<<rb, ZB, 0, s>>>(coords, n_cap, (const long long *)n_dev, B, offsets, flags);
-    WFS_LAUNCH_CHECK();
+    if (const int rc = launch_eval_offsets(coords, n_cap, (const long long *)n_dev, B, offsets, flags, s)) return rc;
     const Plane P = {pred, pred_bs, pred_ps * pred_plane, pred_dtype};
     const Plane Tz = {targ, targ_bs, targ_ps * z_plane, targ_dtype}, Te = {targ, targ_bs, targ_ps * e_plane, targ_dtype},
                 Tp = {targ, targ_bs, targ_ps * psd_plane, targ_dtype};
@@ -361,8 +323,7 @@ extern "C" int wfs_zreal_row_stats(const int32_t *coords, const void *pred, int3
 extern "C" int wfs_zreal_baseline(const int32_t *coords, int64_t n_cap, const int64_t *n_dev, int32_t B,
                                   const int32_t *offsets, const float *z_true, const float *seg_status, int32_t nx,
                                   int32_t ny, float *baseline, void *stream) {
-    WFS_REQUIRE(B >= 1 && n_cap >= 0 && n_cap < (1ll << 31) && nx >= 1 && ny >= 1, WFS_EINVAL,
-                "wfs_zreal_baseline: B = %d, n_cap = %lld, grid %d x %d", B, (long long)n_cap, nx, ny);
+    WFS_REQUIRE_EVAL_BATCH("wfs_zreal_baseline: B", B, n_cap, nx, ny);
     WFS_REQUIRE(offsets && seg_status && (n_cap == 0 || (coords && z_true && baseline)), WFS_EINVAL,
                 "wfs_zreal_baseline: NULL argument");
     if (n_cap == 0) return WFS_OK;
@@ -382,8 +343,7 @@ extern "C" int wfs_zreal_accumulate(const int32_t *coords, int64_t n_cap, const 
                                     const float *energy, const float *seg_status, const int32_t *blind_left, int32_t nx,
                                     int32_t ny, int32_t n_mult, int32_t n_z, double zrange, double E_low, double E_high,
                                     int32_t n_E, int64_t *tables, int32_t *flags, void *stream) {
-    WFS_REQUIRE(B >= 1 && n_cap >= 0 && n_cap < (1ll << 31) && nx >= 1 && ny >= 1, WFS_EINVAL,
-                "wfs_zreal_accumulate: B = %d, n_cap = %lld, grid %d x %d", B, (long long)n_cap, nx, ny);
+    WFS_REQUIRE_EVAL_BATCH("wfs_zreal_accumulate: B", B, n_cap, nx, ny);
     WFS_REQUIRE(n_mult >= 1 && n_z >= 1 && n_E >= 1 && zrange > 0 && E_high > E_low, WFS_EINVAL,
                 "wfs_zreal_accumulate: bad bin parameters");
     WFS_REQUIRE(offsets && seg_status && blind_left && tables && flags &&

@@ -23,7 +23,8 @@ import numpy as np
 import torch
 
 from .. import _lib
-from .metric_pairs import MetricPairTables, split_results, triple_1d
+from .eval_common import check_coords, raise_flags, read_back, require_device_tensors, require_gpu
+from .metric_pairs import MetricPairTables, triple_1d
 
 FLAG_TEXT = {1: "the event column of a batch was not sorted or held an event outside the batch",
              2: "a segment coordinate lay outside the detector grid",
@@ -47,9 +48,7 @@ class PSDEvaluator:
     def __init__(self, class_names, device, gains=None, seg_status=None, n_samples=150, n_bins=100, n_mult=10,
                  n_confusion=10, n_SE_max=4, emin=0.0, emax=5.0, psd_min=0.0, psd_max=0.6, nx=14, ny=11,
                  fix_last_event_n_SE=False, metric_pairs=False):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("waveformml_amd: PSDEvaluator runs on the GPU (there is no CPU path); got %s" % self.device)
+        self.device = require_gpu(device, "PSDEvaluator")
         self.class_names = list(class_names)
         self.n_classes = len(self.class_names)
         self.n_samples, self.n_bins, self.n_mult = int(n_samples), int(n_bins), int(n_mult)
@@ -116,20 +115,17 @@ class PSDEvaluator:
         inputs, labels = batch
         coords, feats = inputs[0], inputs[1]
         n_valid = inputs[2] if len(inputs) > 2 else None
-        for t in (coords, feats, labels, predictions):
-            if not t.is_cuda:
-                raise RuntimeError("waveformml_amd: tensor must live on the GPU (there is no CPU path); got %s" % t.device)
+        require_device_tensors(coords, feats, labels, predictions)
         W = 2 * self.n_samples
         rows = int(coords.shape[0])
-        if coords.dtype != torch.int32 or coords.dim() != 2 or coords.shape[1] != 3:
-            raise RuntimeError("PSDEvaluator.add: coords must be int32 [N, 3] = (x, y, event)")
+        check_coords(coords, None, "PSDEvaluator.add")
         if feats.shape[0] != rows or feats.numel() != rows * W:
             raise RuntimeError("PSDEvaluator.add: waveforms must be [N, %d] (n_samples = %d), got %s"
                                % (W, self.n_samples, tuple(feats.shape)))
         E = int(labels.shape[0])
         if predictions.shape[0] != E or labels.dtype != torch.int64 or predictions.dtype != torch.int64:
             raise RuntimeError("PSDEvaluator.add: labels and predictions must be int64 [E]")
-        if n_valid is not None and n_valid.dtype != torch.int64:
+        if n_valid is not None and n_valid.dtype != torch.int64:      # its device is not tested here, unlike check_n_valid
             raise RuntimeError("PSDEvaluator.add: n_valid must be a device int64")
         self._reserve(rows, E)
         lib, p, st = _lib.load(), _lib.ptr, _lib.stream_ptr()
@@ -167,20 +163,15 @@ class PSDEvaluator:
         f = int(self.flags.item())
         if self.metric_pairs is not None:
             f |= int(self.metric_pairs.flags.item()) & 4
-        if f:
-            raise RuntimeError("PSDEvaluator: " + "; ".join(t for b, t in FLAG_TEXT.items() if f & b))
+        raise_flags("PSDEvaluator", f, FLAG_TEXT)
 
     def results(self):
         """One read-back.  The reference's ``results`` dict after ``finalize()`` -- (mean, n, M2) triples where
         ``metric_accumulate_1d`` fills them, (sum of matches, n, zeros) where ``metric_accumulate_2d`` does, the
         never-filled ``ene_acc`` / ``*_prec_*`` entries as zeros of the reference's shapes -- plus the pulse sums."""
         self._check_flags()
-        host = self.tables.cpu().numpy()
-        t, at = {}, 0
-        for name, shape in self._layout:
-            size = int(np.prod(shape))
-            t[name] = host[at:at + size].reshape(shape).copy()
-            at += size
+        cur = read_back(self.tables)
+        t = {name: cur.take(shape).copy() for name, shape in self._layout}
         nb, nm = self.n_bins + 2, self.n_mult + 2
 
         def empty_1d(k):
@@ -204,6 +195,5 @@ class PSDEvaluator:
         res["summed_labelled_waveforms"] = self.sum_labelled.cpu().numpy().astype(np.float32)
         res["n_labelled_wfs"] = t["n_labelled_wfs"]
         if self.metric_pairs is not None:
-            mp = self.metric_pairs
-            res["metric_pairs"] = split_results(mp.tables.cpu().numpy(), mp._layout, mp.names)
+            res["metric_pairs"] = self.metric_pairs.split(read_back(self.metric_pairs.tables).rest())
         return res

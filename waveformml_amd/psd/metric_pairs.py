@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from .eval_common import FIX_BITS, FIXED_ONE, TableCursor, check_n_valid, raise_flags, read_back, require_gpu
 
 MAX_METRICS = 16                # WFS_METRIC_PAIRS_MAX, include/wfsparse.h
 FLAG_TEXT = {4: "a category lay outside class_names",
@@ -62,49 +63,59 @@ def table_layout(n_bins, n_classes):
 
 
 class MetricPairTables:
+    # what RealMetricPairTables changes: the entry points, the layout, the result's check and the texts
+    _table_ints, _accumulate = "wfs_metric_pairs_table_ints", "wfs_metric_pairs_accumulate"
+    _layout_of = staticmethod(table_layout)
+    _result_text = "result (0 / 1) and category must be int32 [%(M)d]; real-valued results are not supported"
+    _flag_text = FLAG_TEXT
+
     def __init__(self, device, metrics, class_names):
         """``metrics``: a list of ``(name, low, high, n_bins)``, ``MetricAggregator``'s leading arguments."""
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("waveformml_amd: MetricPairTables runs on the GPU (there is no CPU path); got %s" % self.device)
+        self._name = name = type(self).__name__
+        self.device = require_gpu(device, name)
         self.class_names = list(class_names)
         self.n_classes = len(self.class_names)
         self.names = [str(m[0]) for m in metrics]
         self.n_bins = [int(m[3]) for m in metrics]
         self.P = len(self.names)
         if not 1 <= self.P <= MAX_METRICS or self.n_classes < 1 or min(self.n_bins) < 1:
-            raise ValueError("MetricPairTables: 1 to %d metrics with at least one bin each and at least one class" % MAX_METRICS)
+            raise ValueError("%s: 1 to %d metrics with at least one bin each and at least one class" % (name, MAX_METRICS))
         self.ranges = [bin_edge_range(float(m[1]), float(m[2]), int(m[3])) for m in metrics]
         self._nb = _lib.i32_array(self.n_bins)
-        self._layout = table_layout(self.n_bins, self.n_classes)
-        n = int(_lib.load().wfs_metric_pairs_table_ints(self.P, self._nb, self.n_classes))
-        assert n == sum(2 * int(np.prod(s)) for _k, s in self._layout)
+        self._layout = self._layout_of(self.n_bins, self.n_classes)
+        lib = _lib.load()
+        self._accumulate_fn = getattr(lib, self._accumulate)
+        n = int(getattr(lib, self._table_ints)(self.P, self._nb, self.n_classes))
+        assert n == sum((e[2] if len(e) > 2 else 2) * int(np.prod(e[1])) for e in self._layout)
         self.tables = torch.zeros(n, dtype=torch.int64, device=self.device)
         self.flags = torch.zeros(1, dtype=torch.int32, device=self.device)
 
     def add(self, params, result, category, n_valid=None, ranges=None):
-        """``params`` float32 [P, M]; ``result`` int32 [M] of 0 / 1; ``category`` int32 [M], the class index of every
-        element or -1 to leave it out; ``n_valid`` a device int64 count of the valid elements.  ``ranges``: one
-        ``(low, high)`` per metric; the default bins by the metrics' own edges (the reference's ``add``), a caller
-        passes ``add_normalized``'s ranges.  Launches on the current stream; no read-back."""
-        M = int(result.shape[0])
+        """``params`` float32 [P, M]; ``result`` [M], int32 of 0 / 1 (``RealMetricPairTables``: float32); ``category``
+        int32 [M], the class index of every element or -1 to leave it out; ``n_valid`` a device int64 count of the valid
+        elements.  ``ranges``: one ``(low, high)`` per metric; the default bins by the metrics' own edges (the
+        reference's ``add``), a caller passes ``add_normalized``'s ranges.  One launch on the current stream; no
+        read-back."""
+        name, M = self._name, int(result.shape[0])
         if params.dtype != torch.float32 or tuple(params.shape) != (self.P, M):
-            raise RuntimeError("MetricPairTables.add: params must be float32 [%d, %d], got %s %s"
-                               % (self.P, M, params.dtype, tuple(params.shape)))
-        if result.dtype != torch.int32 or category.dtype != torch.int32 or category.shape[0] != M:
-            raise RuntimeError("MetricPairTables.add: result (0 / 1) and category must be int32 [%d]; real-valued "
-                               "results are not supported" % M)
-        if n_valid is not None and (n_valid.dtype != torch.int64 or not n_valid.is_cuda):
-            raise RuntimeError("MetricPairTables.add: n_valid must be a device int64")
+            raise RuntimeError("%s.add: params must be float32 [%d, %d], got %s %s"
+                               % (name, self.P, M, params.dtype, tuple(params.shape)))
+        if not self._result_ok(result, category, M):
+            raise RuntimeError("%s.add: %s" % (name, self._result_text % {"M": M}))
+        check_n_valid(n_valid, name + ".add")
         ranges = self.ranges if ranges is None else ranges
         if len(ranges) != self.P:
-            raise ValueError("MetricPairTables.add: one (low, high) per metric")
+            raise ValueError("%s.add: one (low, high) per metric" % name)
         lo = (ctypes.c_double * self.P)(*[float(r[0]) for r in ranges])
         hi = (ctypes.c_double * self.P)(*[float(r[1]) for r in ranges])
         p = _lib.ptr
-        _lib.check(_lib.load().wfs_metric_pairs_accumulate(
+        _lib.check(self._accumulate_fn(
             p(params), p(result), p(category), M, p(n_valid), self.P, lo, hi, self._nb, self.n_classes, p(self.tables),
             p(self.flags), _lib.stream_ptr()))
+
+    @staticmethod
+    def _result_ok(result, category, M):
+        return result.dtype == torch.int32 and category.dtype == torch.int32 and category.shape[0] == M
 
     def reset(self):
         self.tables.zero_()
@@ -115,34 +126,32 @@ class MetricPairTables:
         return [self.tables]
 
     def _check_flags(self):
-        f = int(self.flags.item())
-        if f:
-            raise RuntimeError("MetricPairTables: " + "; ".join(t for b, t in FLAG_TEXT.items() if f & b))
+        raise_flags(self._name, int(self.flags.item()), self._flag_text)
+
+    def split(self, host):
+        """``results()`` from the host copy of ``tables``."""
+        return split_results(host, self._layout, self.names)
 
     def results(self):
-        """One read-back: ``{"metrics": {name: (mean, n, dev)}, "pairs": {"i_j": (sum of matches, n)}}`` with the
-        reference's shapes [C, nb + 2] and [C, nb_i + 2, nb_j + 2]."""
+        """One read-back: ``{"metrics": {name: (mean, n, dev)}, "pairs": {"i_j": (sum of matches, n)}}`` (real-valued:
+        the sum of results) with the reference's shapes [C, nb + 2] and [C, nb_i + 2, nb_j + 2]."""
         self._check_flags()
-        return split_results(self.tables.cpu().numpy(), self._layout, self.names)
+        return self.split(read_back(self.tables).rest())
 
 
 def split_results(host, layout, names):
-    out, at = {"metrics": {}, "pairs": {}}, 0
+    out, cur = {"metrics": {}, "pairs": {}}, TableCursor(host)
     for key, shape in layout:
-        size = int(np.prod(shape))
-        n = host[at:at + size].reshape(shape).copy()
-        m = host[at + size:at + 2 * size].reshape(shape)
-        at += 2 * size
+        n, m = cur.take_pair(shape)
         if isinstance(key, int):
             out["metrics"][names[key]] = triple_1d(m, n)
         else:
-            out["pairs"][key] = (m.astype(np.float64), n)
+            out["pairs"][key] = (m.astype(np.float64), n.copy())
     return out
 
 
 # ---- real-valued results ---------------------------------------------------------------------------------------------
 REAL_TABS = 5                   # per 1-D cell: n, S, Q0, Q1, Q2 (include/wfsparse.h)
-FIX_BITS = 32                   # the fixed-point image of a result: v = round(result * 2^32)
 REAL_LIMIT = float(1 << 15)     # |result| < 2^15
 REAL_FLAG_TEXT = {4: "a category lay outside class_names",
                   8: "a result had no fixed-point image (not finite, or |result| >= 2^15)",
@@ -169,17 +178,28 @@ def real_table_layout(n_bins, n_classes):
     return [(key, shape, REAL_TABS if isinstance(key, int) else 2) for key, shape in table_layout(n_bins, n_classes)]
 
 
-def split_real_results(host, layout, names):
-    out, at = {"metrics": {}, "pairs": {}}, 0
-    for key, shape, tabs in layout:
-        size = int(np.prod(shape))
-        t = [host[at + k * size:at + (k + 1) * size].reshape(shape) for k in range(tabs)]
-        at += tabs * size
+def raw_real_tables(host, layout):
+    """{key: [int64 tables]} of a ``RealMetricPairTables`` buffer: n, S, Q0, Q1, Q2 per metric, n, S per pair."""
+    cur = TableCursor(host)
+    return {key: [cur.take(shape) for _k in range(tabs)] for key, shape, tabs in layout}
+
+
+def finish_real_tables(raw, names, last_metric_factor=1):
+    """``{"metrics": {name: (mean, n, dev)}, "pairs": {"i_j": (sum, n)}}`` from integer tables; ``last_metric_factor``
+    multiplies n, S and Q of the last metric's 1-D table (every row entered that many times)."""
+    out = {"metrics": {}, "pairs": {}}
+    last = len(names) - 1
+    for key, t in raw.items():
         if isinstance(key, int):
-            out["metrics"][names[key]] = real_triple_1d(*t)
+            f = last_metric_factor if key == last else 1
+            out["metrics"][names[key]] = real_triple_1d(*[a * f for a in t])
         else:
-            out["pairs"][key] = (t[1].astype(np.float64) / float(1 << FIX_BITS), t[0].copy())
+            out["pairs"][key] = (t[1].astype(np.float64) / FIXED_ONE, t[0].copy())
     return out
+
+
+def split_real_results(host, layout, names):
+    return finish_real_tables(raw_real_tables(host, layout), names)
 
 
 class RealMetricPairTables(MetricPairTables):
@@ -187,58 +207,16 @@ class RealMetricPairTables(MetricPairTables):
     reference's ``TensorEvaluator`` feeds it.  Per 1-D cell the count, S = sum v and Q = sum v^2 of the fixed-point images
     v = round(result * 2^32), per pair cell the count and S -- all int64, changed by integer atomics only, so the tables
     are independent of the order of the elements, bit-identical from run to run, and N ranks combine them with one
-    integer SUM.  The ranges, ``reset()`` and ``state_tensors()`` are the base class's."""
+    integer SUM.  Everything but the attributes below is the base class's."""
+    _table_ints, _accumulate = "wfs_metric_pairs_real_table_ints", "wfs_metric_pairs_accumulate_real"
+    _layout_of = staticmethod(real_table_layout)
+    _result_text = "result must be float32 [%(M)d] and category int32 [%(M)d]"
+    _flag_text = REAL_FLAG_TEXT
 
-    def __init__(self, device, metrics, class_names):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("waveformml_amd: RealMetricPairTables runs on the GPU (there is no CPU path); got %s"
-                               % self.device)
-        self.class_names = list(class_names)
-        self.n_classes = len(self.class_names)
-        self.names = [str(m[0]) for m in metrics]
-        self.n_bins = [int(m[3]) for m in metrics]
-        self.P = len(self.names)
-        if not 1 <= self.P <= MAX_METRICS or self.n_classes < 1 or min(self.n_bins) < 1:
-            raise ValueError("RealMetricPairTables: 1 to %d metrics with at least one bin each and at least one class"
-                             % MAX_METRICS)
-        self.ranges = [bin_edge_range(float(m[1]), float(m[2]), int(m[3])) for m in metrics]
-        self._nb = _lib.i32_array(self.n_bins)
-        self._layout = real_table_layout(self.n_bins, self.n_classes)
-        n = int(_lib.load().wfs_metric_pairs_real_table_ints(self.P, self._nb, self.n_classes))
-        assert n == sum(tabs * int(np.prod(s)) for _k, s, tabs in self._layout)
-        self.tables = torch.zeros(n, dtype=torch.int64, device=self.device)
-        self.flags = torch.zeros(1, dtype=torch.int32, device=self.device)
+    @staticmethod
+    def _result_ok(result, category, M):
+        return result.dtype == torch.float32 and result.dim() == 1 and category.dtype == torch.int32 and \
+            tuple(category.shape) == (M,)
 
-    def add(self, params, result, category, n_valid=None, ranges=None):
-        """``params`` float32 [P, M]; ``result`` float32 [M]; ``category``, ``n_valid`` and ``ranges`` as in
-        ``MetricPairTables.add``.  One launch on the current stream; no read-back."""
-        M = int(result.shape[0])
-        if params.dtype != torch.float32 or tuple(params.shape) != (self.P, M):
-            raise RuntimeError("RealMetricPairTables.add: params must be float32 [%d, %d], got %s %s"
-                               % (self.P, M, params.dtype, tuple(params.shape)))
-        if result.dtype != torch.float32 or result.dim() != 1 or category.dtype != torch.int32 or \
-                tuple(category.shape) != (M,):
-            raise RuntimeError("RealMetricPairTables.add: result must be float32 [%d] and category int32 [%d]" % (M, M))
-        if n_valid is not None and (n_valid.dtype != torch.int64 or not n_valid.is_cuda):
-            raise RuntimeError("RealMetricPairTables.add: n_valid must be a device int64")
-        ranges = self.ranges if ranges is None else ranges
-        if len(ranges) != self.P:
-            raise ValueError("RealMetricPairTables.add: one (low, high) per metric")
-        lo = (ctypes.c_double * self.P)(*[float(r[0]) for r in ranges])
-        hi = (ctypes.c_double * self.P)(*[float(r[1]) for r in ranges])
-        p = _lib.ptr
-        _lib.check(_lib.load().wfs_metric_pairs_accumulate_real(
-            p(params), p(result), p(category), M, p(n_valid), self.P, lo, hi, self._nb, self.n_classes, p(self.tables),
-            p(self.flags), _lib.stream_ptr()))
-
-    def _check_flags(self):
-        f = int(self.flags.item())
-        if f:
-            raise RuntimeError("RealMetricPairTables: " + "; ".join(t for b, t in REAL_FLAG_TEXT.items() if f & b))
-
-    def results(self):
-        """One read-back: ``{"metrics": {name: (mean, n, dev)}, "pairs": {"i_j": (sum of results, n)}}`` with the
-        reference's shapes [C, nb + 2] and [C, nb_i + 2, nb_j + 2]."""
-        self._check_flags()
-        return split_real_results(self.tables.cpu().numpy(), self._layout, self.names)
+    def split(self, host, last_metric_factor=1):
+        return finish_real_tables(raw_real_tables(host, self._layout), self.names, last_metric_factor)

@@ -27,8 +27,10 @@ import numpy as np
 import torch
 
 from .. import _lib
-from .metric_pairs import MetricPairTables, bin_edge_range, normalized_range, split_results
-from .segments import SE_DEAD_PMTS, segment_status
+from .eval_common import (check_coords, check_n_valid, raise_flags, read_back, require_device_tensors, require_gpu,
+                          reserve_rows, seg_status_tensor)
+from .metric_pairs import MetricPairTables, bin_edge_range, normalized_range
+from .segments import SE_DEAD_PMTS
 
 FLAG_TEXT = {1: "the event column of a batch was not sorted or held an event outside the batch",
              2: "a segment coordinate lay outside the detector grid",
@@ -67,31 +69,35 @@ def metric_setup(e_scale=None, bin_overrides=None):
                 normalized_ranges=[normalized_range(lo, hi, nf) for (lo, hi), nf in zip(edges, norm)])
 
 
+def set_metric_attributes(ev, setup):
+    """The attributes every evaluator built on ``metric_setup`` carries, under the reference's names."""
+    ev.z_scale, ev.E_scale, ev.E_adjust = setup["z_scale"], setup["E_scale"], setup["E_adjust"]
+    ev.E_index, ev.PSD_index, ev.z_index = E_INDEX, PSD_INDEX, Z_INDEX
+    ev.default_bins = setup["default_bins"]
+    ev.metric_names, ev.metric_params = setup["metric_names"], setup["metric_params"]
+    ev.normalized_ranges = setup["normalized_ranges"]         # MetricAggregator.add_normalized's
+
+
 class PIDEvaluator:
+    # the zero-filled per-row buffers of ``add``
+    _ROW_BUFFERS = [(n, torch.int32, (-1,)) for n in ("accuracy", "multiplicity", "se_mask", "n_SE", "category")] + \
+                   [("parameters", torch.float32, (4, -1))]
+
     def __init__(self, device, additional_field_names=("phys",), e_scale=None, seg_status=None,
                  dead_pmts=SE_DEAD_PMTS, n_confusion=10, n_SE_max=6, bin_overrides=None):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("waveformml_amd: PIDEvaluator runs on the GPU (there is no CPU path); got %s" % self.device)
+        self.device = require_gpu(device, "PIDEvaluator")
         self.nx, self.ny = 14, 11
         setup = metric_setup(e_scale, bin_overrides)
-        self.z_scale, self.E_scale, self.E_adjust = setup["z_scale"], setup["E_scale"], setup["E_adjust"]
-        self.E_index, self.PSD_index, self.z_index = E_INDEX, PSD_INDEX, Z_INDEX
-        self.default_bins = setup["default_bins"]
+        set_metric_attributes(self, setup)
+        self.norm_factors = setup["norm_factors"]
         self.additional_field_names = list(additional_field_names) if additional_field_names is not None else ["phys"]
         self.phys_index = self.additional_field_names.index("phys") if "phys" in self.additional_field_names else 0
         self.n_confusion, self.n_SE_max = int(n_confusion), int(n_SE_max)
         self.class_names = [PID_MAPPED_NAMES[i] for i in range(5)]
         self.n_classes = len(self.class_names)
-        self.metric_names, self.metric_params = setup["metric_names"], setup["metric_params"]
-        self.norm_factors = setup["norm_factors"]
-        s = segment_status(dead_pmts, self.nx, self.ny) if seg_status is None else np.asarray(seg_status, np.float32)
-        if s.shape != (self.nx, self.ny):
-            raise ValueError("seg_status must be [%d, %d]" % (self.nx, self.ny))
-        self.seg_status = torch.from_numpy(np.ascontiguousarray(s)).to(self.device)
+        self.seg_status = seg_status_tensor(self.device, seg_status, dead_pmts, self.nx, self.ny)
         self.metric_pairs = MetricPairTables(self.device, [(n, *p) for n, p in zip(self.metric_names, self.metric_params)],
                                              self.class_names)
-        self.normalized_ranges = setup["normalized_ranges"]       # MetricAggregator.add_normalized's
         self.confusion_energy_high = self.n_confusion / self.E_scale
         C = self.n_classes
         self._layout = [("SE_confusion", (C, C)), ("confusion_SE", (self.n_SE_max + 2, C, C)),
@@ -101,20 +107,6 @@ class PIDEvaluator:
         self.tables = torch.zeros(n, dtype=torch.int64, device=self.device)
         self.flags = torch.zeros(1, dtype=torch.int32, device=self.device)
         self._rows_cap, self._offsets = -1, None
-
-    def _reserve(self, rows, events):
-        """Per-batch buffers; allocated on the first call and again only when the row count changes."""
-        dev = self.device
-        if rows != self._rows_cap:
-            self.accuracy = torch.zeros(rows, dtype=torch.int32, device=dev)
-            self.multiplicity = torch.zeros(rows, dtype=torch.int32, device=dev)
-            self.se_mask = torch.zeros(rows, dtype=torch.int32, device=dev)
-            self.n_SE = torch.zeros(rows, dtype=torch.int32, device=dev)
-            self.category = torch.zeros(rows, dtype=torch.int32, device=dev)
-            self.parameters = torch.zeros((4, rows), dtype=torch.float32, device=dev)
-            self._rows_cap = rows
-        if self._offsets is None or self._offsets.shape[0] != events + 1:
-            self._offsets = torch.zeros(events + 1, dtype=torch.int32, device=dev)
 
     def add(self, pred, target, c, additional_fields=None, n_valid=None, n_events=None):
         """The reference's signature (PIDEvaluator.add): ``pred`` and ``target`` int64 class indices [N], ``c`` int32
@@ -129,23 +121,19 @@ class PIDEvaluator:
         if isinstance(phys, (list, tuple)):
             phys = phys[0]
         rows = int(c.shape[0])
-        for t in (pred, target, c, phys):
-            if not t.is_cuda:
-                raise RuntimeError("waveformml_amd: tensor must live on the GPU (there is no CPU path); got %s" % t.device)
-        if c.dtype != torch.int32 or c.dim() != 2 or c.shape[1] != 3:
-            raise RuntimeError("PIDEvaluator.add: coords must be int32 [N, 3] = (x, y, event)")
+        require_device_tensors(pred, target, c, phys)
+        check_coords(c, None, "PIDEvaluator.add")
         if pred.dtype != torch.int64 or target.dtype != torch.int64 or tuple(pred.shape) != (rows,) or \
                 tuple(target.shape) != (rows,):
             raise RuntimeError("PIDEvaluator.add: predictions and targets must be int64 [N] class indices")
         if phys.dim() != 2 or phys.shape[0] != rows or phys.shape[1] <= max(self.E_index, self.PSD_index, self.z_index):
             raise RuntimeError("PIDEvaluator.add: phys must be [N, n_phys > %d], got %s"
                                % (max(self.E_index, self.PSD_index, self.z_index), tuple(phys.shape)))
-        if n_valid is not None and (n_valid.dtype != torch.int64 or not n_valid.is_cuda):
-            raise RuntimeError("PIDEvaluator.add: n_valid must be a device int64")
+        check_n_valid(n_valid, "PIDEvaluator.add")
         if rows == 0:
             return
         E = int(n_events) if n_events is not None else rows
-        self._reserve(rows, E)
+        reserve_rows(self, rows, self._ROW_BUFFERS, E)
         p = _lib.ptr
         _lib.check(_lib.load().wfs_pid_row_stats(
             p(c), p(pred), p(target), p(phys), int(phys.shape[1]), _lib.dtype_code(phys), rows, p(n_valid), E,
@@ -164,20 +152,12 @@ class PIDEvaluator:
         """The persistent accumulators: integer sums over batches, so N ranks combine them with one SUM all-reduce each."""
         return [self.tables] + self.metric_pairs.state_tensors()
 
-    def _check_flags(self, f):
-        if f:
-            raise RuntimeError("PIDEvaluator: " + "; ".join(t for b, t in FLAG_TEXT.items() if f & b))
-
     def results(self):
         """One read-back.  ``SE_confusion`` [5, 5], ``confusion_SE`` [n_SE_max + 2, 5, 5], ``confusion_energy``
         [n_confusion + 1, 5, 5] as int64 (label-major), and ``metric_pairs`` = ``MetricPairTables.results()``."""
         mp = self.metric_pairs
-        host = torch.cat([self.flags.to(torch.int64), mp.flags.to(torch.int64), self.tables, mp.tables]).cpu().numpy()
-        self._check_flags(int(host[0]) | int(host[1]))
-        res, at = {}, 2
-        for name, shape in self._layout:
-            size = int(np.prod(shape))
-            res[name] = host[at:at + size].reshape(shape).copy()
-            at += size
-        res["metric_pairs"] = split_results(host[at:], mp._layout, mp.names)
+        cur = read_back(self.flags, mp.flags, self.tables, mp.tables)
+        raise_flags("PIDEvaluator", int(cur.take(1)[0]) | int(cur.take(1)[0]), FLAG_TEXT)
+        res = {name: cur.take(shape).copy() for name, shape in self._layout}
+        res["metric_pairs"] = mp.split(cur.rest())
         return res

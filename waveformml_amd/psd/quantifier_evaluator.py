@@ -49,9 +49,11 @@ import numpy as np
 import torch
 
 from .. import _lib
-from .metric_pairs import RealMetricPairTables, split_real_results
-from .pid_evaluator import E_INDEX, PID_MAPPED_NAMES, PSD_INDEX, Z_INDEX, metric_setup
-from .segments import SE_DEAD_PMTS, segment_status
+from .eval_common import (check_coords, check_n_valid, pid_field, raise_flags, read_back, require_device_tensors,
+                          require_gpu, reserve_rows, seg_status_tensor)
+from .metric_pairs import REAL_FLAG_TEXT, RealMetricPairTables
+from .pid_evaluator import PID_MAPPED_NAMES, metric_setup, set_metric_attributes
+from .segments import SE_DEAD_PMTS
 
 FLAG_TEXT = {1: "the event column of a batch was not sorted or held an event outside the batch",
              2: "a segment coordinate lay outside the detector grid"}
@@ -60,18 +62,20 @@ N_SLOTS = 6
 
 
 class SegEvaluator:
+    # the zero-filled per-row buffers of ``add``
+    _ROW_BUFFERS = [("mae", torch.float32, (-1,)), ("error", torch.float64, (-1,))] + \
+                   [(n, torch.int32, (-1,)) for n in ("multiplicity", "se_mask", "category", "slot")] + \
+                   [("parameters", torch.float32, (4, -1))]
+
     def __init__(self, device, additional_field_names=None, e_scale=None, seg_status=None, dead_pmts=SE_DEAD_PMTS,
                  bin_overrides=None, target_index=4, error_edges=None, calgroup=None):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("waveformml_amd: SegEvaluator runs on the GPU (there is no CPU path); got %s" % self.device)
+        self.device = require_gpu(device, "SegEvaluator")
         if calgroup is not None:
             raise RuntimeError("SegEvaluator: the calibration database (calgroup) is not mirrored")
         self.nx, self.ny = 14, 11
         setup = metric_setup(e_scale, bin_overrides)
-        self.z_scale, self.E_scale, self.E_adjust = setup["z_scale"], setup["E_scale"], setup["E_adjust"]
-        self.E_index, self.PSD_index, self.z_index = E_INDEX, PSD_INDEX, Z_INDEX
-        self.default_bins = setup["default_bins"]
+        set_metric_attributes(self, setup)
+        self.norm_factors = setup["norm_factors"]
         self.target_index = int(target_index)
         if not 0 <= self.target_index < len(self.default_bins):
             raise ValueError("SegEvaluator: target_index must name one of the %d phys columns" % len(self.default_bins))
@@ -87,12 +91,7 @@ class SegEvaluator:
         else:
             self.class_names, self.class_PIDs = ["all"], None
         self.n_classes = len(self.class_names)
-        self.metric_names, self.metric_params = setup["metric_names"], setup["metric_params"]
-        self.norm_factors, self.normalized_ranges = setup["norm_factors"], setup["normalized_ranges"]
-        s = segment_status(dead_pmts, self.nx, self.ny) if seg_status is None else np.asarray(seg_status, np.float32)
-        if s.shape != (self.nx, self.ny):
-            raise ValueError("seg_status must be [%d, %d]" % (self.nx, self.ny))
-        self.seg_status = torch.from_numpy(np.ascontiguousarray(s)).to(self.device)
+        self.seg_status = seg_status_tensor(self.device, seg_status, dead_pmts, self.nx, self.ny)
         self.metric_pairs = RealMetricPairTables(
             self.device, [(n, *p) for n, p in zip(self.metric_names, self.metric_params)], self.class_names)
         self.n_bins = int(self.default_bins[self.target_index][2])
@@ -122,21 +121,6 @@ class SegEvaluator:
             self.error_edges[:, 1] = self.fixed_edges[1]
             self.error_edges_set.fill_(1)
 
-    def _reserve(self, rows, events):
-        """Per-batch buffers; allocated on the first call and again only when the row count changes."""
-        dev = self.device
-        if rows != self._rows_cap:
-            self.mae = torch.zeros(rows, dtype=torch.float32, device=dev)
-            self.error = torch.zeros(rows, dtype=torch.float64, device=dev)
-            self.multiplicity = torch.zeros(rows, dtype=torch.int32, device=dev)
-            self.se_mask = torch.zeros(rows, dtype=torch.int32, device=dev)
-            self.category = torch.zeros(rows, dtype=torch.int32, device=dev)
-            self.slot = torch.zeros(rows, dtype=torch.int32, device=dev)
-            self.parameters = torch.zeros((4, rows), dtype=torch.float32, device=dev)
-            self._rows_cap = rows
-        if self._offsets is None or self._offsets.shape[0] != events + 1:
-            self._offsets = torch.zeros(events + 1, dtype=torch.int32, device=dev)
-
     def add(self, results, target, c, additional_fields=None, n_valid=None, n_events=None):
         """The reference's signature (SegEvaluator.add): ``results`` [N] fp32 / bf16 / fp16 predictions, ``target``
         [N, n_phys >= 6] of the same kinds, ``c`` int32 [N, 3] = (x, y, event), ``additional_fields`` the list of extra
@@ -144,17 +128,10 @@ class SegEvaluator:
         ``n_valid``: device-side row count of a capacity-padded batch.  ``n_events``: the batch's event count; without it
         the row count bounds the event indices.  Launches on the current stream; no read-back, the caller's tensors are
         only read."""
-        pid = None
-        if self.has_PID:
-            if additional_fields is None:
-                raise RuntimeError("SegEvaluator.add: additional_field_names holds \"PID\" but no additional fields came")
-            pid = additional_fields[self.PID_index]
+        pid = pid_field(additional_fields, self.PID_index, "SegEvaluator.add") if self.has_PID else None
         rows = int(c.shape[0])
-        for t in (results, target, c) + ((pid,) if pid is not None else ()):
-            if not t.is_cuda:
-                raise RuntimeError("waveformml_amd: tensor must live on the GPU (there is no CPU path); got %s" % t.device)
-        if c.dtype != torch.int32 or c.dim() != 2 or c.shape[1] != 3:
-            raise RuntimeError("SegEvaluator.add: coords must be int32 [N, 3] = (x, y, event)")
+        require_device_tensors(results, target, c, pid)
+        check_coords(c, None, "SegEvaluator.add")
         if tuple(results.shape) != (rows,):
             raise RuntimeError("SegEvaluator.add: results must be [N], got %s" % (tuple(results.shape),))
         need = max(self.E_index, self.PSD_index, self.z_index, self.target_index)
@@ -162,13 +139,12 @@ class SegEvaluator:
             raise RuntimeError("SegEvaluator.add: target must be [N, n_phys > %d], got %s" % (need, tuple(target.shape)))
         if pid is not None and (pid.dtype not in (torch.int32, torch.int64) or tuple(pid.shape) != (rows,)):
             raise RuntimeError("SegEvaluator.add: PID must be int32 or int64 [N]")
-        if n_valid is not None and (n_valid.dtype != torch.int64 or not n_valid.is_cuda):
-            raise RuntimeError("SegEvaluator.add: n_valid must be a device int64")
+        check_n_valid(n_valid, "SegEvaluator.add")
         if rows == 0:
             return
         results, target = results.contiguous(), target.contiguous()
         E = int(n_events) if n_events is not None else rows
-        self._reserve(rows, E)
+        reserve_rows(self, rows, self._ROW_BUFFERS, E)
         p, lib = _lib.ptr, _lib.load()
         rd, td, n_phys = _lib.dtype_code(results), _lib.dtype_code(target), int(target.shape[1])
         _lib.check(lib.wfs_segq_row_stats(
@@ -206,28 +182,19 @@ class SegEvaluator:
         mp = self.metric_pairs
         C, nb = self.n_classes, self.n_bins
         edge_bits = self.error_edges.reshape(-1).view(torch.int64)
-        host = torch.cat([self.flags.to(torch.int64), mp.flags.to(torch.int64), self.error_flags.to(torch.int64),
-                          self.error_edges_set.to(torch.int64), edge_bits, self.error_hist.reshape(-1),
-                          self.error_2d.reshape(-1), mp.tables]).cpu().numpy()
-        f = int(host[0])
-        if f:
-            raise RuntimeError("SegEvaluator: " + "; ".join(t for b, t in FLAG_TEXT.items() if f & b))
-        if int(host[2]):
-            bad = [self.class_names[k] for k in range(C) if int(host[2]) >> k & 1]
+        cur = read_back(self.flags, mp.flags, self.error_flags, self.error_edges_set, edge_bits, self.error_hist,
+                        self.error_2d, mp.tables)
+        f, f_pairs, f_edges = (int(v) for v in cur.take(3))
+        raise_flags("SegEvaluator", f, FLAG_TEXT)
+        if f_edges:
+            bad = [self.class_names[k] for k in range(C) if f_edges >> k & 1]
             raise RuntimeError("SegEvaluator: the first rows of class %s had a largest |error| of 0 or one that is not "
                                "finite: no error histogram range follows from it" % ", ".join(bad))
-        if int(host[1]):
-            from .metric_pairs import REAL_FLAG_TEXT
-            raise RuntimeError("SegEvaluator: " + "; ".join(t for b, t in REAL_FLAG_TEXT.items() if int(host[1]) & b))
-        at = 3
-        res = {"error_edges_set": host[at:at + C].astype(np.int32)}
-        at += C
-        res["error_edges"] = host[at:at + 2 * C].copy().view(np.float64).reshape(C, 2)
-        at += 2 * C
-        res["error_hist"] = host[at:at + C * (nb + 2)].reshape(C, nb + 2).copy()
-        at += C * (nb + 2)
-        res["error_2d"] = host[at:at + C * (nb + 2) ** 2].reshape(C, nb + 2, nb + 2).copy()
-        at += C * (nb + 2) ** 2
-        res["metric_pairs"] = split_real_results(host[at:], mp._layout, mp.names)
+        raise_flags("SegEvaluator", f_pairs, REAL_FLAG_TEXT)
+        res = {"error_edges_set": cur.take(C).astype(np.int32)}
+        res["error_edges"] = cur.take(2 * C).copy().view(np.float64).reshape(C, 2)
+        res["error_hist"] = cur.take((C, nb + 2)).copy()
+        res["error_2d"] = cur.take((C, nb + 2, nb + 2)).copy()
+        res["metric_pairs"] = mp.split(cur.rest())
         res["scale_factor"] = self.scaling
         return res

@@ -40,10 +40,13 @@ import numpy as np
 import torch
 
 from .. import _lib
-from .metric_pairs import (REAL_FLAG_TEXT, RealMetricPairTables, real_triple_1d)
-from .pid_evaluator import CELL_LENGTH, E_INDEX, PID_MAPPED_NAMES, PSD_INDEX, Z_INDEX, metric_setup
-from .segment_evaluator import FIXED_ONE, _check_coords, _plane_args
-from .segments import SE_DEAD_PMTS, blind_left, segment_status
+from .eval_common import (FIXED_ONE, check_coords, pid_field, raise_flags, read_back, require_gpu, reserve_rows,
+                          seg_status_tensor)
+from .metric_pairs import REAL_FLAG_TEXT, RealMetricPairTables, finish_real_tables, raw_real_tables  # noqa: F401
+from .pid_evaluator import (CELL_LENGTH, E_INDEX, PID_MAPPED_NAMES, PSD_INDEX, Z_INDEX, metric_setup,  # noqa: F401
+                            set_metric_attributes)
+from .segment_evaluator import _plane_args
+from .segments import SE_DEAD_PMTS, blind_left
 
 FLAG_TEXT = {1: "the event column of a batch was not sorted or held an event outside the batch",
              2: "a segment coordinate lay outside the detector grid",
@@ -113,30 +116,6 @@ def sample_category(z, cls, n_classes):
     return np.where(ok, sl * n_classes + np.where(ok, cls, 0), N_SLICES * n_classes).astype(np.int32)
 
 
-def raw_real_tables(host, layout):
-    """{key: [int64 tables]} of a ``RealMetricPairTables`` buffer: n, S, Q0, Q1, Q2 per metric, n, S per pair."""
-    out, at = {}, 0
-    for key, shape, tabs in layout:
-        size = int(np.prod(shape))
-        out[key] = [host[at + k * size:at + (k + 1) * size].reshape(shape) for k in range(tabs)]
-        at += tabs * size
-    return out
-
-
-def finish_real_tables(raw, names, last_metric_factor=1):
-    """``{"metrics": {name: (mean, n, dev)}, "pairs": {"i_j": (sum, n)}}`` from integer tables; ``last_metric_factor``
-    multiplies n, S and Q of the last metric's 1-D table (every row entered that many times)."""
-    out = {"metrics": {}, "pairs": {}}
-    last = len(names) - 1
-    for key, t in raw.items():
-        if isinstance(key, int):
-            f = last_metric_factor if key == last else 1
-            out["metrics"][names[key]] = real_triple_1d(*[a * f for a in t])
-        else:
-            out["pairs"][key] = (t[1].astype(np.float64) / FIXED_ONE, t[0].copy())
-    return out
-
-
 def split_sample_tables(raw, names, n_classes):
     """The reference's 13 sample aggregators from the category-encoded tables: a list of 12 per-slice results with
     [C, ...] tables and, last, the all-z aggregator (class "any", [1, ...]) as the integer sum over every category,
@@ -152,24 +131,24 @@ def split_sample_tables(raw, names, n_classes):
 
 class ZEvaluatorRealWFNorm:
     name = "ZEvaluatorRealWFNorm"
+    # the zero-filled per-row buffers of ``add``
+    _ROW_BUFFERS = [(n, torch.float32, (-1,)) for n in ("z_pred", "z_true", "energy", "mae", "dev_mm", "baseline")] + \
+                   [(n, torch.int32, (-1,)) for n in ("class_category", "sample_category", "se_mask")] + \
+                   [("parameters", torch.float32, (4, -1)), ("samples", torch.float32, (2, PULSE_ANALYSIS_SAMPLES, -1)),
+                    ("start", torch.int32, (-1, 2))]
 
     def __init__(self, device, e_scale=None, additional_field_names=None, wf_analysis=_UNSET, bin_overrides=None,
                  excludes=None, seg_status=None, blind_detl=None, dead_pmts=SE_DEAD_PMTS, namespace=None, calgroup=None,
                  count_last_metric_once=False):
         """``excludes``: the reference's keyword for the list of dead PMTs (SingleEndedEvaluator); ``dead_pmts`` is this
         project's name for it.  ``wf_analysis``: present (whatever its value) switches the waveform analysis on."""
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("waveformml_amd: ZEvaluatorRealWFNorm runs on the GPU (there is no CPU path); got %s"
-                               % self.device)
+        self.device = require_gpu(device, "ZEvaluatorRealWFNorm")
         if calgroup is not None:
             raise RuntimeError("ZEvaluatorRealWFNorm: the calibration database (calgroup) is not mirrored")
         self.nx, self.ny = 14, 11
         dead_pmts = dead_pmts if excludes is None else tuple(excludes)
         s = z_real_setup(e_scale, bin_overrides)
-        self.z_scale, self.E_scale, self.E_adjust = s["z_scale"], s["E_scale"], s["E_adjust"]
-        self.E_index, self.PSD_index, self.z_index = E_INDEX, PSD_INDEX, Z_INDEX
-        self.default_bins = s["default_bins"]
+        set_metric_attributes(self, s)
         self.E_bounds, self.mult_bounds, self.z_bounds = s["E_bounds"], s["mult_bounds"], s["z_bounds"]
         self.n_mult, self.n_E, self.n_z = s["n_mult"], s["n_E"], s["n_z"]
         self.E_low, self.E_high = s["E_low"], s["E_high"]
@@ -184,14 +163,12 @@ class ZEvaluatorRealWFNorm:
         self.sample_class_names = self.class_names if self.has_PID else ["any"]
         self.n_sample_classes = len(self.sample_class_names)
         self.last_metric_factor = 1 if count_last_metric_once else len(s["metric_names"]) - 1
-        st = segment_status(dead_pmts, self.nx, self.ny) if seg_status is None else np.asarray(seg_status, np.float32)
+        both = "seg_status and blind_detl must be [%d, %d]"
+        self.seg_status = seg_status_tensor(self.device, seg_status, dead_pmts, self.nx, self.ny, both)
         bl = blind_left(dead_pmts, self.nx, self.ny) if blind_detl is None else np.asarray(blind_detl, np.int32)
-        if st.shape != (self.nx, self.ny) or bl.shape != (self.nx, self.ny):
-            raise ValueError("seg_status and blind_detl must be [%d, %d]" % (self.nx, self.ny))
-        self.seg_status = torch.from_numpy(np.ascontiguousarray(st)).to(self.device)
+        if bl.shape != (self.nx, self.ny):
+            raise ValueError(both % (self.nx, self.ny))
         self.blind_detl = torch.from_numpy(np.ascontiguousarray(bl)).to(self.device)
-        self.metric_names, self.metric_params = s["metric_names"], s["metric_params"]
-        self.normalized_ranges = s["normalized_ranges"]
         self.sample_names, self.sample_params = s["sample_names"], s["sample_params"]
         self.metric_pairs = self.sample_pairs = None
         if self.has_PID:
@@ -207,21 +184,7 @@ class ZEvaluatorRealWFNorm:
         assert n == sum(2 * int(np.prod(sh)) for _n, sh in self._layout)
         self.tables = torch.zeros((2, n), dtype=torch.int64, device=self.device)       # the network's, the baseline's
         self.flags = torch.zeros(1, dtype=torch.int32, device=self.device)
-        self._rows_cap, self._L, self._offsets = -1, -1, None
-
-    def _reserve(self, rows, events, L):
-        """Per-batch buffers; allocated on the first call and again only when the row count changes."""
-        dev = self.device
-        if rows != self._rows_cap:
-            f = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
-            i = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)
-            self.z_pred, self.z_true, self.energy, self.mae, self.dev_mm, self.baseline = (f(rows) for _ in range(6))
-            self.parameters = f(4, rows)
-            self.class_category, self.sample_category, self.se_mask = i(rows), i(rows), i(rows)
-            self.samples, self.start = f(2, PULSE_ANALYSIS_SAMPLES, rows), i(rows, 2)
-            self._rows_cap = rows
-        if self._offsets is None or self._offsets.shape[0] != events + 1:
-            self._offsets = torch.zeros(events + 1, dtype=torch.int32, device=dev)
+        self._rows_cap, self._offsets = -1, None
 
     def add(self, predictions, target, c, f, additional_fields=None, n_valid=None, n_events=None):
         """The reference's signature: ``predictions`` a dense [B, 1, 14, 11] map (plane 0 is scored), ``target`` the
@@ -231,17 +194,14 @@ class ZEvaluatorRealWFNorm:
         ``additional_field_names`` is used (int32 or int64 [N]).  ``n_valid``: device-side row count of a
         capacity-padded batch.  ``n_events``: the batch's event count when it is below B.  Launches on the current
         stream; no read-back, the caller's tensors are only read."""
-        _check_coords(c, n_valid, "ZEvaluatorRealWFNorm.add")
+        check_coords(c, n_valid, "ZEvaluatorRealWFNorm.add")
+        rows, B = int(c.shape[0]), int(predictions.shape[0])
         pid = None
         if self.has_PID:
-            if additional_fields is None:
-                raise RuntimeError("ZEvaluatorRealWFNorm.add: additional_field_names holds \"PID\" but no additional "
-                                   "fields came")
-            pid = additional_fields[self.PID_index]
-            if not pid.is_cuda or pid.dtype not in (torch.int32, torch.int64) or tuple(pid.shape) != (int(c.shape[0]),):
+            pid = pid_field(additional_fields, self.PID_index, "ZEvaluatorRealWFNorm.add")
+            if not pid.is_cuda or pid.dtype not in (torch.int32, torch.int64) or tuple(pid.shape) != (rows,):
                 raise RuntimeError("ZEvaluatorRealWFNorm.add: PID must be a device int32 or int64 [N]")
             pid = pid.contiguous()
-        rows, B = int(c.shape[0]), int(predictions.shape[0])
         E = B if n_events is None else int(n_events)
         if not 1 <= E <= B:
             raise RuntimeError("ZEvaluatorRealWFNorm.add: n_events must lie in [1, %d]" % B)
@@ -255,7 +215,7 @@ class ZEvaluatorRealWFNorm:
             if not f.is_cuda or f.dim() != 2 or f.shape[0] != rows or f.shape[1] % 2 or f.shape[1] < 2:
                 raise RuntimeError("ZEvaluatorRealWFNorm.add: f must be device rows [N, 2 L], got %s" % (tuple(f.shape),))
             f, L = f.contiguous(), int(f.shape[1]) // 2
-        self._reserve(rows, E, L)
+        reserve_rows(self, rows, self._ROW_BUFFERS, E)
         p, lib, stream = _lib.ptr, _lib.load(), _lib.stream_ptr()
         _lib.check(lib.wfs_zreal_row_stats(
             p(c), *pa, ta[0], ta[1], ta[2], ta[3], self.z_index, self.E_index, self.PSD_index, p(pid),
@@ -300,40 +260,30 @@ class ZEvaluatorRealWFNorm:
         with [5, ...] shapes; ``"z_binned_metric_pairs"`` (with ``wf_analysis``): the 13 sample aggregators in the
         reference's order, twelve slices with [C, ...] tables and the all-z one with [1, ...];
         ``"unbinned_sample_pairs"``: the leftover category's own tables; ``"class_out_of_range"``."""
-        parts = [self.flags.to(torch.int64)]
+        parts = [self.flags]
         for t in (self.metric_pairs, self.sample_pairs):
-            parts.append((t.flags if t is not None else torch.zeros_like(self.flags)).to(torch.int64))
-        parts.append(self.tables.reshape(-1))
+            parts.append(t.flags if t is not None else torch.zeros_like(self.flags))
+        parts.append(self.tables)
         for t in (self.metric_pairs, self.sample_pairs):
             if t is not None:
                 parts.append(t.tables)
-        host = torch.cat(parts).cpu().numpy()
-        f = int(host[0])
-        if f & ~CLASS_RANGE_FLAG:
-            raise RuntimeError("%s: %s" % (self.name, "; ".join(t for b, t in FLAG_TEXT.items() if f & b)))
-        for k, what in ((1, "class tables"), (2, "sample tables")):
-            if int(host[k]):
-                raise RuntimeError("%s, %s: %s" % (self.name, what, "; ".join(
-                    t for b, t in REAL_FLAG_TEXT.items() if int(host[k]) & b)))
-        res, at = {"class_out_of_range": bool(f & CLASS_RANGE_FLAG)}, 3
+        cur = read_back(*parts)
+        f, f_class, f_sample = (int(v) for v in cur.take(3))
+        raise_flags(self.name, f & ~CLASS_RANGE_FLAG, FLAG_TEXT)
+        raise_flags(self.name + ", class tables", f_class, REAL_FLAG_TEXT)
+        raise_flags(self.name + ", sample tables", f_sample, REAL_FLAG_TEXT)
+        res = {"class_out_of_range": bool(f & CLASS_RANGE_FLAG)}
         for cal in ("", "_cal"):
             for name, shape in self._layout:
-                size = int(np.prod(shape))
-                n = host[at:at + size].reshape(shape).copy()
-                s = host[at + size:at + 2 * size].reshape(shape).astype(np.float64) / FIXED_ONE
-                res[name + cal] = (s, n)
-                at += 2 * size
+                n, s = cur.take_pair(shape)
+                res[name + cal] = (s.astype(np.float64) / FIXED_ONE, n.copy())
         if self.metric_pairs is not None:
             mp = self.metric_pairs
-            size = int(mp.tables.shape[0])
-            res["metric_pairs"] = finish_real_tables(raw_real_tables(host[at:at + size], mp._layout), mp.names,
-                                                     self.last_metric_factor)
-            at += size
+            res["metric_pairs"] = mp.split(cur.take(mp.tables.shape[0]), self.last_metric_factor)
         if self.sample_pairs is not None:
             sp = self.sample_pairs
-            raw = raw_real_tables(host[at:at + int(sp.tables.shape[0])], sp._layout)
             res["z_binned_metric_pairs"], res["unbinned_sample_pairs"] = split_sample_tables(
-                raw, sp.names, self.n_sample_classes)
+                raw_real_tables(cur.take(sp.tables.shape[0]), sp._layout), sp.names, self.n_sample_classes)
         return res
 
     def retrieve_error_metrics(self, results=None):

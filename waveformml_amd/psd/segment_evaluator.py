@@ -27,13 +27,14 @@ import numpy as np
 import torch
 
 from .. import _lib
-from .segments import SE_DEAD_PMTS, segment_status
+from .eval_common import (FIXED_ONE, check_coords, raise_flags, read_back, require_device_tensors, require_gpu,
+                          reserve_offsets, seg_status_tensor)
+from .segments import SE_DEAD_PMTS
 
 FLAG_TEXT = {1: "the event column of a batch was not sorted or held an event outside the batch",
              2: "a segment coordinate lay outside the detector grid",
              4: "an energy target was zero (the relative error divides by it)",
              8: "a deviation was not finite or too large for the fixed-point sums, or a sum overflowed"}
-FIXED_ONE = 4294967296.0        # WFS_SEG_FIXED_ONE, include/wfsparse.h
 
 
 def z_result_shapes(nmult=6, n_bins=20, n_err_bins=50, n_sample=3, nx=14, ny=11):
@@ -59,18 +60,10 @@ def energy_result_shapes(n_mult=10, n_E=20, n_z=20, nx=14, ny=11):
     return shapes
 
 
-def _require_gpu(device, what):
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise RuntimeError("waveformml_amd: %s runs on the GPU (there is no CPU path); got %s" % (what, device))
-    return device
-
-
 def _plane_args(t, plane, B, nx, ny, what):
     """(pointer, dtype code, batch stride, plane stride, plane) of plane ``plane`` of a [B, P, nx, ny] map; a
     [B, nx, ny] map counts as P = 1."""
-    if not t.is_cuda:
-        raise RuntimeError("waveformml_amd: tensor must live on the GPU (there is no CPU path); got %s" % t.device)
+    require_device_tensors(t)
     if t.dim() == 3:
         t = t.unsqueeze(1)
     if t.dim() != 4 or t.shape[0] != B or t.shape[2] != nx or t.shape[3] != ny or not 0 <= plane < t.shape[1]:
@@ -78,15 +71,6 @@ def _plane_args(t, plane, B, nx, ny, what):
     if t.stride(3) != 1 or t.stride(2) != ny or t.stride(0) < 0 or t.stride(1) < 0:
         raise RuntimeError("%s: the [%d, %d] planes must be contiguous" % (what, nx, ny))
     return ctypes.c_void_p(t.data_ptr()), _lib.dtype_code(t), t.stride(0), t.stride(1), plane
-
-
-def _check_coords(c, n_valid, what):
-    if not c.is_cuda:
-        raise RuntimeError("waveformml_amd: tensor must live on the GPU (there is no CPU path); got %s" % c.device)
-    if c.dtype != torch.int32 or c.dim() != 2 or c.shape[1] != 3:
-        raise RuntimeError("%s: coords must be int32 [N, 3] = (x, y, event)" % what)
-    if n_valid is not None and (n_valid.dtype != torch.int64 or not n_valid.is_cuda):
-        raise RuntimeError("%s: n_valid must be a device int64" % what)
 
 
 class _SegmentTables:
@@ -100,11 +84,6 @@ class _SegmentTables:
         self.flags = torch.zeros(1, dtype=torch.int32, device=self.device)
         self._offsets = None
 
-    def _offsets_for(self, B):
-        if self._offsets is None or self._offsets.shape[0] != B + 1:
-            self._offsets = torch.zeros(B + 1, dtype=torch.int32, device=self.device)
-        return self._offsets
-
     def reset(self):
         self.tables.zero_()
         self.flags.zero_()
@@ -114,25 +93,18 @@ class _SegmentTables:
         return [self.tables]
 
     def _check_flags(self):
-        f = int(self.flags.item())
-        if f:
-            raise RuntimeError("%s: %s" % (self.name, "; ".join(t for b, t in FLAG_TEXT.items() if f & b)))
+        raise_flags(self.name, int(self.flags.item()), FLAG_TEXT)
 
     def _read_tables(self):
         """One read-back: {name: (float32 sums, int32 counts)} or {name: int32 counts}."""
         self._check_flags()
-        host = self.tables.cpu().numpy()
-        out, at = {}, 0
+        cur, out = read_back(self.tables), {}
         for name, shape, pair in self._layout:
-            size = int(np.prod(shape))
-            n = host[at:at + size].reshape(shape)
-            at += size
             if pair:
-                s = host[at:at + size].reshape(shape)
-                at += size
+                n, s = cur.take_pair(shape)
                 out[name] = ((s.astype(np.float64) / FIXED_ONE).astype(np.float32), n.astype(np.int32))
             else:
-                out[name] = n.astype(np.int32)
+                out[name] = cur.take(shape).astype(np.int32)
         return out
 
 
@@ -142,17 +114,14 @@ class ZEvaluator(_SegmentTables):
     def __init__(self, device, seg_status=None, use_energy=False, nmult=6, n_bins=20, n_err_bins=50, error_low=-1000.,
                  error_high=1000., z_scale=1200., E_low=0.0, E_high=10.0, true_E_high=9.0, E_scale=12.,
                  sample_segs=((5, 4), (10, 3), (7, 5)), nx=14, ny=11):
-        self.device = _require_gpu(device, "ZEvaluator")
+        self.device = require_gpu(device, "ZEvaluator")
         self.use_energy = bool(use_energy)
         self.nmult, self.n_bins, self.n_err_bins, self.nx, self.ny = int(nmult), int(n_bins), int(n_err_bins), int(nx), int(ny)
         self.error_low, self.error_high, self.z_scale = float(error_low), float(error_high), float(z_scale)
         self.E_low, self.E_high, self.true_E_high, self.E_scale = float(E_low), float(E_high), float(true_E_high), float(E_scale)
         self.has_true_E = False
-        s = segment_status(SE_DEAD_PMTS, self.nx, self.ny) if seg_status is None else np.asarray(seg_status, np.float32)
-        if s.shape != (self.nx, self.ny):
-            raise ValueError("seg_status must be [%d, %d]" % (self.nx, self.ny))
+        self.seg_status = seg_status_tensor(self.device, seg_status, SE_DEAD_PMTS, self.nx, self.ny)
         self.sample_segs = np.asarray(sample_segs, dtype=np.int32).reshape(-1, 2)
-        self.seg_status = torch.from_numpy(np.ascontiguousarray(s)).to(self.device)
         self._sample_segs = torch.from_numpy(np.ascontiguousarray(self.sample_segs)).to(self.device)
         ns, nm1, nb = len(self.sample_segs), self.nmult + 1, self.n_bins + 2
         n = int(_lib.load().wfs_seg_z_table_ints(self.nx, self.ny, self.nmult, self.n_bins, self.n_err_bins, ns))
@@ -176,7 +145,7 @@ class ZEvaluator(_SegmentTables):
     def add_planes(self, predictions, pred_plane, target, target_plane, c, E=None, E_plane=0, n_valid=None):
         """``add`` on chosen planes of [B, P, 14, 11] maps, without slicing them.  Launches on the current stream; no
         read-back, the caller's tensors are only read."""
-        _check_coords(c, n_valid, "ZEvaluator.add")
+        check_coords(c, n_valid, "ZEvaluator.add")
         B = int(predictions.shape[0])
         if E is not None:
             self.set_true_E()
@@ -190,7 +159,7 @@ class ZEvaluator(_SegmentTables):
         _lib.check(_lib.load().wfs_seg_z_accumulate(
             p(c), int(c.shape[0]), p(n_valid), B, *pa, *ta, *ea, p(self.seg_status), self.nx, self.ny,
             p(self._sample_segs), len(self.sample_segs), self.nmult, self.n_bins, self.z_scale, self.n_err_bins,
-            self.error_low, self.error_high, self.E_low, self.E_high, self.E_scale, p(self._offsets_for(B)),
+            self.error_low, self.error_high, self.E_low, self.E_high, self.E_scale, p(reserve_offsets(self, B)),
             p(self.tables), p(self.flags), _lib.stream_ptr()))
 
     def results(self):
@@ -220,13 +189,10 @@ class EnergyEvaluator(_SegmentTables):
     name = "EnergyEvaluator"
 
     def __init__(self, device, seg_status=None, n_mult=10, n_E=20, E_bounds=(0., 9.), E_scale=12., n_z=20, nx=14, ny=11):
-        self.device = _require_gpu(device, "EnergyEvaluator")
+        self.device = require_gpu(device, "EnergyEvaluator")
         self.n_mult, self.n_E, self.n_z, self.nx, self.ny = int(n_mult), int(n_E), int(n_z), int(nx), int(ny)
         self.E_bounds, self.E_scale = [float(E_bounds[0]), float(E_bounds[1])], float(E_scale)
-        s = segment_status(SE_DEAD_PMTS, self.nx, self.ny) if seg_status is None else np.asarray(seg_status, np.float32)
-        if s.shape != (self.nx, self.ny):
-            raise ValueError("seg_status must be [%d, %d]" % (self.nx, self.ny))
-        self.seg_status = torch.from_numpy(np.ascontiguousarray(s)).to(self.device)
+        self.seg_status = seg_status_tensor(self.device, seg_status, SE_DEAD_PMTS, self.nx, self.ny)
         nm1, nb = self.n_mult + 1, self.n_E + 2
         n = int(_lib.load().wfs_seg_energy_table_ints(self.nx, self.ny, self.n_mult, self.n_E))
         self._init_tables(n, [("seg_mult_Emape", (self.nx, self.ny, nm1), True), ("E_mult_single", (nb, nm1), True),
@@ -237,14 +203,14 @@ class EnergyEvaluator(_SegmentTables):
         self.add_planes(predictions, 0, target, 0, c, n_valid)
 
     def add_planes(self, predictions, pred_plane, target, target_plane, c, n_valid=None):
-        _check_coords(c, n_valid, "EnergyEvaluator.add")
+        check_coords(c, n_valid, "EnergyEvaluator.add")
         B = int(predictions.shape[0])
         pa = _plane_args(predictions, pred_plane, B, self.nx, self.ny, "predictions")
         ta = _plane_args(target, target_plane, B, self.nx, self.ny, "target")
         p = _lib.ptr
         _lib.check(_lib.load().wfs_seg_energy_accumulate(
             p(c), int(c.shape[0]), p(n_valid), B, *pa, *ta, p(self.seg_status), self.nx, self.ny, self.n_mult, self.n_E,
-            self.E_bounds[0], self.E_bounds[1], self.E_scale, p(self._offsets_for(B)), p(self.tables), p(self.flags),
+            self.E_bounds[0], self.E_bounds[1], self.E_scale, p(reserve_offsets(self, B)), p(self.tables), p(self.flags),
             _lib.stream_ptr()))
 
     def results(self):
@@ -279,7 +245,7 @@ class EZEvaluator:
                  energy_params=None):
         if planes not in ("reference", "lit"):
             raise ValueError("planes must be 'reference' or 'lit', got %r" % (planes,))
-        self.device = _require_gpu(device, "EZEvaluator")
+        self.device = require_gpu(device, "EZEvaluator")
         self.planes = planes
         self.energy_plane, self.z_plane = (0, 1) if planes == "reference" else (1, 0)
         self.EnergyEvaluator = EnergyEvaluator(device, seg_status=seg_status, E_scale=E_scale, **(energy_params or {}))

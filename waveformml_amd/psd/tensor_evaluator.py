@@ -25,7 +25,9 @@ import numpy as np
 import torch
 
 from .. import _lib
-from .metric_pairs import FIX_BITS, REAL_FLAG_TEXT, RealMetricPairTables, normalized_range, split_real_results
+from .eval_common import (FIXED_ONE, check_n_valid, raise_flags, read_back, require_device_tensors, require_gpu,
+                          reserve_rows)
+from .metric_pairs import REAL_FLAG_TEXT, RealMetricPairTables, normalized_range
 from .pid_evaluator import CELL_LENGTH, E_NORMALIZATION_FACTOR, Z_NORMALIZATION_FACTOR, default_bins
 
 PHYS_NAMES = ["Energy", "dt", "PE0", "PE1", "z", "PSD", "t offset", "distance to PMT"]
@@ -72,9 +74,7 @@ def metric_setup(e_scale=None, target_has_phys=False, target_index=None, metric_
 class TensorEvaluator:
     def __init__(self, device, calgroup=None, e_scale=None, target_has_phys=False, target_index=None, metric_name=None,
                  metric_unit=None, class_names=None, bin_overrides=None):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("waveformml_amd: TensorEvaluator runs on the GPU (there is no CPU path); got %s" % self.device)
+        self.device = require_gpu(device, "TensorEvaluator")
         if calgroup is not None:
             raise RuntimeError("TensorEvaluator: calgroup (the PROSPECT_CALDB calibration database) is not supported")
         self.nx, self.ny = 14, 11
@@ -97,22 +97,13 @@ class TensorEvaluator:
         self.flags = torch.zeros(1, dtype=torch.int32, device=self.device)
         self._rows_cap = -1
 
-    def _reserve(self, rows):
-        """Per-batch buffers; allocated on the first call and again only when the row count changes."""
-        if rows != self._rows_cap:
-            self.parameters = torch.zeros((self.P, rows), dtype=torch.float32, device=self.device)
-            self.category = torch.zeros(rows, dtype=torch.int32, device=self.device)
-            self._rows_cap = rows
-
     def add(self, c, f, target, results, n_valid=None):
         """The reference's signature (TensorEvaluator.add): ``c`` int32 / int64 detector numbers [N] or (x, y, side) rows
         [N, 3]; ``f`` the rows (not used, as in the reference); ``target`` [N, 8] fp32 / bf16 / fp16 with
         ``target_has_phys``, else [N] of those types or of int64 class indices; ``results`` the per-row loss [N].
         ``n_valid``: device-side row count of a capacity-padded batch.  Two launches on the current stream; no
         read-back, the caller's tensors are only read."""
-        for t in (c, target, results):
-            if not t.is_cuda:
-                raise RuntimeError("waveformml_amd: tensor must live on the GPU (there is no CPU path); got %s" % t.device)
+        require_device_tensors(c, target, results)
         if c.dim() == 2 and c.shape[1] == 1:
             c = c.reshape(-1)
         rows = int(c.shape[0])
@@ -125,15 +116,14 @@ class TensorEvaluator:
         if tuple(results.shape) != (rows,):
             raise RuntimeError("TensorEvaluator.add: results must be the per-row loss [%d], got %s"
                                % (rows, tuple(results.shape)))
-        if n_valid is not None and (n_valid.dtype != torch.int64 or not n_valid.is_cuda):
-            raise RuntimeError("TensorEvaluator.add: n_valid must be a device int64")
+        check_n_valid(n_valid, "TensorEvaluator.add")
         if rows == 0:
             return
         if target.dtype not in _TARGET_CODES:
             target = target.to(torch.float32)
         results = results.detach().to(torch.float32).contiguous()
         c, target = c.contiguous(), target.detach().contiguous()
-        self._reserve(rows)
+        reserve_rows(self, rows, [("parameters", torch.float32, (self.P, -1)), ("category", torch.int32, (-1,))])
         p = _lib.ptr
         _lib.check(_lib.load().wfs_tensor_rows(
             p(c), int(c.dtype == torch.int64), 1 if c.dim() == 1 else 3, p(target), _TARGET_CODES[target.dtype], self.P,
@@ -156,14 +146,10 @@ class TensorEvaluator:
         [14, 11, 2] float64, n [14, 11, 2] int64), ``scale_factor`` what the reference scales the metric by in its
         plots."""
         mp = self.metric_pairs
-        host = torch.cat([self.flags.to(torch.int64), mp.flags.to(torch.int64), self.det_tables, mp.tables]).cpu().numpy()
-        f = int(host[0]) | int(host[1])
-        if f:
-            raise RuntimeError("TensorEvaluator: " + "; ".join(t for b, t in REAL_FLAG_TEXT.items() if f & b))
-        cells = self.nx * self.ny * 2
-        shape = (self.nx, self.ny, 2)
-        res = split_real_results(host[2 + 2 * cells:], mp._layout, mp.names)
-        res[self.det_name] = (host[2 + cells:2 + 2 * cells].reshape(shape).astype(np.float64) / float(1 << FIX_BITS),
-                              host[2:2 + cells].reshape(shape).copy())
+        cur = read_back(self.flags, mp.flags, self.det_tables, mp.tables)
+        raise_flags("TensorEvaluator", int(cur.take(1)[0]) | int(cur.take(1)[0]), REAL_FLAG_TEXT)
+        n, s = cur.take_pair((self.nx, self.ny, 2))
+        res = mp.split(cur.rest())
+        res[self.det_name] = (s.astype(np.float64) / FIXED_ONE, n.copy())
         res["scale_factor"] = self.scale_factor
         return res
