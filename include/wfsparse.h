@@ -1126,6 +1126,49 @@ int wfs_predict_scatter(void *records, int64_t n, int64_t item_size, int64_t mem
                         int32_t col0, int32_t L, const int32_t *coords, const void *src, int32_t src_dtype, int32_t mode,
                         int64_t B, int32_t nx, int32_t ny, int32_t affine, float sub, float mul, void *stream);
 
+/* ---- GraphNet: FiLM message passing on an event-local kNN graph (csrc/graphconv.hip) ----------------------------
+ * The slice of the reference's src/models/GraphNet.py that its example configs use (graph_class_index 11): torch_cluster's
+ * knn_graph and torch_geometric's FiLMConv with mean aggregation, both RESTATED (neither library is available to hold the
+ * kernels to: parity unpinned).  Additions only: WFS_ABI_VERSION stays.
+ *
+ * Neighbour tables.  coords int32 [n_cap, 3] = (x, y, event), rows grouped by event; k in 1 .. wfs_graph_kmax() (= 8).
+ *   nbr int32 [n_cap, 8]: row i's neighbours ordered by (squared integer distance on (x, y), row index), -1 padded;
+ *   deg int32 [n_cap].  Candidates are the other valid rows of the same event; among equal distances the LOWER ROW INDEX
+ *   wins; the row itself is left out by index (self_loop != 0: it is a candidate at distance 0 and k counts it).  CONTRACT: an
+ *   event's run is at most 1024 rows (a detector event has at most 154); a row looks no further to either side, so a longer
+ *   run costs bounded time and no access leaves the arrays, but its lists and reverse lists are then undefined.
+ *   rev_pos int32 [n_cap, 2] = (start, count) into rev_rows int32 [n_cap * 8]: the rows that name row j as a neighbour, in
+ *   ascending row order (the backward pass's fixed summation order).  Rows at and beyond the valid count get deg 0, a list
+ *   of -1 and an empty reverse list, and appear in nobody's list.
+ *   wfs_graph_knn: two launches (lists, reverse lists).  wfs_graph_knn_host: the same selection rule -- one
+ *   __host__ __device__ function -- over HOST arrays (nbr, deg only), so that the rule can be checked without a GPU.
+ * Messages.  P [n_cap, 6 D] of `dtype` holds the six column blocks s | bs | gs | h | b | g of one product row
+ *   (x . lin_skip^T | split(x . film_skip^T) | x . lins.0^T | split(x . films.0^T + bias), beta first):
+ *     out_i = relu(gs_i * s_i + bs_i) + (1 / deg_i) sum_{j in nbr(i)} relu(g_i * h_j + b_i)        (0 edges: first term only)
+ *   wfs_film_message_fwd (one launch): out [n_cap, D] of `dtype`; rows at and beyond the valid count are written as 0.
+ *   wfs_film_message_bwd (one launch): dP [n_cap, 6 D] from dout [n_cap, D]; a ReLU passes where its argument -- the same
+ *   fused multiply-add of the same stored values -- is > 0; fp32 accumulators, the source-side sum walks the reverse list
+ *   in its order, no atomics: bit-identical from run to run.  Rows at and beyond the valid count are not written.
+ * wfs_rows_zero_tail (one launch; none without n_dev): X[n_valid .. n_cap) := 0 in place.
+ * Event max (torch_geometric's global_max_pool over the event column, whose numbers ascend with the rows):
+ *   wfs_event_max_fwd: Y [B, D] = the largest X over the rows of event e, arg int32 [B, D] the row it came from (the first
+ *   row wins a tie); an event without rows: 0 and -1.  wfs_event_max_bwd: dX [n_cap, D] = dY where arg names the row, else 0. */
+int wfs_graph_kmax(void);
+int wfs_graph_knn_host(const int32_t *coords, int64_t n, int64_t n_valid, int32_t k, int32_t self_loop, int32_t *nbr,
+                       int32_t *deg);
+int wfs_graph_knn(const int32_t *coords, int64_t n_cap, const int64_t *n_dev, int32_t k, int32_t self_loop, int32_t *nbr,
+                  int32_t *deg, int32_t *rev_pos, int32_t *rev_rows, void *stream);
+int wfs_film_message_fwd(const void *P, const int32_t *nbr, const int32_t *deg, int64_t n_cap, int32_t D, void *out,
+                         int32_t dtype, const int64_t *n_dev, void *stream);
+int wfs_film_message_bwd(const void *P, const void *dout, const int32_t *nbr, const int32_t *deg, const int32_t *rev_pos,
+                         const int32_t *rev_rows, int64_t n_cap, int32_t D, void *dP, int32_t dtype, const int64_t *n_dev,
+                         void *stream);
+int wfs_rows_zero_tail(void *X, int64_t n_cap, int32_t C, int32_t dtype, const int64_t *n_dev, void *stream);
+int wfs_event_max_fwd(const int32_t *coords, const void *X, int64_t n_cap, int32_t D, int32_t B, void *Y, int32_t *arg,
+                      int32_t dtype, const int64_t *n_dev, void *stream);
+int wfs_event_max_bwd(const int32_t *coords, const void *dY, const int32_t *arg, int64_t n_cap, int32_t D, int32_t B,
+                      void *dX, int32_t dtype, const int64_t *n_dev, void *stream);
+
 /* opt-in per-kernel timing (HIP events on the launch stream), used by bench.py's roofline ---- */
 #define WFS_TIMER_GATHER_CONV 0
 #define WFS_TIMER_GATHER_DW 1

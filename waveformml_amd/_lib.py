@@ -213,6 +213,14 @@ SIGNATURES = {
                                            _vp, _vp, _sz, _vp]),
     "wfs_predict_scatter": (ctypes.c_int, [_vp, _i64, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i64, _i32,
                                            _i32, _i32, ctypes.c_float, ctypes.c_float, _vp]),
+    "wfs_graph_kmax": (ctypes.c_int, []),
+    "wfs_graph_knn_host": (ctypes.c_int, [_vp, _i64, _i64, _i32, _i32, _vp, _vp]),
+    "wfs_graph_knn": (ctypes.c_int, [_vp, _i64, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "wfs_film_message_fwd": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _vp]),
+    "wfs_film_message_bwd": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _vp]),
+    "wfs_rows_zero_tail": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _vp]),
+    "wfs_event_max_fwd": (ctypes.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _i32, _vp, _vp]),
+    "wfs_event_max_bwd": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _i32, _vp, _vp]),
     "wfs_timing_enable": (ctypes.c_int, [_i32]),
     "wfs_timing_read": (ctypes.c_int, [_i32, ctypes.POINTER(ctypes.c_double), c_i64p]),
 }

@@ -19,7 +19,8 @@ evaluator=module.evaluator)`` fills the tables without a read-back per batch.  T
 parameters with ``evaluation_config`` when the config has one and so loses ``additional_field_names`` (and with them the
 PID classes); here ``evaluation_config`` is merged over them.
 
-Out of scope: the torch_geometric ``Data`` batch form and ``GraphNet`` (the reference config's net), ``write_script``.
+The reference config's net, ``GraphNet.GraphNet``, is psd/graphnet.py (config/segment_quantifier_graph.json).  Out of
+scope: the torch_geometric ``Data`` batch form, ``write_script``.
 """
 import copy
 
