@@ -830,6 +830,42 @@ int wfs_eval_accumulate(int32_t E, int32_t T, int32_t n_classes, const double *a
                         double emax, double psd_min, double psd_max, int64_t *tables, double *sum_wf,
                         double *sum_labelled, int32_t *flags, void *stream);
 
+/* extracted-feature evaluation statistics (csrc/physstats.hip) ---------------------------------------
+ * The per-batch work of the reference's PhysEvaluator.add (src/evaluation/PSDEvaluator.py:319-397) on the device.
+ * Additions only: WFS_ABI_VERSION stays.
+ *
+ * wfs_phys_event_stats (two launches: event offsets, then one wavefront per event): weighted_average_quantities
+ * (src/utils/SparseUtils.py:490-529) over the derived columns energy = f0 * 12, psd = f5, dt = (f1 - 0.5) * 30,
+ * PEL = f2 * 5000, PER = f3 * 5000, z = (f4 - 0.5) * 1200, t0 = f6 * 30, formed in fp32.
+ *   coords      int32 [n_cap, 3] = (x, y, event), rows of an event contiguous, event column non-decreasing in [0, E)
+ *   rows        [n_cap, 7] of `dtype`; only read.  n_dev: valid rows as everywhere (NULL = n_cap)
+ *   offsets     int32 [E + 1] scratch, zero-initialised once by the caller
+ *   outputs     avg_coo double [E, 2]; features float [8, E] = energy, psd, dt, PEL, PER, z, t0, multiplicity;
+ *               multiplicity int32 [E].  Sums run in row order with the reference's accumulator types under numba (energy
+ *               and coordinates fp64, the six weighted quantities fp32, products and sums rounded separately); the
+ *               coordinate sum weighs a row by the RUNNING energy, as the reference does.  An event whose energy sum is
+ *               not > 0 keeps its un-normalised sums, energy 0 and multiplicity 0; one without rows gets zeros.
+ *   flags       int32 [1], STICKY bits: 1 event column unsorted / out of range, 4 (set by wfs_phys_accumulate) prediction
+ *               or label outside [0, n_classes)
+ * wfs_phys_accumulate (one launch): folds the batch into persistent tables.  tables int64 [wfs_phys_table_ints], count
+ *   table then match-sum table each: mult [n_mult + 2], ene_psd [(n_bins + 2)^2], pos [(nx + 2)(ny + 2)]; then
+ *   confusion_energy [n_confusion + 1, C, C] (label-major); then per TRUE class ene_psd_prec [C][2][(n_bins + 2)^2],
+ *   ene_prec [C][2][n_bins + 2], mult_prec [C][2][n_mult + 2].  Bin edges are the reference's.
+ *   spectra     NULL, or int64 [wfs_phys_spectra_ints] = [by truth | by prediction][C][8 features][bins_f + 2] in
+ *               hist_add_1d's convention (underflow first, overflow last); spec_ranges HOST double [8, 2], spec_bins HOST
+ *               int32 [8]. */
+size_t wfs_phys_table_ints(int32_t n_bins, int32_t n_mult, int32_t n_confusion, int32_t nx, int32_t ny,
+                           int32_t n_classes);
+size_t wfs_phys_spectra_ints(int32_t n_classes, const int32_t *spec_bins);
+int wfs_phys_event_stats(const int32_t *coords, const void *rows, int64_t n_cap, int32_t dtype, const int64_t *n_dev,
+                         int32_t E, int32_t *offsets, double *avg_coo, float *features, int32_t *multiplicity,
+                         int32_t *flags, void *stream);
+int wfs_phys_accumulate(int32_t E, int32_t n_classes, const double *avg_coo, const float *features,
+                        const int32_t *multiplicity, const int64_t *predictions, const int64_t *labels, int32_t n_bins,
+                        int32_t n_mult, int32_t n_confusion, int32_t nx, int32_t ny, double emin, double emax,
+                        double psd_min, double psd_max, int64_t *tables, const double *spec_ranges,
+                        const int32_t *spec_bins, int64_t *spectra, int32_t *flags, void *stream);
+
 /* per-segment evaluation tables (csrc/segstats.hip) ---------------------------------------------------
  * The per-batch work of the reference's ZEvaluatorWF.add and EnergyEvaluatorWF.add without a calibration group
  * (src/evaluation/ZEvaluator.py:528-562, EnergyEvaluator.py:132-145) on the device: the row walks z_deviation,

@@ -172,6 +172,11 @@ SIGNATURES = {
     "wfs_eval_accumulate": (ctypes.c_int, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32,
                                            _i32, _i32, _i32, _i32, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                            ctypes.c_double, _vp, _vp, _vp, _vp, _vp]),
+    "wfs_phys_table_ints": (_sz, [_i32, _i32, _i32, _i32, _i32, _i32]),
+    "wfs_phys_spectra_ints": (_sz, [_i32, c_i32p]),
+    "wfs_phys_event_stats": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "wfs_phys_accumulate": (ctypes.c_int, [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _dbl, _dbl,
+                                           _dbl, _dbl, _vp, ctypes.POINTER(_dbl), c_i32p, _vp, _vp, _vp]),
     "wfs_seg_z_table_ints": (_sz, [_i32, _i32, _i32, _i32, _i32, _i32]),
     "wfs_seg_energy_table_ints": (_sz, [_i32, _i32, _i32, _i32]),
     "wfs_seg_z_accumulate": (ctypes.c_int, [_vp, _i64, _vp, _i32] + [_vp, _i32, _i64, _i64, _i32] * 3 +

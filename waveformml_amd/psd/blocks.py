@@ -1,6 +1,6 @@
 """Layer-schedule generators for the PSD net: host-side mirror of the reference's builders
 (src/models/SPConvBlocks.py:411-727 ``SparseConv2DBlock`` versions 0-3, :730-948 ``SparseConv2DPreserve`` versions 0-2,
-src/models/ConvBlocks.py:82-102 ``LinearBlock``, :49-62 ``LinearPlanes``, src/utils/ModelValidation.py:119-177 output-size arithmetic).  Pure
+SPConvBlocks.py:346-386 ``ExtractedFeatureConv``, src/models/ConvBlocks.py:82-102 ``LinearBlock``, :49-62 ``LinearPlanes``, src/utils/ModelValidation.py:119-177 output-size arithmetic).  Pure
 Python arithmetic + constructor calls on whatever module is handed in as ``spconv``; the golden schedules in
 tests/golden/reference_callers.json and tests/golden/block_schedules.json were captured from the reference's own
 generators (tests/golden/make_reference_goldens.py, make_block_goldens.py).
@@ -247,6 +247,62 @@ class SparseConv2DPreserve(nn.Module):
 
     def forward(self, x):
         return self.func(x)
+
+
+def feature_conv_layers(nin, nout, n, size_factor=3, pad_factor=0.0, stride_factor=1, dil_factor=1,
+                        expansion_factor=10.):
+    """[(cin, cout, kernel, stride, padding, dilation)] of an ExtractedFeatureConv (reference SPConvBlocks.py:346-386).
+    The channel list is the reference's, quirks included: nin, round(nin * expansion_factor), THE SAME VALUE AGAIN, then
+    linear steps towards ``nout`` that stop one short of it (the last layer's width is the step before ``nout``).  The
+    kernel never drops below 2; the padding decays from 1 + 1 / (n - 1) times its nominal value at the first layer to 0
+    after the last."""
+    frames = [nin, int(round(nin * expansion_factor))]
+    diff = float(frames[1] - nout) / (n - 1)
+    frames += [int(floor(frames[1] - diff * i)) for i in range(n - 1)]
+    layers = []
+    for i in range(n):
+        decay = 1. - (i - 1) / (n - 1)
+        fs = max(int(floor(size_factor / (i + 1.))), 2)
+        st = max(int(round(stride_factor * i / (n - 1))), 1)
+        dil = int(round(dil_factor ** i))
+        pd = int(round(pad_factor * (fs - 1) * dil_factor * decay))
+        layers.append((frames[i], frames[i + 1], fs, st, pd, dil))
+    return layers
+
+
+class ExtractedFeatureConv(nn.Module):
+    """n x (SparseConv2d -> BatchNorm1d -> ReLU [-> Dropout]) -> ToDense on rows of extracted features: the stack of the
+    reference's ``ExtractedFeatureConvNet`` (src/models/SPConvBlocks.py:346-386), on whatever module is handed in as
+    ``spconv``.  ``n`` must exceed 1 (the schedule divides by n - 1)."""
+
+    def __init__(self, spconv, nin, nout, n, size, expansion_factor=10., size_factor=3, pad_factor=0.0, stride_factor=1,
+                 dil_factor=1, dropout=0, trainable_weights=False):
+        super().__init__()
+        assert (n > 1)
+        self.alg = []
+        self.out_size = list(size)
+        self.dropout = dropout
+        self.ndim = len(size) - 1
+        self.schedule = []
+        for cin, cout, fs, st, pd, dil in feature_conv_layers(nin, nout, n, size_factor, pad_factor, stride_factor,
+                                                              dil_factor, expansion_factor):
+            # the reference passes `trainable_weights` positionally into spconv's `bias` slot (:372)
+            self.alg.append(spconv.SparseConv2d(cin, cout, fs, st, pd, dil, 1, trainable_weights))
+            self.alg.append(nn.BatchNorm1d(cout))
+            self.alg.append(nn.ReLU())
+            if self.dropout:
+                self.alg.append(nn.Dropout(self.dropout))
+            if self.out_size[-1] != cin:
+                raise IOError("Input feature dimension {0} does not match previous output feature dimension {1}."
+                              .format(cin, self.out_size[-1]))
+            self.out_size = conv_output_size(self.out_size, cout, fs, st, pd, dil, self.ndim)
+            self.schedule.append(dict(nin=cin, nout=cout, kernel=fs, stride=st, padding=pd, dilation=dil,
+                                      out_size=list(self.out_size)))
+        self.alg.append(spconv.ToDense())
+        self.network = spconv.SparseSequential(*self.alg)
+
+    def forward(self, x):
+        return self.network(x)
 
 
 class LinearBlock(object):

@@ -9,8 +9,8 @@ What is mirrored: the constructor defaults, the accumulators of ``add`` (``mult_
 ``confusion_energy``, ``confusion_SE``, the summed pulses and their counts) and ``finalize()``; with ``metric_pairs=True``
 also ``MetricPairAggregator``'s per-class tables over the nine metrics of ``_init_results`` (psd/metric_pairs.py, two more
 launches per ``add``; their input is ``self.features``, the ``[9, E]`` feature matrix of the batch).  What is not:
-TensorBoard histograms, plots, ``PhysEvaluator`` and the calibration database -- a caller that has gains passes them as
-an array.
+TensorBoard histograms, plots and the calibration database -- a caller that has gains passes them as an array.
+``PhysEvaluator`` is psd/phys_evaluator.py.
 
 Two things of the reference that matter for comparing numbers:
 

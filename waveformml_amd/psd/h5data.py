@@ -7,8 +7,8 @@ Host-side mirror of the reference's dataset interface for this row (SURVEY.md 8a
                          per-directory event budget (:152-183), ONE item = one file's event range ``[0, n-1]``,
                          ``[[coords, feats], labels]``, labels = directory index unless a ``labels`` dataset / member is
                          named, features scaled by 1/(2^14 - 1) when ``normalize`` (:14-17, :345-346)
-  * ``PulseDataset2D`` / ``PulseDataset3D``   the table / pattern / batch-column bindings of
-                         reference src/datasets/PulseDataset.py:543-625
+  * ``PulseDataset2D`` / ``PulseDataset3D`` / ``PulseDatasetDet``   the table / pattern / batch-column bindings of
+                         reference src/datasets/PulseDataset.py:543-625, :679-719
 
 What differs from the reference, on purpose:
   * rows are read with hyperslab selections of just the item's range and of just the ``coord`` / ``waveform`` members
@@ -360,6 +360,17 @@ class PulseDatasetWaveformNorm(HDF5Dataset):
         if self.label_index is not None:
             return val, label[:, self.label_index]
         return val, label
+
+
+class PulseDatasetDet(HDF5Dataset):
+    """``DetPulseCoord`` tables of ``*DetCoordSim.h5`` files: coord (x, y, evt), pulse float32 [7] = the extracted
+    quantities E / 12, dt / 30 + 0.5, PE0 / 5000, PE1 / 5000, z / 1200 + 0.5, PSD, t offset / 30 of one segment, stored
+    normalised (``normalize=False``) (reference src/datasets/PulseDataset.py:679-719)."""
+    layout = "2d"
+
+    def __init__(self, file_paths, n_per_dir, device=None, normalize=False, **kw):
+        super().__init__(file_paths, "*DetCoordSim.h5", "DetPulseCoord", "coord", "pulse", n_per_dir, device,
+                         normalize=normalize, batch_index=2, **kw)
 
 
 class PulseDataset3D(HDF5Dataset):

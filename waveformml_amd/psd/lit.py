@@ -38,14 +38,25 @@ class LitPSD(nn.Module):
     @property
     def evaluator(self):
         """The reference's ``self.evaluator = PSDEvaluator(system_config.type_names, ...)`` (src/engineering/LitPSD.py:
-        42-48), built on first use on the device the model lives on; ``None`` when the config names no types.  Nothing
-        calls it implicitly: hand it to ``evaluate.test_loop(..., evaluator=module.evaluator)``."""
+        35-46), built on first use on the device the model lives on; ``None`` when the config names no types.  As
+        there, the dataset class picks it: ``PulseDatasetDet`` (the last dotted component of ``dataset_class``) gets
+        ``PhysEvaluator`` with ``evaluation_config`` as keywords, every other class ``PSDEvaluator``.  The reference's
+        third branch, ``PulseDatasetWaveformNorm`` -> ``TensorEvaluator``, is not wired: its ``test_step`` calls
+        ``add(batch, predictions, pred)``, which ``TensorEvaluator.add`` cannot take.  Nothing calls the evaluator
+        implicitly: hand it to ``evaluate.test_loop(..., evaluator=module.evaluator)``."""
         names = getattr(self.config.system_config, "type_names", None)
         if self._evaluator is None and names:
-            from .evaluator import PSDEvaluator
             device = next(self.model.parameters()).device
-            self._evaluator = PSDEvaluator(list(names), device,
-                                           n_samples=getattr(self.config.system_config, "n_samples", 150))
+            dataset_class = str(getattr(self.config.dataset_config, "dataset_class", ""))
+            if dataset_class.split(".")[-1] == "PulseDatasetDet":
+                from .phys_evaluator import PhysEvaluator
+                eval_params = getattr(self.config, "evaluation_config", None)
+                eval_params = DictionaryUtility.to_dict(eval_params) if eval_params is not None else {}
+                self._evaluator = PhysEvaluator(list(names), device, **eval_params)
+            else:
+                from .evaluator import PSDEvaluator
+                self._evaluator = PSDEvaluator(list(names), device,
+                                               n_samples=getattr(self.config.system_config, "n_samples", 150))
         return self._evaluator
 
     def forward(self, x):
