@@ -1121,6 +1121,68 @@ int wfs_zreal_accumulate(const int32_t *coords, int64_t n_cap, const int64_t *n_
                          const int32_t *blind_left, int32_t nx, int32_t ny, int32_t n_mult, int32_t n_z, double zrange,
                          double E_low, double E_high, int32_t n_E, int64_t *tables, int32_t *flags, void *stream);
 
+/* the calibrated z / E baseline (csrc/calibz.hip, csrc/segstats.hip) -------------------------------------
+ * The reference's classical reconstruction calc_calib_z_E (src/utils/SparseUtils.py:938-1026 and its helpers :532-935)
+ * and the `hascal` branches of ZEvaluatorWF.add / z_from_cal (src/evaluation/ZEvaluator.py:502-562) and
+ * EnergyEvaluatorWF.add / calc_deviation_with_z (EnergyEvaluator.py:53-69,132-138) on the device.  Additions only:
+ * WFS_ABI_VERSION stays.  Raw pointers, an explicit stream, n_dev as everywhere, STICKY flags, no read-back.
+ *
+ * wfs_calib_z_E (one launch, one wavefront per row):
+ *   feats       [n_cap, 2 L] of dtype: the left PMT's L samples, then the right PMT's; 2 <= L <= WFS_CALIB_MAX_L
+ *   coords      int32 [n_cap, 3] = (x, y, event); only x and y are used (they choose the segment's curves)
+ *   curves      fp64 on the device, what a Calibrator carries: gain_factor = MAX_RANGE / gains, eres, sampletime
+ *               [nx, ny, 2]; rel_times [nx, ny]; t_interp_curves [nx, ny, 2, WFS_CALIB_T_POINTS, 2]; time_pos_curves
+ *               [nx, ny, WFS_CALIB_TIME_POINTS, 2]; light_pos_curves [nx, ny, WFS_CALIB_LIGHT_POINTS, 2];
+ *               light_sum_curves [nx, ny, WFS_CALIB_SUM_POINTS, 2]; a curve is (x, y) points; a PMT whose t_interp curve has
+ *               abscissa 0 at point 10 has none
+ *   z_cal,E_cal double [n_cap]: z / z_scale + 0.5 and E of the row's segment, 0 where the reference leaves its map alone
+ *   state       int32 [n_cap]: 0 skipped (no peak on either side), 1 one side only (z = 0.5), 2 equal peak counts
+ *               (peak_to_z per pair), 3 unequal counts (match_peaks, peak_to_dt, z_dt_to_z)
+ *   peaks       int32 [n_cap, 2, WFS_CALIB_PEAKS]: per side the peaks that survive cull_peaks in find_peaks' order, -1
+ *               behind them.  A side with all WFS_CALIB_PEAKS slots taken counts as having no peak, as in the reference.
+ *   flags       int32 [1], STICKY: 2 segment outside [nx, ny] (row skipped, state 0), 16 a row with a sample, z or E that
+ *               is not finite (numba raises on the zero divisors): z_cal and E_cal hold the values as they came out (NaN for a
+ *               bad sample) and the accumulate calls below leave the row out of every table.
+ *   fp64 arithmetic on the stored values, rounded products and sums (no fma).  Rows beyond the valid count: zeros, -1.
+ *
+ * wfs_seg_z_accumulate_cal (two launches, as wfs_seg_z_accumulate): per row z_deviation_with_E + z_error twice, the
+ *   prediction plane into the first table set and z_cal into a second set of the same layout behind it (the reference's
+ *   `*_cal` entries): tables int64 [2 * wfs_seg_z_table_ints].  The energy axis of both: float(E * E_scale) of the energy
+ *   plane when one is given, else E_cal unscaled.  target_is_cal != 0 (two more launches, row_scratch float
+ *   [2, n_cap]): the second set scores, in place of z_cal, the map z_from_cal builds -- 0.5 on single-ended segments, the
+ *   target elsewhere, through z_basic_prediction_dense(truth_is_cal = True), i.e. wfs_zreal_baseline on the target's rows.
+ * wfs_seg_energy_accumulate_cal: E_deviation_with_z twice, the prediction plane and float(E_cal), both binned by
+ *   (float(z_cal) - 0.5) * zrange over [-zrange / 2, zrange / 2) in nE bins of zrange / nE (the reference's width) into
+ *   [nE + 2, nz + 2] tables, nz >= nE.  tables int64 [wfs_seg_energy_cal_table_ints]: seg_mult_Emape, E_mult_single,
+ *   E_mult_dual (as wfs_seg_energy_table_ints), E_z_single, E_z_dual pairs, then the same five again for `*_cal`. */
+#define WFS_CALIB_MAX_L 512
+#define WFS_CALIB_PEAKS 5
+#define WFS_CALIB_T_POINTS 50
+#define WFS_CALIB_TIME_POINTS 50
+#define WFS_CALIB_LIGHT_POINTS 51
+#define WFS_CALIB_SUM_POINTS 50
+int wfs_calib_z_E(const void *feats, int32_t dtype, const int32_t *coords, int64_t n_cap, const int64_t *n_dev, int32_t L,
+                  int32_t nx, int32_t ny, const double *gain_factor, const double *eres, const double *rel_times,
+                  const double *sampletime, const double *t_interp_curves, const double *time_pos_curves,
+                  const double *light_pos_curves, const double *light_sum_curves, int32_t sample_width, double z_scale,
+                  double *z_cal, double *E_cal, int32_t *state, int32_t *peaks, int32_t *flags, void *stream);
+int wfs_seg_z_accumulate_cal(const int32_t *coords, int64_t n_cap, const int64_t *n_dev, int32_t B, const void *pred,
+                             int32_t pred_dtype, int64_t pred_bs, int64_t pred_ps, int32_t pred_plane, const void *targ,
+                             int32_t targ_dtype, int64_t targ_bs, int64_t targ_ps, int32_t targ_plane, const void *energy,
+                             int32_t e_dtype, int64_t e_bs, int64_t e_ps, int32_t e_plane, const double *z_cal,
+                             const double *E_cal, int32_t target_is_cal, float *row_scratch, const float *seg_status,
+                             int32_t nx, int32_t ny, const int32_t *sample_segs, int32_t n_sample, int32_t nmult, int32_t nz, double zrange,
+                             int32_t n_err, double err_low, double err_high, double E_low, double E_high, double E_scale,
+                             int32_t *offsets, int64_t *tables, int32_t *flags, void *stream);
+size_t wfs_seg_energy_cal_table_ints(int32_t nx, int32_t ny, int32_t nmult, int32_t nE, int32_t nz);
+int wfs_seg_energy_accumulate_cal(const int32_t *coords, int64_t n_cap, const int64_t *n_dev, int32_t B, const void *pred,
+                                  int32_t pred_dtype, int64_t pred_bs, int64_t pred_ps, int32_t pred_plane,
+                                  const void *targ, int32_t targ_dtype, int64_t targ_bs, int64_t targ_ps,
+                                  int32_t targ_plane, const double *z_cal, const double *E_cal, const float *seg_status,
+                                  int32_t nx, int32_t ny, int32_t nmult, int32_t nE, int32_t nz, double E_low,
+                                  double E_high, double E_scale, double zrange, int32_t *offsets, int64_t *tables,
+                                  int32_t *flags, void *stream);
+
 /* ---- prediction writers (csrc/predwrite.hip; reference src/datasets/PredictionWriter.py swap_values) ----------------
  * A chunk of a table travels as RAW compound records uint8 [N, item_size] (include/wfh5w.h); the two entry points turn
  * them into the net's input and put the net's output back into them, on the device.

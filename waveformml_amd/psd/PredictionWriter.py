@@ -135,7 +135,8 @@ class PredictionWriter(object):
         self.gains = None
         if "calgroup" in kwargs:
             raise NotImplementedError("calgroup=%r needs the calibration database (PROSPECT_CALDB), which this project "
-                                      "does not have: pass gains=<array [14, 11, 2]>" % (kwargs["calgroup"],))
+                                      "does not have: pass gains=<array [14, 11, 2]> (the evaluators take the curves "
+                                      "as calibration=, psd/calibration.py)" % (kwargs["calgroup"],))
         datatype = kwargs.pop("datatype", None)
         if datatype == "PhysPulse":
             raise NotImplementedError("the PhysPulse conversion (convert_values) is left out: DESIGN.md 7")

@@ -37,6 +37,19 @@ def real_evaluator_params(config, params):
     return params
 
 
+def calibration_from_config(config):
+    """``dataset_config.calibration_file``, an ``.npz`` of calibration curves (calibration.py), is this project's
+    counterpart of the reference's ``dataset_config.calgroup`` (LitZ.py:57-58, LitEZ.py:31-32): the curves a Calibrator
+    would read from the calibration database, loaded for the evaluator.  Returns the keyword arguments the evaluator gets:
+    none without a file, else the curves and the waveform length of ``system_config.n_samples`` (the reference hard-codes
+    150 there)."""
+    path = getattr(config.dataset_config, "calibration_file", None)
+    if path is None:
+        return {}
+    from .calibration import CalibrationCurves
+    return {"calibration": CalibrationCurves.load(path), "n_samples": int(config.system_config.n_samples)}
+
+
 class LitSegmentBase(nn.Module):
     """What LitZ and LitEZ share of the reference's LitBase with ``event_predictions=False`` (LitBase.py:13-55)."""
     model_class = None
@@ -166,6 +179,8 @@ class LitZ(LitSegmentBase):
             from .real_z_evaluator import ZEvaluatorRealWFNorm
             return ZEvaluatorRealWFNorm(device, **real_evaluator_params(self.config, params))
         from .segment_evaluator import ZEvaluator
+        for k, v in calibration_from_config(self.config).items():
+            params.setdefault(k, v)
         return ZEvaluator(device, **params)
 
     def test_step(self, batch, batch_idx):
@@ -226,6 +241,8 @@ class LitEZ(LitSegmentBase):
     def _make_evaluator(self, device, params):
         from .segment_evaluator import EZEvaluator
         params.setdefault("E_scale", self.e_adjust)            # the reference passes e_scale=self.e_adjust
+        for k, v in calibration_from_config(self.config).items():
+            params.setdefault(k, v)
         return EZEvaluator(device, **params)
 
     def test_step(self, batch, batch_idx):

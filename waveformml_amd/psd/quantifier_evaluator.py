@@ -71,7 +71,8 @@ class SegEvaluator:
                  bin_overrides=None, target_index=4, error_edges=None, calgroup=None):
         self.device = require_gpu(device, "SegEvaluator")
         if calgroup is not None:
-            raise RuntimeError("SegEvaluator: the calibration database (calgroup) is not mirrored")
+            raise RuntimeError("SegEvaluator: the calibration database (calgroup) is not mirrored; ZEvaluator takes the "
+                               "curves as calibration= (psd/calibration.py)")
         self.nx, self.ny = 14, 11
         setup = metric_setup(e_scale, bin_overrides)
         set_metric_attributes(self, setup)

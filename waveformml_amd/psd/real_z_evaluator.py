@@ -144,7 +144,8 @@ class ZEvaluatorRealWFNorm:
         project's name for it.  ``wf_analysis``: present (whatever its value) switches the waveform analysis on."""
         self.device = require_gpu(device, "ZEvaluatorRealWFNorm")
         if calgroup is not None:
-            raise RuntimeError("ZEvaluatorRealWFNorm: the calibration database (calgroup) is not mirrored")
+            raise RuntimeError("ZEvaluatorRealWFNorm: the calibration database (calgroup) is not mirrored; ZEvaluator takes "
+                               "the curves as calibration= (psd/calibration.py)")
         self.nx, self.ny = 14, 11
         dead_pmts = dead_pmts if excludes is None else tuple(excludes)
         s = z_real_setup(e_scale, bin_overrides)

@@ -1,6 +1,7 @@
 """``ZEvaluator``, ``EnergyEvaluator``, ``EZEvaluator``: the per-batch half of the reference's per-segment evaluators
 (src/evaluation/ZEvaluator.py ``ZEvaluatorBase`` / ``ZEvaluatorWF``, EnergyEvaluator.py ``EnergyEvaluatorWF``,
-EZEvaluator.py ``EZEvaluatorBase``) on the GPU, for the case that needs no calibration database.
+EZEvaluator.py ``EZEvaluatorBase``) on the GPU.  The calibration database itself is not read; a caller that has the
+curves a ``Calibrator`` carries passes them as ``calibration=`` (calibration.py).
 
 The reference's ``add`` copies predictions, targets and coordinates to the host and walks the rows one by one
 (``z_deviation``, ``z_deviation_with_E``, ``z_error``, ``E_deviation``, src/utils/SparseUtils.py).  Here ``add`` is two HIP
@@ -9,9 +10,12 @@ until ``results()``.  Deviation sums are kept as exact fixed-point integers (2^-
 from run to run and N ranks combine them with an integer SUM.
 
 What is mirrored: the constructor defaults, the tables of ``add`` with their keys, shapes and dtypes, and the scalars
-of ``retrieve_error_metrics`` (returned as a dict instead of TensorBoard calls).  The ``*_cal`` entries exist and stay
-zero.  Not mirrored: ``ZEvaluatorPhys``, ``ZEvaluatorRealWFNorm``, ``EZEvaluatorPhys``, everything behind a calibration
-group, plots.
+of ``retrieve_error_metrics`` (returned as a dict instead of TensorBoard calls).  Without a calibration the ``*_cal``
+and ``E_z_*`` entries exist and stay zero.  With one, ``add`` first runs the reference's classical reconstruction
+``calc_calib_z_E`` on the waveform rows ``f`` (csrc/calibz.hip, one wavefront per row, results stay on the device) and
+the accumulate launch scores the prediction and the calibrated value side by side, as the reference's ``hascal`` branches
+do (``ZEvaluatorWF.add`` / ``z_from_cal``, ``EnergyEvaluatorWF.add`` / ``calc_deviation_with_z``).  Not mirrored:
+``ZEvaluatorPhys``, ``EZEvaluatorPhys``, the sqlite reader behind ``calgroup``, plots.
 
 Two things of the reference that matter for comparing numbers:
 
@@ -27,6 +31,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from .calibration import CalibratedReconstruction
 from .eval_common import (FIXED_ONE, check_coords, raise_flags, read_back, require_device_tensors, require_gpu,
                           reserve_offsets, seg_status_tensor)
 from .segments import SE_DEAD_PMTS
@@ -34,7 +39,8 @@ from .segments import SE_DEAD_PMTS
 FLAG_TEXT = {1: "the event column of a batch was not sorted or held an event outside the batch",
              2: "a segment coordinate lay outside the detector grid",
              4: "an energy target was zero (the relative error divides by it)",
-             8: "a deviation was not finite or too large for the fixed-point sums, or a sum overflowed"}
+             8: "a deviation was not finite or too large for the fixed-point sums, or a sum overflowed",
+             16: "a waveform sample or the calibrated z / E of a row was not finite (the reference raises there)"}
 
 
 def z_result_shapes(nmult=6, n_bins=20, n_err_bins=50, n_sample=3, nx=14, ny=11):
@@ -113,7 +119,7 @@ class ZEvaluator(_SegmentTables):
 
     def __init__(self, device, seg_status=None, use_energy=False, nmult=6, n_bins=20, n_err_bins=50, error_low=-1000.,
                  error_high=1000., z_scale=1200., E_low=0.0, E_high=10.0, true_E_high=9.0, E_scale=12.,
-                 sample_segs=((5, 4), (10, 3), (7, 5)), nx=14, ny=11):
+                 sample_segs=((5, 4), (10, 3), (7, 5)), nx=14, ny=11, calibration=None, n_samples=150, sample_width=4):
         self.device = require_gpu(device, "ZEvaluator")
         self.use_energy = bool(use_energy)
         self.nmult, self.n_bins, self.n_err_bins, self.nx, self.ny = int(nmult), int(n_bins), int(n_err_bins), int(nx), int(ny)
@@ -125,10 +131,17 @@ class ZEvaluator(_SegmentTables):
         self._sample_segs = torch.from_numpy(np.ascontiguousarray(self.sample_segs)).to(self.device)
         ns, nm1, nb = len(self.sample_segs), self.nmult + 1, self.n_bins + 2
         n = int(_lib.load().wfs_seg_z_table_ints(self.nx, self.ny, self.nmult, self.n_bins, self.n_err_bins, ns))
-        self._init_tables(n, [("seg_mult_mae", (self.nx, self.ny, nm1), True), ("z_mult_mae_single", (nb, nm1), True),
-                              ("z_mult_mae_dual", (nb, nm1), True), ("E_mult_mae_single", (nb, nm1), True),
-                              ("E_mult_mae_dual", (nb, nm1), True),
-                              ("seg_sample_error", (ns, nm1, self.n_err_bins + 2), False)])
+        layout = [("seg_mult_mae", (self.nx, self.ny, nm1), True), ("z_mult_mae_single", (nb, nm1), True),
+                  ("z_mult_mae_dual", (nb, nm1), True), ("E_mult_mae_single", (nb, nm1), True),
+                  ("E_mult_mae_dual", (nb, nm1), True), ("seg_sample_error", (ns, nm1, self.n_err_bins + 2), False)]
+        self.calibration, self._recon, self._row_scratch = calibration, None, None
+        if calibration is not None:
+            # ZEvaluatorWF with a calibrator: a second table set of the same layout behind the first
+            self._recon = CalibratedReconstruction(self.device, calibration, n_samples, sample_width, self.z_scale,
+                                                   self.nx, self.ny)
+            layout = layout + [(k + "_cal", shape, pair) for k, shape, pair in layout]
+            n *= 2
+        self._init_tables(n, layout)
 
     def set_true_E(self):
         if not self.has_true_E:
@@ -137,20 +150,42 @@ class ZEvaluator(_SegmentTables):
 
     def add(self, predictions, target, c, f, E=None, target_is_cal=False, additional_fields=None, n_valid=None):
         """The reference's signature (ZEvaluatorWF.add): ``predictions`` and ``target`` are dense [B, 1, 14, 11] maps
-        (plane 0 is scored), ``c`` int32 [N, 3] = (x, y, event), ``E`` an optional dense [B, 14, 11] true-energy map;
-        ``f``, ``target_is_cal`` and ``additional_fields`` only matter with a calibration group and are ignored.
+        (plane 0 is scored), ``c`` int32 [N, 3] = (x, y, event), ``E`` an optional dense [B, 14, 11] true-energy map.
+        Without a calibration ``f``, ``target_is_cal`` and ``additional_fields`` are ignored.  With one, ``f`` holds
+        the waveform rows [N, 2 * n_samples] the calibrated z and E are reconstructed from, and ``target_is_cal=True``
+        scores z_from_cal's neighbour-average map (z_basic_prediction_dense) in place of the calibrated z.
         ``n_valid``: device-side row count of a capacity-padded ``c``."""
-        self.add_planes(predictions, 0, target, 0, c, E, 0, n_valid)
+        self.add_planes(predictions, 0, target, 0, c, E, 0, n_valid, f=f, target_is_cal=target_is_cal)
 
-    def add_planes(self, predictions, pred_plane, target, target_plane, c, E=None, E_plane=0, n_valid=None):
+    def add_planes(self, predictions, pred_plane, target, target_plane, c, E=None, E_plane=0, n_valid=None, f=None,
+                   cal=None, target_is_cal=False):
         """``add`` on chosen planes of [B, P, 14, 11] maps, without slicing them.  Launches on the current stream; no
-        read-back, the caller's tensors are only read."""
+        read-back, the caller's tensors are only read.  ``cal``: (z_cal, E_cal) of these rows when the caller has run the
+        reconstruction already (EZEvaluator runs it once for both evaluators)."""
         check_coords(c, n_valid, "ZEvaluator.add")
         B = int(predictions.shape[0])
         if E is not None:
             self.set_true_E()
         pa = _plane_args(predictions, pred_plane, B, self.nx, self.ny, "predictions")
         ta = _plane_args(target, target_plane, B, self.nx, self.ny, "target")
+        if self._recon is not None:
+            # the reference's hascal branch: z_deviation_with_E for the prediction and for the calibrated z, on the true
+            # energy when there is one, else on the calibrated energy
+            zc, Ec = cal if cal is not None else self._recon.run(f, c, self.flags, n_valid)
+            ea = _plane_args(E, E_plane, B, self.nx, self.ny, "E") if E is not None else (None, _lib.WFS_F32, 0, 0, 0)
+            p = _lib.ptr
+            scratch = None
+            if target_is_cal:
+                if self._row_scratch is None or self._row_scratch.shape[1] != c.shape[0]:
+                    self._row_scratch = torch.zeros((2, int(c.shape[0])), dtype=torch.float32, device=self.device)
+                scratch = self._row_scratch
+            _lib.check(_lib.load().wfs_seg_z_accumulate_cal(
+                p(c), int(c.shape[0]), p(n_valid), B, *pa, *ta, *ea, p(zc), p(Ec), 1 if target_is_cal else 0, p(scratch),
+                p(self.seg_status), self.nx, self.ny,
+                p(self._sample_segs), len(self.sample_segs), self.nmult, self.n_bins, self.z_scale, self.n_err_bins,
+                self.error_low, self.error_high, self.E_low, self.E_high, self.E_scale, p(reserve_offsets(self, B)),
+                p(self.tables), p(self.flags), _lib.stream_ptr()))
+            return
         if E is not None and self.use_energy:
             ea = _plane_args(E, E_plane, B, self.nx, self.ny, "E")
         else:
@@ -163,11 +198,12 @@ class ZEvaluator(_SegmentTables):
             p(self.tables), p(self.flags), _lib.stream_ptr()))
 
     def results(self):
-        """One read-back.  The reference's ``results`` dict: (float32 sums, int32 counts) pairs, int32 histograms, the
-        never-filled ``*_cal`` entries as zeros."""
+        """One read-back.  The reference's ``results`` dict: (float32 sums, int32 counts) pairs, int32 histograms; without
+        a calibration the never-filled ``*_cal`` entries as zeros."""
         res = self._read_tables()
-        for k, v in list(res.items()):
-            res[k + "_cal"] = tuple(np.zeros_like(a) for a in v) if isinstance(v, tuple) else np.zeros_like(v)
+        if self._recon is None:
+            for k, v in list(res.items()):
+                res[k + "_cal"] = tuple(np.zeros_like(a) for a in v) if isinstance(v, tuple) else np.zeros_like(v)
         return res
 
     def retrieve_error_metrics(self, results=None):
@@ -179,7 +215,11 @@ class ZEvaluator(_SegmentTables):
             for kind in ("single", "dual"):
                 s, n = res["z_mult_mae_%s" % kind]
                 out["evaluation/%s_mae" % kind] = float(np.sum(s) / np.sum(n) * self.z_scale)
-                out["evaluation/%s_mae_cal" % kind] = 0.0
+                if self._recon is None:
+                    out["evaluation/%s_mae_cal" % kind] = 0.0
+                else:
+                    sc, nc = res["z_mult_mae_%s_cal" % kind]
+                    out["evaluation/%s_mae_cal" % kind] = float(np.sum(sc) / np.sum(nc) * self.z_scale)
                 out["evaluation/%s_mae_mult" % kind] = [float(self.z_scale * np.sum(s[:, i]) / np.sum(n[:, i]))
                                                         for i in range(self.nmult)]
         return out
@@ -188,34 +228,55 @@ class ZEvaluator(_SegmentTables):
 class EnergyEvaluator(_SegmentTables):
     name = "EnergyEvaluator"
 
-    def __init__(self, device, seg_status=None, n_mult=10, n_E=20, E_bounds=(0., 9.), E_scale=12., n_z=20, nx=14, ny=11):
+    def __init__(self, device, seg_status=None, n_mult=10, n_E=20, E_bounds=(0., 9.), E_scale=12., n_z=20, nx=14, ny=11,
+                 calibration=None, z_scale=1200., n_samples=150, sample_width=4):
         self.device = require_gpu(device, "EnergyEvaluator")
         self.n_mult, self.n_E, self.n_z, self.nx, self.ny = int(n_mult), int(n_E), int(n_z), int(nx), int(ny)
         self.E_bounds, self.E_scale = [float(E_bounds[0]), float(E_bounds[1])], float(E_scale)
         self.seg_status = seg_status_tensor(self.device, seg_status, SE_DEAD_PMTS, self.nx, self.ny)
         nm1, nb = self.n_mult + 1, self.n_E + 2
         n = int(_lib.load().wfs_seg_energy_table_ints(self.nx, self.ny, self.n_mult, self.n_E))
-        self._init_tables(n, [("seg_mult_Emape", (self.nx, self.ny, nm1), True), ("E_mult_single", (nb, nm1), True),
-                              ("E_mult_dual", (nb, nm1), True)])
+        layout = [("seg_mult_Emape", (self.nx, self.ny, nm1), True), ("E_mult_single", (nb, nm1), True),
+                  ("E_mult_dual", (nb, nm1), True)]
+        self.calibration, self._recon, self.z_scale = calibration, None, float(z_scale)
+        if calibration is not None:
+            # EnergyEvaluatorWF with a calibrator: the E_z tables, and a second table set for the calibrated energy
+            if self.n_z < self.n_E:
+                raise ValueError("EnergyEvaluator: with a calibration n_z >= n_E (E_deviation_with_z bins z in n_E bins)")
+            self._recon = CalibratedReconstruction(self.device, calibration, n_samples, sample_width, self.z_scale,
+                                                   self.nx, self.ny)
+            layout = layout + [("E_z_single", (nb, self.n_z + 2), True), ("E_z_dual", (nb, self.n_z + 2), True)]
+            layout = layout + [(k + "_cal", shape, pair) for k, shape, pair in layout]
+            n = int(_lib.load().wfs_seg_energy_cal_table_ints(self.nx, self.ny, self.n_mult, self.n_E, self.n_z))
+        self._init_tables(n, layout)
 
     def add(self, predictions, target, c, f, n_valid=None):
-        """The reference's signature (EnergyEvaluatorWF.add): plane 0 of dense [B, 1, 14, 11] maps; ``f`` is ignored."""
-        self.add_planes(predictions, 0, target, 0, c, n_valid)
+        """The reference's signature (EnergyEvaluatorWF.add): plane 0 of dense [B, 1, 14, 11] maps.  ``f`` is ignored
+        without a calibration; with one it holds the waveform rows [N, 2 * n_samples]."""
+        self.add_planes(predictions, 0, target, 0, c, n_valid, f=f)
 
-    def add_planes(self, predictions, pred_plane, target, target_plane, c, n_valid=None):
+    def add_planes(self, predictions, pred_plane, target, target_plane, c, n_valid=None, f=None, cal=None):
         check_coords(c, n_valid, "EnergyEvaluator.add")
         B = int(predictions.shape[0])
         pa = _plane_args(predictions, pred_plane, B, self.nx, self.ny, "predictions")
         ta = _plane_args(target, target_plane, B, self.nx, self.ny, "target")
         p = _lib.ptr
+        if self._recon is not None:
+            # calc_deviation_with_z: the prediction and the calibrated E, both binned by the calibrated z
+            zc, Ec = cal if cal is not None else self._recon.run(f, c, self.flags, n_valid)
+            _lib.check(_lib.load().wfs_seg_energy_accumulate_cal(
+                p(c), int(c.shape[0]), p(n_valid), B, *pa, *ta, p(zc), p(Ec), p(self.seg_status), self.nx, self.ny,
+                self.n_mult, self.n_E, self.n_z, self.E_bounds[0], self.E_bounds[1], self.E_scale, self.z_scale,
+                p(reserve_offsets(self, B)), p(self.tables), p(self.flags), _lib.stream_ptr()))
+            return
         _lib.check(_lib.load().wfs_seg_energy_accumulate(
             p(c), int(c.shape[0]), p(n_valid), B, *pa, *ta, p(self.seg_status), self.nx, self.ny, self.n_mult, self.n_E,
             self.E_bounds[0], self.E_bounds[1], self.E_scale, p(reserve_offsets(self, B)), p(self.tables), p(self.flags),
             _lib.stream_ptr()))
 
     def results(self):
-        """One read-back.  The reference's ``results`` dict; ``*_cal`` and the ``E_z_*`` tables (filled only with a
-        calibration group) are zeros of the reference's shapes."""
+        """One read-back.  The reference's ``results`` dict; without a calibration ``*_cal`` and the ``E_z_*`` tables are
+        zeros of the reference's shapes."""
         res = self._read_tables()
         for k, shape in energy_result_shapes(self.n_mult, self.n_E, self.n_z, self.nx, self.ny).items():
             if k not in res:
@@ -231,6 +292,10 @@ class EnergyEvaluator(_SegmentTables):
                 s, n = res["E_mult_%s" % kind]
                 out["evaluation/%s_E_MAPE" % kind] = [float(100. * np.sum(s[i, :]) / np.sum(n[i, :]))
                                                      for i in range(1, self.n_E + 1)]
+                if self._recon is not None:
+                    s, n = res["E_mult_%s_cal" % kind]
+                    out["evaluation/%s_E_MAPE_cal" % kind] = [float(100. * np.sum(s[i, :]) / np.sum(n[i, :]))
+                                                             for i in range(1, self.n_E + 1)]
         return out
 
 
@@ -242,19 +307,30 @@ class EZEvaluator:
     crosswise; ``planes="lit"`` scores plane 0 as z and plane 1 as energy."""
 
     def __init__(self, device, planes="reference", seg_status=None, use_energy=False, E_scale=12., z_params=None,
-                 energy_params=None):
+                 energy_params=None, calibration=None, n_samples=150, sample_width=4):
         if planes not in ("reference", "lit"):
             raise ValueError("planes must be 'reference' or 'lit', got %r" % (planes,))
         self.device = require_gpu(device, "EZEvaluator")
         self.planes = planes
         self.energy_plane, self.z_plane = (0, 1) if planes == "reference" else (1, 0)
-        self.EnergyEvaluator = EnergyEvaluator(device, seg_status=seg_status, E_scale=E_scale, **(energy_params or {}))
-        self.ZEvaluator = ZEvaluator(device, seg_status=seg_status, use_energy=use_energy, E_scale=E_scale,
+        self.calibration = calibration
+        wf = dict(calibration=calibration, n_samples=n_samples, sample_width=sample_width)
+        self.EnergyEvaluator = EnergyEvaluator(device, seg_status=seg_status, E_scale=E_scale, **wf, **(energy_params or {}))
+        self.ZEvaluator = ZEvaluator(device, seg_status=seg_status, use_energy=use_energy, E_scale=E_scale, **wf,
                                      **(z_params or {}))
+        if calibration is not None:
+            ra, rb = self.EnergyEvaluator._recon, self.ZEvaluator._recon
+            if (ra.n_samples, ra.sample_width, ra.z_scale) != (rb.n_samples, rb.sample_width, rb.z_scale):
+                raise ValueError("EZEvaluator: the two evaluators must agree on n_samples, sample_width and z_scale")
 
     def add(self, predictions, target, c, f, n_valid=None):
-        self.EnergyEvaluator.add_planes(predictions, self.energy_plane, target, self.energy_plane, c, n_valid)
-        self.ZEvaluator.add_planes(predictions, self.z_plane, target, self.z_plane, c, target, self.energy_plane, n_valid)
+        cal = None
+        if self.calibration is not None:
+            # one reconstruction serves both; its flag lands in the energy evaluator's word, which results() reads
+            cal = self.EnergyEvaluator._recon.run(f, c, self.EnergyEvaluator.flags, n_valid)
+        self.EnergyEvaluator.add_planes(predictions, self.energy_plane, target, self.energy_plane, c, n_valid, cal=cal)
+        self.ZEvaluator.add_planes(predictions, self.z_plane, target, self.z_plane, c, target, self.energy_plane, n_valid,
+                                   cal=cal)
 
     def reset(self):
         self.EnergyEvaluator.reset()

@@ -76,7 +76,8 @@ class TensorEvaluator:
                  metric_unit=None, class_names=None, bin_overrides=None):
         self.device = require_gpu(device, "TensorEvaluator")
         if calgroup is not None:
-            raise RuntimeError("TensorEvaluator: calgroup (the PROSPECT_CALDB calibration database) is not supported")
+            raise RuntimeError("TensorEvaluator: calgroup (the PROSPECT_CALDB calibration database) is not supported; the segment "
+                               "evaluators take the curves as calibration= (psd/calibration.py)")
         self.nx, self.ny = 14, 11
         setup = metric_setup(e_scale, target_has_phys, target_index, metric_name, metric_unit, bin_overrides)
         self.E_scale, self.E_adjust, self.z_scale = setup["E_scale"], setup["E_adjust"], Z_NORMALIZATION_FACTOR
