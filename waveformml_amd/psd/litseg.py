@@ -9,9 +9,7 @@ per batch.  The torch_geometric ``Data`` batch form, the torchmetrics objects an
 """
 import torch
 
-from .config import DictionaryUtility
 from .lit import LitPSD
-from .segments import SE_DEAD_PMTS, segment_status, single_ended_mask
 
 
 class LitSegClassifier(LitPSD):
@@ -19,43 +17,16 @@ class LitSegClassifier(LitPSD):
 
     def __init__(self, config, trial=None):
         super().__init__(config, trial)
-        self.softmax = torch.nn.Softmax(dim=1)
-        self.SE_only = bool(getattr(config.net_config, "SELoss", False))
-        if self.SE_only:
-            dead = getattr(config.net_config, "SE_dead_pmts", SE_DEAD_PMTS)
-            self.register_buffer("SE_mask", single_ended_mask(segment_status(dead)))
-        self.last_test_outputs = None     # test_step's (pred, target, c, additional_fields), for segment_test_loop
-        self._evaluator = None
+        self.softmax = torch.nn.Softmax(dim=1)          # LitPSD's is a LogSoftmax
 
-    @property
-    def evaluator(self):
-        """The ``PIDEvaluator`` the reference builds in ``__init__`` (LitSegClassifier.py:26-33), built on first use on
-        the device the model lives on: ``additional_field_names`` from ``dataset_config.test_dataset_params
-        .additional_fields``, then ``config.evaluation_config`` as keyword arguments (``excludes``, the reference's name
-        for the dead PMTs, included).  Nothing calls it implicitly: hand it to ``evaluate.segment_test_loop``."""
-        if self._evaluator is None:
-            from .pid_evaluator import PIDEvaluator
-            params = {}
-            test_params = getattr(getattr(self.config, "dataset_config", None), "test_dataset_params", None)
-            if hasattr(test_params, "additional_fields"):
-                params["additional_field_names"] = list(test_params.additional_fields)
-            if hasattr(self.config, "evaluation_config"):
-                params.update(DictionaryUtility.to_dict(self.config.evaluation_config))
-            if "excludes" in params:
-                params["dead_pmts"] = params.pop("excludes")
-            self._evaluator = PIDEvaluator(next(self.model.parameters()).device, **params)
-        return self._evaluator
+    def _make_evaluator(self, device):
+        """The ``PIDEvaluator`` the reference builds in ``__init__`` (LitSegClassifier.py:26-33)."""
+        from .pid_evaluator import PIDEvaluator
+        return PIDEvaluator(device, **self._segment_evaluator_params())
 
     # reference LitSegClassifier._process_batch, :36-63
     def _process_batch(self, batch):
-        inputs, target = batch
-        c, f = inputs[0], inputs[1]
-        n_valid = inputs[2] if len(inputs) > 2 else None       # capacity-padded batch of a captured step (psd/graph.py)
-        additional_fields = None
-        if isinstance(f, list):
-            additional_fields, f = f[1:], f[0]
-        if self.occlude_index:
-            f[:, self.occlude_index] = 0
+        c, f, additional_fields, n_valid, target = self._inputs(batch)
         predictions = self.model([c, f, n_valid] if n_valid is not None else [c, f])
         logits = predictions if predictions.dtype == torch.float32 else predictions.float()
         if self.SE_only:

@@ -26,9 +26,7 @@ import copy
 
 import torch
 
-from .config import DictionaryUtility
-from .lit import LitPSD
-from .segments import SE_DEAD_PMTS, segment_status, single_ended_mask
+from .litbase import LitBase
 
 
 def masked_regression_composition(criterion_none, predictions, scored, counted):
@@ -44,7 +42,7 @@ def masked_regression_composition(criterion_none, predictions, scored, counted):
     return loss, mse.detach()
 
 
-class LitSegQuantifier(LitPSD):
+class LitSegQuantifier(LitBase):
     per_row_targets = True            # one target row per active segment: psd/graph.GraphedTrainStep pads them per row
     # Trainer.validate: the captured eval runner (psd/evaluate) scores logits as a classifier; this module validates
     # through its own validation_step
@@ -52,38 +50,19 @@ class LitSegQuantifier(LitPSD):
 
     def __init__(self, config, trial=None):
         if not hasattr(config.system_config, "n_type"):
-            config.system_config.n_type = 1           # one number per segment
+            config.system_config.n_type = 1           # one number per segment: the nets read it (net.py, graphnet.py)
         super().__init__(config, trial)
-        self.SE_only = bool(getattr(config.net_config, "SELoss", False))
-        if self.SE_only:
-            dead = getattr(config.net_config, "SE_dead_pmts", SE_DEAD_PMTS)
-            self.register_buffer("SE_mask", single_ended_mask(segment_status(dead)))
         self.target_index = config.dataset_config.dataset_params.label_index
         self.criterion_none = copy.deepcopy(self.criterion)
         self.criterion_none.reduction = "none"
-        self.last_test_outputs = None     # test_step's (predictions, target, c, additional_fields), for segment_test_loop
-        self._evaluator = None
 
-    @property
-    def evaluator(self):
-        """The ``SegEvaluator`` the reference builds in ``__init__`` (LitSegQuantifier.py:16-28), built on first use on
-        the device the model lives on: ``additional_field_names`` from ``dataset_config.test_dataset_params
-        .additional_fields``, ``config.evaluation_config`` merged over it (``excludes``, the reference's name for the
-        dead PMTs, included), then ``target_index``.  Nothing calls it implicitly: hand it to
-        ``evaluate.segment_test_loop``."""
-        if self._evaluator is None:
-            from .quantifier_evaluator import SegEvaluator
-            params = {}
-            test_params = getattr(getattr(self.config, "dataset_config", None), "test_dataset_params", None)
-            if hasattr(test_params, "additional_fields"):
-                params["additional_field_names"] = list(test_params.additional_fields)
-            if hasattr(self.config, "evaluation_config"):
-                params.update(DictionaryUtility.to_dict(self.config.evaluation_config))
-            if "excludes" in params:
-                params["dead_pmts"] = params.pop("excludes")
-            params["target_index"] = self.target_index
-            self._evaluator = SegEvaluator(next(self.model.parameters()).device, **params)
-        return self._evaluator
+    def _make_evaluator(self, device):
+        """The ``SegEvaluator`` the reference builds in ``__init__`` (LitSegQuantifier.py:16-28): the per-row evaluators'
+        keywords, then ``target_index``."""
+        from .quantifier_evaluator import SegEvaluator
+        params = self._segment_evaluator_params()
+        params["target_index"] = self.target_index
+        return SegEvaluator(device, **params)
 
     def _loss(self, predictions, target, c, n_valid=None):
         """(loss, mse) over the counted rows: below ``n_valid`` and, with ``SELoss``, on a single-ended segment."""
@@ -107,14 +86,7 @@ class LitSegQuantifier(LitPSD):
 
     # reference LitSegQuantifier._process_batch
     def _process_batch(self, batch):
-        inputs, target = batch
-        c, f = inputs[0], inputs[1]
-        n_valid = inputs[2] if len(inputs) > 2 else None       # capacity-padded batch of a captured step (psd/graph.py)
-        additional_fields = None
-        if isinstance(f, list):
-            additional_fields, f = f[1:], f[0]
-        if self.occlude_index:                       # falsy for index 0, exactly as the reference
-            f[:, self.occlude_index] = 0
+        c, f, additional_fields, n_valid, target = self._inputs(batch)
         predictions = self.model([c, f, n_valid] if n_valid is not None else [c, f]).squeeze(1)
         loss, mse = self._loss(predictions, target, c, n_valid)
         return loss, predictions, target, c, f, additional_fields, mse

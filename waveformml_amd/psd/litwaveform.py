@@ -1,7 +1,7 @@
 """``LitWaveform``: host-side mirror of the reference's per-pulse module (src/engineering/LitWaveform.py on
 src/engineering/LitBase.py:13-55): one waveform row per PMT pulse, one target per ROW, a mean-reduced criterion
-(``L1Loss``, ``MSELoss`` or ``CrossEntropyLoss``).  As psd/lit.LitPSD, a plain ``nn.Module`` with Lightning's step
-methods; ``configure_optimizers`` is LitPSD's, so FlatSGD / FlatAdam / FlatAdamW take over a flat GPU parameter.
+(``L1Loss``, ``MSELoss`` or ``CrossEntropyLoss``), on psd/litbase.LitBase: ``configure_optimizers`` is the shared one, so
+FlatSGD / FlatAdam / FlatAdamW take over a flat GPU parameter.
 
 ``use_detector_number`` appends the pulse's detector position to its row (n_samples += 3, fill_coords), for the
 308-PMT detector only.  (The reference's error message for another count reads a misspelt attribute and raises
@@ -22,57 +22,37 @@ evaluator=module.evaluator)`` fills the per-PMT and the binned loss tables witho
 
 Out of scope: ``write_script`` / TorchScript export.
 """
-import logging
-
 import torch
 from torch import nn
 
-from .config import DictionaryUtility, ModuleUtility
-from .lit import LitPSD
+from .litbase import LitBase, evaluation_params, test_has_phys
 
 
-class LitWaveform(nn.Module):
+class LitWaveform(LitBase):
     per_row_targets = True            # one target per pulse (row): the captured step pads them per row
     # Trainer.validate: the captured eval runner (psd/evaluate) scores logits as a classifier; this module validates
     # through its own validation_step (L1 / MSE have no accuracy: val_acc is NaN)
     captured_validation = False
 
     def __init__(self, config, trial=None):
-        super().__init__()
         nc = config.net_config
-        self.use_detector_number = False
-        if hasattr(nc, "use_detector_number"):
-            self.use_detector_number = nc.use_detector_number
-            if self.use_detector_number:
-                if not hasattr(nc, "num_detectors"):
-                    raise IOError("net config must contain 'num_detectors' property if 'use_detector_number' set to true")
-                config.system_config.n_samples = config.system_config.n_samples + 3
-                self.nx, self.ny = 14, 11
-                if nc.num_detectors == 308:
-                    self.detector_num_factor_x = 1. / (self.nx - 1)
-                    self.detector_num_factor_y = 1. / (self.ny - 1)
-                else:
-                    raise IOError("num detectors " + str(nc.num_detectors) + " not supported")
-        # LitBase (event_predictions=True)
-        self.trial = trial
-        self.pylog = logging.getLogger(__name__)
-        self.config = config
-        self.lr = config.optimize_config.lr
-        self.modules_util = ModuleUtility(nc.imports + config.dataset_config.imports + config.optimize_config.imports)
-        self.model = self.modules_util.retrieve_class(nc.net_class)(config)
-        self.criterion_class = self.modules_util.retrieve_class(nc.criterion_class)
-        self.criterion = self.criterion_class(*nc.criterion_params, reduction="mean")
+        use_detector_number = getattr(nc, "use_detector_number", False)
+        if use_detector_number:
+            # before the net is built: it reads n_samples
+            if not hasattr(nc, "num_detectors"):
+                raise IOError("net config must contain 'num_detectors' property if 'use_detector_number' set to true")
+            config.system_config.n_samples = config.system_config.n_samples + 3
+            if nc.num_detectors != 308:
+                raise IOError("num detectors " + str(nc.num_detectors) + " not supported")
+        super().__init__(config, trial)
+        self.use_detector_number = use_detector_number
+        if use_detector_number:
+            self.detector_num_factor_x = 1. / (self.nx - 1)
+            self.detector_num_factor_y = 1. / (self.ny - 1)
         self.write_script = False
-        self.occlude_index = getattr(config.dataset_config, "occlude_index", None)
-        self.optimizer_parameters = None
-        self.logged = {}
-        # LitWaveform
         self.squeeze_index = 2 if nc.net_class.endswith("RecurrentWaveformNet") else 1
         dc = config.dataset_config
-        self.test_has_phys = False
-        if hasattr(dc, "test_dataset_params"):
-            if dc.test_dataset_params.label_name == "phys" and not hasattr(dc.test_dataset_params, "label_index"):
-                self.test_has_phys = True
+        self.test_has_phys = test_has_phys(config)
         self.target_index = dc.dataset_params.label_index if hasattr(dc.dataset_params, "label_index") else None
         self.use_accuracy = False
         if nc.criterion_class == "L1Loss":
@@ -87,32 +67,16 @@ class LitWaveform(nn.Module):
         self.loss_no_reduce = self.criterion_class(*nc.criterion_params, reduction="none")
         if self.use_accuracy:
             self.softmax = nn.Softmax(dim=1)
-        self.last_test_outputs = None     # test_step's (c, f, target, results), for segment_test_loop
-        self._evaluator = None
 
-    @property
-    def evaluator(self):
-        """The ``TensorEvaluator`` the reference builds in ``__init__`` (LitWaveform.py:39-63), built on first use on the
-        device the model lives on (it raises on the CPU): ``calgroup`` from ``dataset_config``, ``target_has_phys``,
-        ``target_index`` and ``metric_name`` as the constructor derives them, then ``config.evaluation_config`` as
-        keyword arguments.  Nothing calls it implicitly: hand it to ``evaluate.segment_test_loop``."""
-        if self._evaluator is None:
-            from .tensor_evaluator import TensorEvaluator
-            params = {}
-            if hasattr(self.config, "evaluation_config"):
-                params = DictionaryUtility.to_dict(self.config.evaluation_config)
-            self._evaluator = TensorEvaluator(next(self.model.parameters()).device,
-                                              calgroup=getattr(self.config.dataset_config, "calgroup", None),
-                                              target_has_phys=self.test_has_phys, target_index=self.target_index,
-                                              metric_name=self.metric_name, **params)
-        return self._evaluator
-
-    configure_optimizers = LitPSD.configure_optimizers
-    log = LitPSD.log
-    log_dict = LitPSD.log_dict
-
-    def forward(self, x):
-        return self.model(x)
+    def _make_evaluator(self, device):
+        """The ``TensorEvaluator`` the reference builds in ``__init__`` (LitWaveform.py:39-63; it raises on the CPU):
+        ``calgroup`` from ``dataset_config``, ``target_has_phys``, ``target_index`` and ``metric_name`` as the
+        constructor derives them, then ``config.evaluation_config`` as keyword arguments (one that repeats a name of
+        the four raises TypeError)."""
+        from .tensor_evaluator import TensorEvaluator
+        return TensorEvaluator(device, calgroup=getattr(self.config.dataset_config, "calgroup", None),
+                               target_has_phys=self.test_has_phys, target_index=self.target_index,
+                               metric_name=self.metric_name, **evaluation_params(self.config))
 
     def fill_coords(self, coords, det):
         """Detector number -> (x, y, end) of the pulse (reference LitWaveform.fill_coords): segment det // 2 on the
@@ -147,13 +111,9 @@ class LitWaveform(nn.Module):
         return predictions
 
     def _loss(self, predictions, target, n_valid=None):
-        if predictions.is_cuda:
-            from ..spconv import functional as Fsp
-            if Fsp.can_fuse_cross_entropy(self.criterion, predictions, target):
-                # one HIP launch (LitPSD._loss); the padding rows of a captured batch hold ignore_index (psd/graph.py)
-                return Fsp.cross_entropy_mean(predictions, target, self.criterion.ignore_index)
-        if n_valid is None:
-            return self.criterion.forward(predictions, target)
+        # the fused cross-entropy takes a padded batch too: its padding rows hold ignore_index (psd/graph.py)
+        if n_valid is None or self._fuses_cross_entropy(predictions, target):
+            return super()._loss(predictions, target)
         # a capacity-padded batch: the mean over the first n_valid rows, with no host read-back of the count
         per = self.loss_no_reduce(predictions, target)
         valid = torch.arange(per.shape[0], device=per.device) < n_valid.reshape(())
@@ -161,11 +121,6 @@ class LitWaveform(nn.Module):
             valid = valid.reshape((-1,) + (1,) * (per.dim() - 1))
         count = n_valid.reshape(()).to(per.dtype) * (per[0].numel() if per.dim() > 1 else 1)
         return torch.where(valid, per, torch.zeros_like(per)).sum() / count
-
-    @staticmethod
-    def _unpack(batch):
-        inputs, target = batch
-        return inputs[0], inputs[1], (inputs[2] if len(inputs) > 2 else None), target
 
     def training_step(self, batch, batch_idx):
         c, f, n_valid, target = self._unpack(batch)

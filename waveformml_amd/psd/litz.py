@@ -4,36 +4,24 @@ predicts a dense [B, out, 14, 11] map, the loss compares it with the targets of 
 and the dense target come from ``SparseConvTensor(...).dense()`` (wfs_to_dense) -- with a sum-reduced criterion divided by
 the number of rows (``net_config.SELoss``: of the single-ended segments only, psd/segments.py).
 
-As psd/lit.LitPSD these are plain ``nn.Module``s with Lightning's step methods (Lightning is not installable offline).
-The evaluators the reference's ``test_step`` feeds (ZEvaluatorWF, EZEvaluatorWF without a calibration group) are
+Both sit on psd/litbase.LitBase through ``LitSegmentBase``.  The evaluators the reference's ``test_step`` feeds (ZEvaluatorWF, EZEvaluatorWF without a calibration group) are
 psd/segment_evaluator.py, and for ``LitZ`` with phys test targets (``test_has_phys``) psd/real_z_evaluator.py; ``test_step`` leaves what it would hand them in ``last_test_outputs`` and
 psd/evaluate.segment_test_loop does the hand-over.  Their plots and the calibration-database variants are out of scope.
 """
-import logging
-
 import torch
-from torch import nn
 
-from .config import DictionaryUtility, ModuleUtility
+from .litbase import LitBase, additional_field_names, evaluation_params, test_has_phys
 from .pid_evaluator import Z_INDEX
-from .segments import SE_DEAD_PMTS, segment_status, single_ended_mask
 from .znet import SingleEndedEZConv, SingleEndedZConv
 
 
-def test_has_phys(config):
-    """The reference's ``LitZ.test_has_phys`` (LitZ.py:34-37): the test dataset's label is the whole ``"phys"`` row,
-    without a ``label_index`` that picks one column of it."""
-    params = getattr(config.dataset_config, "test_dataset_params", None)
-    return params is not None and getattr(params, "label_name", None) == "phys" and not hasattr(params, "label_index")
-
-
 def real_evaluator_params(config, params):
-    """``evaluation_config`` as keyword arguments with ``test_dataset_params.additional_fields`` merged under it as
-    ``additional_field_names`` (LitZ.py:43-48)."""
+    """``evaluation_config`` as keyword arguments with ``test_dataset_params.additional_fields`` written over it as
+    ``additional_field_names`` (LitZ.py:43-48); no ``excludes`` rename here."""
     params = dict(params)
-    test_params = getattr(config.dataset_config, "test_dataset_params", None)
-    if test_params is not None and hasattr(test_params, "additional_fields"):
-        params["additional_field_names"] = list(test_params.additional_fields)
+    names = additional_field_names(config)
+    if names is not None:
+        params["additional_field_names"] = names
     return params
 
 
@@ -50,71 +38,26 @@ def calibration_from_config(config):
     return {"calibration": CalibrationCurves.load(path), "n_samples": int(config.system_config.n_samples)}
 
 
-class LitSegmentBase(nn.Module):
-    """What LitZ and LitEZ share of the reference's LitBase with ``event_predictions=False`` (LitBase.py:13-55)."""
-    model_class = None
+class LitSegmentBase(LitBase):
+    """What LitZ and LitEZ share: LitBase with ``event_predictions=False`` (a sum-reduced criterion) and the segment loss.
+    Their evaluators (LitZ.py:43-60, LitEZ.py:24-35, the case without a calibration group) get
+    ``config.evaluation_config`` as keyword arguments."""
+    # the optimizer steps model.parameters() even after Trainer.fit has set optimizer_parameters: a gap kept on purpose
+    # (DESIGN.md, "A preserved gap")
+    flat_optimizer = False
 
     def __init__(self, config, trial=None):
-        super().__init__()
-        self.trial = trial
-        self.pylog = logging.getLogger(__name__)
-        self.config = config
-        self.nx, self.ny = 14, 11
-        self.lr = config.optimize_config.lr
-        self.modules_util = ModuleUtility(config.net_config.imports + config.dataset_config.imports +
-                                          config.optimize_config.imports)
-        self.model = type(self).model_class(config)
-        criterion_class = self.modules_util.retrieve_class(config.net_config.criterion_class)
-        self.criterion = criterion_class(*config.net_config.criterion_params, reduction="sum")   # event_predictions=False
-        self.occlude_index = getattr(config.dataset_config, "occlude_index", None)
-        self.SE_only = bool(getattr(config.net_config, "SELoss", False))
-        if self.SE_only:
-            # the reference takes the table from its SingleEndedEvaluator; `net_config.SE_dead_pmts` replaces the default
-            dead = getattr(config.net_config, "SE_dead_pmts", SE_DEAD_PMTS)
-            self.register_buffer("SE_mask", single_ended_mask(segment_status(dead, self.nx, self.ny)))
+        super().__init__(config, trial, event_predictions=False)
         if hasattr(config.net_config, "UseFFT"):
             raise NotImplementedError("UseFFT feeds complex features; not on the mirrored path")
-        self.logged = {}
-        self.last_test_outputs = None         # test_step's (predictions, target_tensor, c, f), for segment_test_loop
-        self._evaluator = None
 
-    def _make_evaluator(self, device, params):
-        raise NotImplementedError
-
-    @property
-    def evaluator(self):
-        """The evaluator the reference builds in ``__init__`` (LitZ.py:43-60, LitEZ.py:24-35) for the case without a
-        calibration group, built on first use on the device the model lives on, with ``config.evaluation_config`` as
-        keyword arguments.  Nothing calls it implicitly: hand it to ``evaluate.segment_test_loop(..., evaluator=...)``."""
-        if self._evaluator is None:
-            params = {}
-            if hasattr(self.config, "evaluation_config"):
-                params = DictionaryUtility.to_dict(self.config.evaluation_config)
-            self._evaluator = self._make_evaluator(next(self.model.parameters()).device, params)
-        return self._evaluator
-
-    def forward(self, x):
-        return self.model(x)
-
-    def log(self, name, value, **kwargs):
-        self.logged[name] = value.detach() if torch.is_tensor(value) else value
-
-    def log_dict(self, d, **kwargs):
-        for k, v in d.items():
-            self.log(k, v)
-
-    def configure_optimizers(self):
-        oc = self.config.optimize_config
-        optimizer = self.modules_util.retrieve_class(oc.optimizer_class)(
-            self.model.parameters(), lr=self.lr, **DictionaryUtility.to_dict(oc.optimizer_params))
-        if getattr(oc, "scheduler_class", None):
-            if not hasattr(oc, "scheduler_params"):
-                raise IOError("Optimizer config has a learning scheduler class specified. You must also set "
-                              "lr_schedule_parameters (dictionary of key value pairs).")
-            scheduler = self.modules_util.retrieve_class(oc.scheduler_class)(
-                optimizer, **DictionaryUtility.to_dict(oc.scheduler_params))
-            return [optimizer], [scheduler]
-        return optimizer
+    @staticmethod
+    def _unpack(batch):
+        c, f, n_valid, target = LitBase._unpack(batch)
+        if n_valid is not None:
+            raise ValueError("LitZ / LitEZ do not take a capacity-padded batch (a valid-row count as third element of "
+                             "the inner list): the segment loss reads the batch size back from the host")
+        return c, f, None, target
 
     # reference LitBase._calc_segment_loss, :124-174
     def _calc_segment_loss(self, coo, predictions, target, use_float=True, target_index=None, sparse_mask=None):
@@ -154,12 +97,7 @@ class LitZ(LitSegmentBase):
 
     # reference LitZ._process_batch, :89-108
     def _process_batch(self, batch, target_index=None):
-        (c, f), target = batch
-        additional_fields = None
-        if isinstance(f, list):
-            additional_fields, f = f[1:], f[0]
-        if self.occlude_index:
-            f[:, self.occlude_index] = 0
+        c, f, additional_fields, _, target = self._inputs(batch)
         predictions = self.model([c, f])
         loss, target_tensor, predictions, _ = self._calc_segment_loss(c, predictions, target, target_index=target_index)
         return loss, predictions, target_tensor, c, f, additional_fields
@@ -174,7 +112,8 @@ class LitZ(LitSegmentBase):
         self.log("val_loss", loss, on_epoch=True, prog_bar=True, logger=True)
         return loss
 
-    def _make_evaluator(self, device, params):
+    def _make_evaluator(self, device):
+        params = evaluation_params(self.config)
         if self.test_has_phys:
             from .real_z_evaluator import ZEvaluatorRealWFNorm
             return ZEvaluatorRealWFNorm(device, **real_evaluator_params(self.config, params))
@@ -211,7 +150,7 @@ class LitEZ(LitSegmentBase):
         self.phys_coord = nc.algorithm == "features"
 
     def _process_batch(self, batch):
-        (c, f), target = batch
+        c, f, _, target = self._unpack(batch)
         if self.phys_coord and self.e_factor != 1.:
             f[:, 0] *= self.e_factor
             f[:, 2] *= self.e_factor
@@ -238,8 +177,9 @@ class LitEZ(LitSegmentBase):
         self.log_dict(results, on_epoch=True, prog_bar=True, logger=True)
         return results
 
-    def _make_evaluator(self, device, params):
+    def _make_evaluator(self, device):
         from .segment_evaluator import EZEvaluator
+        params = evaluation_params(self.config)
         params.setdefault("E_scale", self.e_adjust)            # the reference passes e_scale=self.e_adjust
         for k, v in calibration_from_config(self.config).items():
             params.setdefault(k, v)
