@@ -411,6 +411,18 @@ int wfs_bn_relu_bwd(const void *X, const void *dY, int64_t N, int32_t C, const f
                     void *workspace, size_t workspace_bytes, int32_t dtype, const int64_t *n_dev,
                     void *stream);
 
+/* Which kernel family wfs_bn_relu_fwd (backward == 0) or wfs_bn_relu_bwd (backward != 0) runs for N rows of C channels
+ * of `dtype`; host only, nothing is launched (the tests use it to know what a case covers).  Returns
+ *   0  column-block kernels (wide layers with few rows)
+ *   1  register-resident kernels; *rows_per_thread = rows a thread holds (2, 4, 8 or 16)
+ *   2  loop kernels, four channels per thread        3  loop kernels, one channel per thread
+ *   4  channel slices of at most 1024 channels
+ *   -WFS_EINVAL (negative: 1 is taken) for a channel count, dtype or N < 0 that the entry points refuse.
+ * *partials = the number of per-block partial sums the elementwise pass folds (0: none, the eval forward); both pointers
+ * may be NULL, *rows_per_thread is 0 outside family 1.  Additions only: WFS_ABI_VERSION stays. */
+int wfs_bn_plan(int64_t N, int32_t C, int32_t dtype, int32_t training, int32_t backward, int32_t *rows_per_thread,
+                int32_t *partials);
+
 /* After wfs_rulebook_emit of a regular conv whose site table was a direct grid: pointers into `workspace` to the
  * cell -> output row map of the build (ticket[cell] != 0xFFFFFFFF <=> the output cell b * out_volume + pos is active,
  * slot_id[cell] = its row).  Returns 1 and sets the pointers, or 0 when this build has no such map.  The map lives as

@@ -99,6 +99,7 @@ SIGNATURES = {
                                        _i32, _vp, _vp, _vp, _vp, _sz, _i32, _vp, _vp]),
     "wfs_bn_relu_bwd": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _sz,
                                        _i32, _vp, _vp]),
+    "wfs_bn_plan": (ctypes.c_int, [_i64, _i32, _i32, _i32, _i32, c_i32p, c_i32p]),
     "wfs_rulebook_cell_map": (ctypes.c_int, [ctypes.POINTER(Geometry), _i64, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp),
                                              c_i64p]),
     "wfs_to_dense_mapped": (ctypes.c_int, [_vp, _vp, _vp, _i64, _vp, _i32, _i64, _i32, _vp, _i32, _vp]),

@@ -890,7 +890,50 @@ extern "C" size_t wfs_bn_workspace_bytes(int64_t N, int32_t C) {
     return (nb + 1) * 2 * C * sizeof(float);
 }
 
-// C channels starting at X / Y (row stride ld elements): one slice of a wide layer, or the whole layer (ld == C)
+// The arm a call of wfs_bn_relu_fwd (backward == 0) or wfs_bn_relu_bwd takes, decided as the two entry points and
+// bn_fwd_slice / bn_bwd_slice decide it and with the same helpers; nothing is launched.  MUST change together with
+// them: tests/test_bn_cases_host.py takes from here which kernels a case of its table runs.
+//   0 column-block   1 register-resident (*rows_per_thread = PER)   2 loop kernels, VEC = 4   3 loop kernels, VEC = 1
+//   4 channel slices (whole-row arm of each slice not reported)      -WFS_EINVAL: arguments the entry points refuse
+//   (negative, 1 being taken; also for N < 0, which the entry points leave unchecked)
+// *partials = the number of partials the elementwise pass folds (0: it folds none, the eval forward).  N == 0 launches
+// nothing; the arm reported is the one whose checks the call passes through.
+extern "C" int wfs_bn_plan(int64_t N, int32_t C, int32_t dtype, int32_t training, int32_t backward,
+                           int32_t *rows_per_thread, int32_t *partials) {
+    int per = 0;
+    long long np = 0;
+    int arm;
+    const bool sums = training || backward;            // a reduce launch precedes the elementwise pass
+    if (!wfs_dtype_ok(dtype) || N < 0) {
+        arm = -WFS_EINVAL;
+    } else if (bw_ok(N, C) && N > 0) {
+        arm = 0;
+        np = sums ? bw_chunks(N) : 0;
+    } else if (C <= (C % 4 == 0 ? MAXC : TB)) {        // bn_fwd_slice / bn_bwd_slice with ld == C
+        const bool vec4 = C % 4 == 0;
+        if (!(C >= 1 && C <= MAXC && (vec4 ? C / 4 : C) <= TB)) {
+            arm = -WFS_EINVAL;
+        } else {
+            long long rb = 0;
+            if (N > 0 && sums) per = rr_plan(N, C, backward && dtype == WFS_F32 ? 8 : 16, &rb);
+            if (per) {
+                arm = 1;
+                np = rb;
+            } else {
+                arm = vec4 ? 2 : 3;
+                np = N > 0 && sums ? bn_reduce_blocks(N, C) : 0;
+            }
+        }
+    } else {
+        arm = 4;
+    }
+    if (rows_per_thread) *rows_per_thread = per;
+    if (partials) *partials = (int32_t)np;
+    return arm;
+}
+
+// C channels starting at X / Y (row stride ld elements): one slice of a wide layer, or the whole layer (ld == C).
+// The choice of kernels below is restated by wfs_bn_plan: change the two together.
 static int bn_fwd_slice(const void *X, int64_t N, int32_t C, long long ld, const float *gamma, const float *beta,
                         float *running_mean, float *running_var, int64_t *num_batches_tracked, float momentum,
                         float eps, int32_t training, int32_t relu, void *Y, float *save_mean, float *save_invstd,
@@ -981,6 +1024,7 @@ extern "C" int wfs_bn_relu_fwd(const void *X, int64_t N, int32_t C, const float 
     return WFS_OK;
 }
 
+// The choice of kernels below is restated by wfs_bn_plan: change the two together.
 static int bn_bwd_slice(const void *X, const void *dY, int64_t N, int32_t C, long long ld, const float *gamma,
                         const float *beta, const float *save_mean, const float *save_invstd, int32_t training,
                         int32_t relu, void *dX, float *dgamma, float *dbeta, void *workspace, size_t workspace_bytes,
