@@ -801,6 +801,49 @@ int wfs_load_batch(const int32_t *coords, int64_t n, int32_t cols, const int32_t
                    const int64_t *labels, int64_t *labels_dst, int64_t B, int64_t *n_valid_dst,
                    int32_t *event_offsets, int32_t events, void *stream);
 
+/* filter images -----------------------------------------------------------------------------------------
+ * The 32 -> 32 kernels for 16-bit rows (wfs_gather_conv, wfs_conv_backward) start every block by converting the layer's
+ * fp32 filter into a 16-bit LDS image.  A caller whose filters change once per step can have that image made once per
+ * step and hand it to those calls, whose blocks then copy it into LDS as it is.  Additions only: WFS_ABI_VERSION stays.
+ *
+ * An image of W [K, 32, 32] fp32 (K <= 32) for the row type `dtype` (WFS_BF16 / WFS_F16) is K * 128 fragments of 16 bytes
+ * (wfs_filter_image_bytes: K * 2048 bytes; 16-byte aligned):
+ *     img[k][s][h][col][j] = dtype(B[16h + 8s + j][col]),   s, h in {0, 1}, col in [0, 32), j in [0, 8),
+ * with B = W[k] in the forward image (wfs_gather_conv with transpose_w == 0) and B = W[k]^T in the dX image
+ * (transpose_w != 0, wfs_conv_backward), rounded as the kernels round (to nearest even).
+ *
+ * wfs_conv_filter_images: one launch that fills the images of one filter; either image may be NULL.
+ * wfs_load_batch_images: wfs_load_batch with up to WFS_FILTER_IMAGE_JOBS_MAX image jobs in the same launch (the
+ *   hand-over is the head of every captured step and reads the filters as the previous step's optimizer left them).
+ *   The copy part is wfs_load_batch's, unchanged; njobs == 0 is wfs_load_batch.
+ * wfs_gather_conv_image / wfs_conv_backward_image: wfs_gather_conv / wfs_conv_backward with the image of the orientation
+ *   the call contracts with (forward image for transpose_w == 0, dX image otherwise); NULL = the plain entry.  The
+ *   image is read only by the 32 -> 32 kernels for 16-bit rows and K <= 27; every other route ignores it.  The image
+ *   must hold W's current values: the results are then bit-identical to the plain entry's. */
+#define WFS_FILTER_IMAGE_JOBS_MAX 16
+typedef struct wfs_filter_image_job {
+    const float *W;       /* [K, 32, 32] fp32 */
+    void *img_fwd;        /* K * 2048 bytes or NULL */
+    void *img_t;          /* K * 2048 bytes or NULL */
+    int32_t K;
+    int32_t dtype;
+} wfs_filter_image_job;
+size_t wfs_filter_image_bytes(int32_t K);
+int wfs_conv_filter_images(const float *W, int32_t K, int32_t dtype, void *img_fwd, void *img_t, void *stream);
+int wfs_load_batch_images(const int32_t *coords, int64_t n, int32_t cols, const int32_t *perm_host, int32_t *coords_dst,
+                          int32_t *indices_dst, const void *feats, void *feats_dst, int64_t feat_bytes,
+                          const int64_t *labels, int64_t *labels_dst, int64_t B, int64_t *n_valid_dst,
+                          int32_t *event_offsets, int32_t events, const wfs_filter_image_job *jobs, int32_t njobs,
+                          void *stream);
+int wfs_gather_conv_image(const int32_t *table, const int32_t *kmap_host, int32_t K, int32_t identity_k,
+                          int64_t R, const void *X, int64_t X_rows, int32_t Cx, const float *W,
+                          int32_t Cw_in, int32_t Cw_out, int32_t transpose_w, const float *bias, void *Y,
+                          int32_t dtype, const int64_t *r_dev, int32_t packed_kl, const void *image, void *stream);
+int wfs_conv_backward_image(const int32_t *table, int32_t K, int32_t identity_k, int64_t R, const void *X, const void *dY,
+                            int64_t dY_rows, int32_t Cin, int32_t Cout, const float *W, void *dX, float *dW, int32_t dtype,
+                            void *workspace, size_t workspace_bytes, const int64_t *r_dev, wfs_dw_job *defer,
+                            int32_t packed_kl, const void *image_t, void *stream);
+
 /* evaluation statistics (csrc/evalstats.hip) ----------------------------------------------------------
  * The per-batch work of the reference's PSDEvaluator.add (src/evaluation/PSDEvaluator.py:101-198) on the device.  These
  * entry points are additions: no existing signature or struct changes, so WFS_ABI_VERSION stays.

@@ -61,6 +61,27 @@ by1 = N * 32 * ES + M1 * 32 * ES + P1 * 8 + 27 * 4096
 timeit("conv s4 fwd 32->32", lambda: Fsp.gather_conv(rb1.nbr_in, None, 27, -1, M1, X, W, False, None), by1)
 timeit("conv s4 dX", lambda: Fsp.gather_conv(rb1.nbr_out, None, 27, -1, N, dY1, W, True, None), by1)
 timeit("conv s4 dW", lambda: Fsp.gather_dw(rb1.nbr_out, 27, -1, N, X, dY1, False), by1)
+if DT != torch.float32:
+    # the one-launch backward (k_bwd32_bf16: dW blocks + dX blocks); its dX blocks run the forward kernels' body
+    timeit("subm bwd 32->32 (dW+dX)", lambda: Fsp.conv_backward(rb.nbr_out, 27, rb.centre_k, N, X, dY, W))
+    timeit("conv s4 bwd (dW+dX)", lambda: Fsp.conv_backward(rb1.nbr_out, 27, -1, N, X, dY1, W))
+    # the same launches handed the filter's 16-bit LDS images (include/wfsparse.h "filter images"); a library without
+    # them (an older build selected with WFS_LIB) skips these lines
+    from waveformml_amd import _lib
+    lib = _lib.load()
+    if hasattr(lib, "wfs_conv_filter_images"):
+        img_f = torch.zeros(27 * 2048, dtype=torch.uint8, device=dev)
+        img_t = torch.zeros_like(img_f)
+        _lib.check(lib.wfs_conv_filter_images(_lib.ptr(W), 27, _lib.dtype_code(X), _lib.ptr(img_f), _lib.ptr(img_t),
+                                              _lib.stream_ptr()))
+        timeit("img subm fwd 32->32", lambda: Fsp.gather_conv(t, km, 27, rb.centre_k, N, X, W, False, None, image=img_f), by)
+        timeit("img subm dX 32->32", lambda: Fsp.gather_conv(rb.nbr_out, None, 27, rb.centre_k, N, dY, W, True, None, image=img_t), by)
+        timeit("img conv s4 fwd 32->32", lambda: Fsp.gather_conv(rb1.nbr_in, None, 27, -1, M1, X, W, False, None, image=img_f), by1)
+        timeit("img conv s4 dX", lambda: Fsp.gather_conv(rb1.nbr_out, None, 27, -1, N, dY1, W, True, None, image=img_t), by1)
+        timeit("img subm bwd 32->32 (dW+dX)", lambda: Fsp.conv_backward(rb.nbr_out, 27, rb.centre_k, N, X, dY, W, image_t=img_t))
+        timeit("img conv s4 bwd (dW+dX)", lambda: Fsp.conv_backward(rb1.nbr_out, 27, -1, N, X, dY1, W, image_t=img_t))
+        timeit("filter images (both, one launch)", lambda: _lib.check(lib.wfs_conv_filter_images(
+            _lib.ptr(W), 27, _lib.dtype_code(X), _lib.ptr(img_f), _lib.ptr(img_t), _lib.stream_ptr())))
 timeit("subm fwd 2->32", lambda: Fsp.gather_conv(t, km, 27, rb.centre_k, N, X2, W2, False, None), N * 136 + P * 8)
 timeit("subm dW 32x2 (dY stationary)", lambda: Fsp.gather_dw(t, 27, rb.centre_k, N, dY, X2, True, km), N * 34 * ES + P * 8)
 nv = torch.tensor([N], dtype=torch.int64, device=dev)

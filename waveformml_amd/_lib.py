@@ -43,6 +43,13 @@ class DwJob(ctypes.Structure):
                 ("transpose", _i32), ("dW", _vp)]
 
 
+class FilterImageJob(ctypes.Structure):
+    """struct wfs_filter_image_job"""
+    _fields_ = [("W", _vp), ("img_fwd", _vp), ("img_t", _vp), ("K", _i32), ("dtype", _i32)]
+
+
+FILTER_IMAGE_JOBS_MAX = 16      # WFS_FILTER_IMAGE_JOBS_MAX
+
 # name -> (restype, argtypes); mirrors include/wfsparse.h one to one
 SIGNATURES = {
     "wfs_abi_version": (ctypes.c_int, []),
@@ -167,6 +174,14 @@ SIGNATURES = {
     "wfs_adam_step": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "wfs_load_batch": (ctypes.c_int, [_vp, _i64, _i32, c_i32p, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i32,
                                       _vp]),
+    "wfs_filter_image_bytes": (_sz, [_i32]),
+    "wfs_conv_filter_images": (ctypes.c_int, [_vp, _i32, _i32, _vp, _vp, _vp]),
+    "wfs_load_batch_images": (ctypes.c_int, [_vp, _i64, _i32, c_i32p, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp,
+                                             _i32, ctypes.POINTER(FilterImageJob), _i32, _vp]),
+    "wfs_gather_conv_image": (ctypes.c_int, [_vp, c_i32p, _i32, _i32, _i64, _vp, _i64, _i32, _vp, _i32, _i32, _i32,
+                                             _vp, _vp, _i32, _vp, _i32, _vp, _vp]),
+    "wfs_conv_backward_image": (ctypes.c_int, [_vp, _i32, _i32, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _i32, _vp,
+                                               _sz, _vp, ctypes.POINTER(DwJob), _i32, _vp, _vp]),
     "wfs_eval_table_ints": (_sz, [_i32, _i32, _i32, _i32, _i32, _i32, _i32]),
     "wfs_event_pulse_stats": (ctypes.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp,
                                              _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

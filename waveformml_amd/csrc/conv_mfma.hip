@@ -452,14 +452,30 @@ __device__ __forceinline__ void gconv32_bf16_body(unsigned char *smem, int vbid,
                                                   long long R, const long long *__restrict__ r_dev,
                                                   const H *__restrict__ X, const float *__restrict__ W,
                                                   const float *__restrict__ bias, H *__restrict__ Y, long long ntiles,
-                                                  long long tiles_per_xcd) {
+                                                  long long tiles_per_xcd, const uint4 *__restrict__ img) {
     uint4 *sWb = reinterpret_cast<uint4 *>(smem);                           // K * 128 fragments of 16 B
     int *sNb = reinterpret_cast<int *>(smem + (size_t)K * 2048);            // [waves][K][32]
     // filter staging, WSB fragments per thread at a time: all their loads are issued (unconditionally, clamped)
     // before the first conversion, so a block pays one memory round trip per batch instead of one per fragment
     constexpr int WSB = 5;
     const int nfrag = K * 128;
-    if (!(WFS_KNOCK & 1))
+    // With an image (include/wfsparse.h "filter images": this LDS image itself, made once per step) nothing is converted
+    // and half the bytes are read: one 16-byte load and one LDS store per fragment, the barrier where it is.  (The image
+    // is lane-linear and was also copied by LDS DMA, with the barrier moved behind the first tile's table reads: 6.5 us
+    // per step against this form's 10.3, profiles/filter_images_ab.txt.)
+    if (!(WFS_KNOCK & 1) && img != nullptr) {
+        for (int u0 = threadIdx.x; u0 < nfrag; u0 += nthreads * WSB) {
+            uint4 f[WSB];
+#pragma unroll
+            for (int b = 0; b < WSB; ++b) {
+                const int u = u0 + b * nthreads;
+                f[b] = img[u < nfrag ? u : nfrag - 1];
+            }
+#pragma unroll
+            for (int b = 0; b < WSB; ++b)
+                if (u0 + b * nthreads < nfrag) sWb[u0 + b * nthreads] = f[b];
+        }
+    } else if (!(WFS_KNOCK & 1))
     for (int u0 = threadIdx.x; u0 < nfrag; u0 += nthreads * WSB) {
         float w[WSB][8];
 #pragma unroll
@@ -609,10 +625,10 @@ __global__ void __launch_bounds__(1024) k_gconv32_bf16(const int *__restrict__ t
                                                        const H *__restrict__ X,
                                                        const float *__restrict__ W, const float *__restrict__ bias,
                                                        H *__restrict__ Y, long long ntiles,
-                                                       long long tiles_per_xcd) {
+                                                       long long tiles_per_xcd, const uint4 *__restrict__ img) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     gconv32_bf16_body<H, TRANSPOSE_W, PK>(smem, (int)blockIdx.x, (int)gridDim.x, (int)blockDim.x, table, mirror, K,
-                                          identity_k, R, r_dev, X, W, bias, Y, ntiles, tiles_per_xcd);
+                                          identity_k, R, r_dev, X, W, bias, Y, ntiles, tiles_per_xcd, img);
 }
 
 // ------------------------------------------------------------------------------------------ 2 -> 32
@@ -1263,7 +1279,8 @@ __global__ void __launch_bounds__(1024) k_bwd32_bf16(const int *__restrict__ tab
                                                      const long long *__restrict__ r_dev, const H *__restrict__ S,
                                                      const H *__restrict__ G, const float *__restrict__ W,
                                                      H *__restrict__ dX, float *__restrict__ part, int ngroups,
-                                                     int nbx_dw, int n_dw_pad, int n_dx, int dx_threads) {
+                                                     int nbx_dw, int n_dw_pad, int n_dx, int dx_threads,
+                                                     const uint4 *__restrict__ img_t) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int bid = (int)blockIdx.x;
     if (bid < n_dw_pad) {
@@ -1273,7 +1290,7 @@ __global__ void __launch_bounds__(1024) k_bwd32_bf16(const int *__restrict__ tab
     } else {
         if ((int)threadIdx.x >= dx_threads) return;          // the dX body was tuned for fewer waves per block
         gconv32_bf16_body<H, true, PK>(smem, bid - n_dw_pad, n_dx, dx_threads, table, 0, K, identity_k, Rcap, r_dev, G, W,
-                                       nullptr, dX, 0, 0);
+                                       nullptr, dX, 0, 0, img_t);
     }
 }
 
@@ -1846,7 +1863,7 @@ int wfs_launch_gconv32_f32(const int *table, int mirror, int K, int identity_k, 
 template <typename H>
 static int launch_gconv32_h16(const int *table, int mirror, int K, int identity_k, long long R, const long long *r_dev,
                               const H *Xb, const float *W, int transpose_w, const float *bias, H *Yb,
-                              hipStream_t stream, int packed_kl) {
+                              hipStream_t stream, int packed_kl, const uint4 *img) {
     long long ntiles, nblk, tiles_per_xcd;
     int wpb;
     gconv32_grid(R, r_dev != nullptr, &ntiles, &wpb, &nblk, &tiles_per_xcd, 16);
@@ -1858,23 +1875,23 @@ static int launch_gconv32_h16(const int *table, int mirror, int K, int identity_
     if (packed_kl) {
         static bool attr_p = false;
         return launch_big_lds(k_gconv32_bf16<H, true, 3>, &attr_p, grid, block, lds, stream, table, mirror, K, identity_k, R,
-                              r_dev, Xb, W, bias, Yb, ntiles, tiles_per_xcd);
+                              r_dev, Xb, W, bias, Yb, ntiles, tiles_per_xcd, img);
     }
     if (transpose_w)
         return launch_big_lds(k_gconv32_bf16<H, true>, &attr[0], grid, block, lds, stream, table, mirror, K, identity_k, R,
-                              r_dev, Xb, W, bias, Yb, ntiles, tiles_per_xcd);
+                              r_dev, Xb, W, bias, Yb, ntiles, tiles_per_xcd, img);
     return launch_big_lds(k_gconv32_bf16<H, false>, &attr[1], grid, block, lds, stream, table, mirror, K, identity_k, R,
-                          r_dev, Xb, W, bias, Yb, ntiles, tiles_per_xcd);
+                          r_dev, Xb, W, bias, Yb, ntiles, tiles_per_xcd, img);
 }
 
 int wfs_launch_gconv32_h16(const int *table, int mirror, int K, int identity_k, long long R, const long long *r_dev,
                            const void *X, const float *W, int transpose_w, const float *bias, void *Y, int dtype,
-                           hipStream_t stream, int packed_kl) {
+                           hipStream_t stream, int packed_kl, const void *image) {
     if (dtype == WFS_F16)
         return launch_gconv32_h16<wfs_f16>(table, mirror, K, identity_k, R, r_dev, (const wfs_f16 *)X, W, transpose_w,
-                                           bias, (wfs_f16 *)Y, stream, packed_kl);
+                                           bias, (wfs_f16 *)Y, stream, packed_kl, (const uint4 *)image);
     return launch_gconv32_h16<wfs_bf16>(table, mirror, K, identity_k, R, r_dev, (const wfs_bf16 *)X, W, transpose_w, bias,
-                                        (wfs_bf16 *)Y, stream, packed_kl);
+                                        (wfs_bf16 *)Y, stream, packed_kl, (const uint4 *)image);
 }
 
 // 2 -> 32
@@ -1991,7 +2008,8 @@ int wfs_launch_gdw32(const int *table, int K, int identity_k, long long R, const
 // dW and dX of a 32 -> 32 layer with 16-bit rows in one launch (k_bwd32_bf16)
 template <typename H>
 static int launch_bwd32_h16(const int *table, int packed_kl, int K, int identity_k, long long R, const long long *r_dev,
-                            const H *S, const H *G, const float *W, H *dX, float *part, hipStream_t stream) {
+                            const H *S, const H *G, const float *W, H *dX, float *part, hipStream_t stream,
+                            const uint4 *img_t) {
     const long long nbx_dw = dw32_blocks(R, false);
     const int ngroups = (K + DWB_KG - 1) / DWB_KG;
     const long long n_dw = nbx_dw * ngroups, n_dw_pad = (n_dw + 7) / 8 * 8;
@@ -2004,11 +2022,11 @@ static int launch_bwd32_h16(const int *table, int packed_kl, int K, int identity
     if (packed_kl) {
         static bool attr = false;
         return launch_big_lds(k_bwd32_bf16<H, 3>, &attr, grid, block, lds, stream, table, K, identity_k, R, r_dev, S, G, W, dX,
-                              part, ngroups, (int)nbx_dw, (int)n_dw_pad, (int)n_dx, wpb * 64);
+                              part, ngroups, (int)nbx_dw, (int)n_dw_pad, (int)n_dx, wpb * 64, img_t);
     }
     static bool attr0 = false;
     return launch_big_lds(k_bwd32_bf16<H, 0>, &attr0, grid, block, lds, stream, table, K, identity_k, R, r_dev, S, G, W, dX,
-                          part, ngroups, (int)nbx_dw, (int)n_dw_pad, (int)n_dx, wpb * 64);
+                          part, ngroups, (int)nbx_dw, (int)n_dw_pad, (int)n_dx, wpb * 64, img_t);
 }
 
 // 16-bit rows and three-piece fp32 rows.  The fp32-INSTRUCTION kernels were measured too (same construction: 0.828 vs
@@ -2055,17 +2073,17 @@ static int launch_bwd32_split(const int *table, int packed_kl, int K, int identi
 
 int wfs_launch_bwd32_h16(const int *table, int packed_kl, int K, int identity_k, long long R, const long long *r_dev,
                          const void *S, const void *G, const float *W, void *dX, int swap, float *dW, float *part, int dtype,
-                         wfs_dw_job *defer, hipStream_t stream) {
+                         wfs_dw_job *defer, hipStream_t stream, const void *image_t) {
     int rc;
     if (dtype == WFS_F32)
         rc = launch_bwd32_split(table, packed_kl, K, identity_k, R, r_dev, (const float *)S, (const float *)G, W, (float *)dX,
                                 part, stream);
     else if (dtype == WFS_F16)
         rc = launch_bwd32_h16<wfs_f16>(table, packed_kl, K, identity_k, R, r_dev, (const wfs_f16 *)S, (const wfs_f16 *)G, W,
-                                       (wfs_f16 *)dX, part, stream);
+                                       (wfs_f16 *)dX, part, stream, (const uint4 *)image_t);
     else
         rc = launch_bwd32_h16<wfs_bf16>(table, packed_kl, K, identity_k, R, r_dev, (const wfs_bf16 *)S, (const wfs_bf16 *)G,
-                                        W, (wfs_bf16 *)dX, part, stream);
+                                        W, (wfs_bf16 *)dX, part, stream, (const uint4 *)image_t);
     if (rc != WFS_OK) return rc;
     return dw_reduce_or_defer(part, dw32_blocks(R, false), (long long)K * 1024, K, 32, 32, swap, dW, defer, stream);
 }

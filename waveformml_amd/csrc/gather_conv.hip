@@ -402,8 +402,9 @@ long long dw_chunks_mfma(long long R, int K, int Cs, int Cg) {
 static int gather_conv_impl(const int32_t *table, const int32_t *kmap_host, int32_t K, int32_t identity_k,
                             int64_t R, const void *X, int64_t X_rows, int32_t Cx, const float *W, int32_t Cw_in,
                             int32_t Cw_out, int32_t transpose_w, const float *bias, void *Y, int32_t dtype,
-                            const int64_t *r_dev_, void *stream_, int packed_kl = 0) {
+                            const int64_t *r_dev_, void *stream_, int packed_kl = 0, const void *image = nullptr) {
     hipStream_t stream = (hipStream_t)stream_;
+    WFS_REQUIRE(((uintptr_t)image & 15) == 0, WFS_EINVAL, "the filter image must be 16-byte aligned");
     WFS_REQUIRE(packed_kl == 0 || wfs_gather_packed_ok(packed_kl, K, Cx, transpose_w ? Cw_in : Cw_out, dtype, transpose_w ? 1 : 2),
                 WFS_EINVAL, "a packed table (kl %d) is not taken by this product (wfs_gather_packed_ok): expand it with "
                 "wfs_unpack_table", packed_kl);
@@ -433,7 +434,7 @@ static int gather_conv_impl(const int32_t *table, const int32_t *kmap_host, int3
     }
     if (dtype != WFS_F32 && Cx == 32 && Cy == 32 && K <= 27 && table && kind != WFS_KMAP_OTHER && X_rows < (1ll << 25)) {
         return wfs_launch_gconv32_h16(table, mirror, K, identity_k, R, r_dev, X, W, transpose_w, bias, Y, dtype, stream,
-                                      packed_kl);
+                                      packed_kl, image);
     }
     WFS_REQUIRE(packed_kl == 0, WFS_EINVAL, "a packed table reached a kernel that reads dense ones");
     if (Cx == 2 && Cy == 32 && !transpose_w && table)
@@ -473,6 +474,16 @@ extern "C" int wfs_gather_conv(const int32_t *table, const int32_t *kmap_host, i
     WFS_REQUIRE(packed_kl == 0 || !kmap_host, WFS_EINVAL, "a packed table takes no column map");
     return gather_conv_impl(table, kmap_host, K, identity_k, R, X, X_rows, Cx, W, Cw_in, Cw_out, transpose_w, bias, Y,
                             dtype, r_dev, stream, packed_kl);
+}
+
+// wfs_gather_conv with the filter's image of this call's orientation (include/wfsparse.h "filter images")
+extern "C" int wfs_gather_conv_image(const int32_t *table, const int32_t *kmap_host, int32_t K, int32_t identity_k,
+                                     int64_t R, const void *X, int64_t X_rows, int32_t Cx, const float *W, int32_t Cw_in,
+                                     int32_t Cw_out, int32_t transpose_w, const float *bias, void *Y, int32_t dtype,
+                                     const int64_t *r_dev, int32_t packed_kl, const void *image, void *stream) {
+    WFS_REQUIRE(packed_kl == 0 || !kmap_host, WFS_EINVAL, "a packed table takes no column map");
+    return gather_conv_impl(table, kmap_host, K, identity_k, R, X, X_rows, Cx, W, Cw_in, Cw_out, transpose_w, bias, Y,
+                            dtype, r_dev, stream, packed_kl, image);
 }
 
 // which = 1: wfs_gather_conv with transpose_w (dX), 2: wfs_gather_conv forward, 3: wfs_gather_dw
@@ -600,7 +611,18 @@ extern "C" int wfs_conv_backward(const int32_t *table, int32_t K, int32_t identi
                                  const void *dY, int64_t dY_rows, int32_t Cin, int32_t Cout, const float *W, void *dX,
                                  float *dW, int32_t dtype, void *workspace, size_t workspace_bytes, const int64_t *r_dev,
                                  wfs_dw_job *defer, int32_t packed_kl, void *stream_) {
+    return wfs_conv_backward_image(table, K, identity_k, R, X, dY, dY_rows, Cin, Cout, W, dX, dW, dtype, workspace,
+                                   workspace_bytes, r_dev, defer, packed_kl, nullptr, stream_);
+}
+
+// ... with the filter's dX image (include/wfsparse.h "filter images"); NULL = wfs_conv_backward
+extern "C" int wfs_conv_backward_image(const int32_t *table, int32_t K, int32_t identity_k, int64_t R, const void *X,
+                                       const void *dY, int64_t dY_rows, int32_t Cin, int32_t Cout, const float *W,
+                                       void *dX, float *dW, int32_t dtype, void *workspace, size_t workspace_bytes,
+                                       const int64_t *r_dev, wfs_dw_job *defer, int32_t packed_kl, const void *image_t,
+                                       void *stream_) {
     hipStream_t stream = (hipStream_t)stream_;
+    WFS_REQUIRE(((uintptr_t)image_t & 15) == 0, WFS_EINVAL, "the filter image must be 16-byte aligned");
     WFS_REQUIRE(dX && dW, WFS_EINVAL, "wfs_conv_backward computes both gradients (use wfs_gather_conv / wfs_gather_dw for one)");
     const long long row_lim = dtype == WFS_F32 ? (1ll << 24) : (1ll << 25);       // 32-bit byte offsets of the gathers
     const bool fused = Cin == 32 && Cout == 32 && table && wfs_bwd32_fused_ok(K, packed_kl, dtype) && R > 0 &&
@@ -610,7 +632,7 @@ extern "C" int wfs_conv_backward(const int32_t *table, int32_t K, int32_t identi
                                 workspace_bytes, r_dev, defer, stream_, packed_kl);
         if (rc != WFS_OK) return rc;
         return gather_conv_impl(table, nullptr, K, identity_k, R, dY, dY_rows, Cout, W, Cin, Cout, 1, nullptr, dX, dtype, r_dev,
-                                stream_, packed_kl);
+                                stream_, packed_kl, image_t);
     }
     WFS_REQUIRE(X && dY && W && workspace, WFS_EINVAL, "NULL device pointer");
     const size_t need = wfs_gather_dw_workspace_bytes(K, R, Cin, Cout);
@@ -618,7 +640,7 @@ extern "C" int wfs_conv_backward(const int32_t *table, int32_t K, int32_t identi
     if (defer) *defer = wfs_dw_job_none();
     WfsTimerScope timer(WFS_TIMER_CONV_BACKWARD, stream);
     return wfs_launch_bwd32_h16(table, packed_kl, K, identity_k, R, (const long long *)r_dev, X, dY, W, dX, 0, dW,
-                                (float *)workspace, dtype, defer, stream);
+                                (float *)workspace, dtype, defer, stream, image_t);
 }
 
 static size_t first_bn_slab_bytes(int32_t K, int64_t R) {

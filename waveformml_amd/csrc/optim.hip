@@ -10,6 +10,7 @@
 //     g = nesterov ? g + momentum * buf : buf
 //     p -= lr * g
 #include "wfs_common.h"
+#include "wfs_filterimg.h"
 
 namespace {
 
@@ -207,8 +208,17 @@ __global__ void __launch_bounds__(256) k_load_batch(const int *__restrict__ coor
                                                     unsigned char *__restrict__ feats_tail_dst, int tail_bytes,
                                                     const long long *__restrict__ labels, long long *__restrict__ labels_dst,
                                                     long long B, long long *__restrict__ n_valid_dst,
-                                                    int *__restrict__ ev_off, int ev_B, int ev_col) {
-    const long long tid = (long long)blockIdx.x * 256 + threadIdx.x, nth = (long long)gridDim.x * 256;
+                                                    int *__restrict__ ev_off, int ev_B, int ev_col, int copy_blocks,
+                                                    WfsFilterImageJobs images) {
+    // blocks past the copy's own count fill filter images (wfs_load_batch_images); the copy keeps its tid / nth
+    if ((int)blockIdx.x >= copy_blocks) {
+        const int b = (int)blockIdx.x - copy_blocks;
+        for (int i = 0; i < images.n; ++i)
+            if (b >= images.first_block[i] && b < images.first_block[i + 1])
+                wfs_filter_images_block(images.j[i], b - images.first_block[i]);
+        return;
+    }
+    const long long tid = (long long)blockIdx.x * 256 + threadIdx.x, nth = (long long)copy_blocks * 256;
     if (tid == 0 && n_valid_dst) *n_valid_dst = n;
     // event offsets of the batch (evrulebook.hip k_event_offsets, same words, same flags): the first WFS_EVENT_FLAG_WORDS
     // blocks walk the batch column of the SOURCE rows -- the captured step then starts with the rulebook build itself
@@ -255,13 +265,58 @@ __global__ void __launch_bounds__(256) k_load_batch(const int *__restrict__ coor
     for (long long i = tid; i < B; i += nth) labels_dst[i] = labels[i];
 }
 
+__global__ void __launch_bounds__(256) k_filter_images(wfs_filter_image_job job) {
+    wfs_filter_images_block(job, (int)blockIdx.x);
+}
+
+int filter_image_job_ok(const wfs_filter_image_job &j) {
+    WFS_REQUIRE(j.K >= 1 && j.K <= 32, WFS_EINVAL, "filter image of K = %d (1 .. 32)", j.K);
+    WFS_REQUIRE(j.dtype == WFS_BF16 || j.dtype == WFS_F16, WFS_EINVAL, "filter images are 16-bit (dtype %d)", j.dtype);
+    // (the filter may sit anywhere in a flat parameter buffer: 4-byte alignment, as the conv kernels read it)
+    WFS_REQUIRE(j.W && ((uintptr_t)j.W & 3) == 0, WFS_EINVAL, "NULL or misaligned filter");
+    WFS_REQUIRE((((uintptr_t)j.img_fwd | (uintptr_t)j.img_t) & 15) == 0, WFS_EINVAL, "images must be 16-byte aligned");
+    return WFS_OK;
+}
+
 }  // namespace
+
+extern "C" size_t wfs_filter_image_bytes(int32_t K) { return K > 0 ? (size_t)K * 2048 : 0; }
+
+extern "C" int wfs_conv_filter_images(const float *W, int32_t K, int32_t dtype, void *img_fwd, void *img_t,
+                                      void *stream_) {
+    const wfs_filter_image_job job{W, img_fwd, img_t, K, dtype};
+    const int rc = filter_image_job_ok(job);
+    if (rc != WFS_OK) return rc;
+    if (!img_fwd && !img_t) return WFS_OK;
+    k_filter_images<<<dim3((unsigned)K), dim3(256), 0, (hipStream_t)stream_>>>(job);
+    WFS_LAUNCH_CHECK();
+    return WFS_OK;
+}
 
 extern "C" int wfs_load_batch(const int32_t *coords, int64_t n, int32_t cols, const int32_t *perm_host,
                               int32_t *coords_dst, int32_t *indices_dst, const void *feats, void *feats_dst,
                               int64_t feat_bytes, const int64_t *labels, int64_t *labels_dst, int64_t B,
                               int64_t *n_valid_dst, int32_t *event_offsets, int32_t events, void *stream_) {
+    return wfs_load_batch_images(coords, n, cols, perm_host, coords_dst, indices_dst, feats, feats_dst, feat_bytes, labels,
+                                 labels_dst, B, n_valid_dst, event_offsets, events, nullptr, 0, stream_);
+}
+
+extern "C" int wfs_load_batch_images(const int32_t *coords, int64_t n, int32_t cols, const int32_t *perm_host,
+                                     int32_t *coords_dst, int32_t *indices_dst, const void *feats, void *feats_dst,
+                                     int64_t feat_bytes, const int64_t *labels, int64_t *labels_dst, int64_t B,
+                                     int64_t *n_valid_dst, int32_t *event_offsets, int32_t events,
+                                     const wfs_filter_image_job *jobs, int32_t njobs, void *stream_) {
     hipStream_t stream = (hipStream_t)stream_;
+    WFS_REQUIRE(njobs >= 0 && njobs <= WFS_FILTER_IMAGE_JOBS_MAX && (njobs == 0 || jobs), WFS_EINVAL,
+                "%d filter image jobs (0 .. %d)", njobs, WFS_FILTER_IMAGE_JOBS_MAX);
+    WfsFilterImageJobs images = {};
+    for (int i = 0; i < njobs; ++i) {
+        const int rc = filter_image_job_ok(jobs[i]);
+        if (rc != WFS_OK) return rc;
+        images.j[i] = jobs[i];
+        images.first_block[i + 1] = images.first_block[i] + jobs[i].K;
+    }
+    images.n = njobs;
     WFS_REQUIRE(cols >= 1 && cols <= 8, WFS_EINVAL, "bad coordinate width %d", cols);
     WFS_REQUIRE(n >= 0 && B >= 0 && feat_bytes >= 0, WFS_EINVAL, "negative size");
     WFS_REQUIRE((n == 0 || coords) && (feat_bytes == 0 || (feats && feats_dst)) && (B == 0 || (labels && labels_dst)),
@@ -280,10 +335,10 @@ extern "C" int wfs_load_batch(const int32_t *coords, int64_t n, int32_t cols, co
     if (blocks > 1024) blocks = 1024;
     WFS_REQUIRE(!event_offsets || events >= 1, WFS_EINVAL, "event offsets of %d events", events);
     if (event_offsets && blocks < WFS_EVENT_FLAG_WORDS) blocks = WFS_EVENT_FLAG_WORDS;
-    k_load_batch<<<dim3((unsigned)blocks), dim3(256), 0, stream>>>(
+    k_load_batch<<<dim3((unsigned)(blocks + images.first_block[njobs])), dim3(256), 0, stream>>>(
         coords, n, cols, pm, coords_dst, indices_dst, (const uint4 *)feats, (uint4 *)feats_dst, words,
         (const unsigned char *)feats + words * 16, (unsigned char *)feats_dst + words * 16, tail, (const long long *)labels,
-        (long long *)labels_dst, B, (long long *)n_valid_dst, event_offsets, events, pm.v[0]);
+        (long long *)labels_dst, B, (long long *)n_valid_dst, event_offsets, events, pm.v[0], (int)blocks, images);
     WFS_LAUNCH_CHECK();
     return WFS_OK;
 }

@@ -172,7 +172,7 @@ int wfs_launch_gconv32_f32(const int *table, int mirror, int K, int identity_k, 
 // 16-bit rows (dtype WFS_BF16 or WFS_F16)
 int wfs_launch_gconv32_h16(const int *table, int mirror, int K, int identity_k, long long R, const long long *r_dev,
                            const void *X, const float *W, int transpose_w, const float *bias, void *Y, int dtype,
-                           hipStream_t stream, int packed_kl = 0);
+                           hipStream_t stream, int packed_kl = 0, const void *image = nullptr);
 int wfs_launch_gconv_c2c32(const int *table, const int *kmap, int K, int identity_k, long long R,
                            const long long *r_dev, const void *X, const float *W, const float *bias, void *Y, int dtype,
                            hipStream_t stream);
@@ -190,7 +190,7 @@ int wfs_launch_gdw32(const int *table, int K, int identity_k, long long R, const
 bool wfs_bwd32_fused_ok(int K, int packed_kl, int dtype);
 int wfs_launch_bwd32_h16(const int *table, int packed_kl, int K, int identity_k, long long R, const long long *r_dev,
                          const void *S, const void *G, const float *W, void *dX, int swap, float *dW, float *part, int dtype,
-                         wfs_dw_job *defer, hipStream_t stream);
+                         wfs_dw_job *defer, hipStream_t stream, const void *image_t = nullptr);
 int wfs_launch_gdw_c32c2(const int *table, int mirror, int K, int identity_k, long long R, const long long *r_dev,
                          const void *S, const void *G, int swap, float *dW, float *part, int dtype,
                          wfs_dw_job *defer, hipStream_t stream);

@@ -90,6 +90,7 @@ class _CapturedRunner(object):
         dev = coords.device
         self.module, self.per_row = module, per_row
         self.graph, self._graphs = None, []
+        self._images = []
         self.n_cap = max(_round_up(headroom * coords.shape[0], granule), _round_up(min_rows, granule))
         self.coords = torch.zeros((self.n_cap, coords.shape[1]), dtype=coords.dtype, device=dev)
         self.feats = torch.zeros((self.n_cap, feats.shape[1]), dtype=feats.dtype, device=dev)
@@ -111,6 +112,59 @@ class _CapturedRunner(object):
         self.indices = torch.zeros_like(self.coords) if self._perm is not None else None
         self.events = None            # event offsets of the loaded batch, when the hand-over launch writes them
         return net
+
+    # ---- filter images (include/wfsparse.h "filter images"; spconv.ops.FILTER_IMAGES) --------------------------------
+    # The 32 -> 32 layers of a net with 16-bit rows get the 16-bit LDS images of their filters made ONCE per step, by the
+    # hand-over launch, instead of by every block of every conv launch.  The hand-over is the head of every step and
+    # reads the weights as the previous step's optimizer (or load_state_dict, or a gradient exchange after the replay)
+    # left them, so nothing has to be tracked.  The buffers are this runner's; its layers see them only while its own
+    # body runs (_filter_images_live), so eager calls of the same modules never meet an image.
+    def _make_filter_images(self, backward):
+        from ..spconv.conv import SparseConvolution
+        self._images = []
+        if not ops.FILTER_IMAGES or self.feats.dtype not in (torch.bfloat16, torch.float16):
+            return
+        lib = _lib.load()
+        for m in self.module.modules():
+            if (isinstance(m, SparseConvolution) and m.in_channels == 32 and m.out_channels == 32 and not m.conv1x1
+                    and not m.inverse and m.weight.is_cuda and m.weight.dtype == torch.float32
+                    and m.weight.is_contiguous() and len(self._images) < _lib.FILTER_IMAGE_JOBS_MAX):
+                K = m.weight.numel() // 1024
+                if K > 27:
+                    continue
+                nbytes = int(lib.wfs_filter_image_bytes(K))
+                fwd = torch.zeros((nbytes,), dtype=torch.uint8, device=m.weight.device)
+                t = torch.zeros_like(fwd) if backward else None
+                self._images.append((m, K, (self.feats.dtype, fwd, t)))
+
+    def _filter_image_jobs(self):
+        """The jobs of the hand-over launch, from where the weights live NOW."""
+        code = _lib.dtype_code(self.feats)
+        jobs = (_lib.FilterImageJob * max(1, len(self._images)))()
+        for job, (m, K, (_dt, fwd, t)) in zip(jobs, self._images):
+            w = m.weight
+            if not (w.is_cuda and w.dtype == torch.float32 and w.is_contiguous() and w.numel() == K * 1024):
+                raise RuntimeError("a conv weight changed its layout under a captured step (filter images)")
+            job.W, job.img_fwd, job.img_t, job.K, job.dtype = w.data_ptr(), _lib.ptr(fwd), _lib.ptr(t), K, code
+        return jobs
+
+    def _refresh_filter_images(self):
+        """The images from the current weights by their own launches: wherever the one-launch hand-over does not run."""
+        if not self._images:
+            return
+        lib = _lib.load()
+        for job in self._filter_image_jobs()[:len(self._images)]:
+            _lib.check(lib.wfs_conv_filter_images(job.W, job.K, job.dtype, job.img_fwd, job.img_t, _lib.stream_ptr()))
+
+    @contextlib.contextmanager
+    def _filter_images_live(self):
+        for m, _K, imgs in self._images:
+            m.filter_images = imgs
+        try:
+            yield
+        finally:
+            for m, _K, _imgs in self._images:
+                m.filter_images = None
 
     def _own_stream(self, dev):
         # Stream discipline.  (1) Autograd's AccumulateGrad nodes remember the stream they were created on, and a
@@ -208,6 +262,7 @@ class _CapturedRunner(object):
             if self.indices is not None:
                 self.indices[:n].copy_(coords[:, self._perm], non_blocking=True)
             self._event_offsets()
+            self._refresh_filter_images()
             return
         if (coords.is_cuda and coords.dtype == torch.int32 and coords.is_contiguous() and feats.is_cuda
                 and feats.is_contiguous() and feats.dtype == self.feats.dtype and labels.is_cuda
@@ -216,11 +271,14 @@ class _CapturedRunner(object):
             lib = _lib.load()
             perm = _lib.i32_array(self._perm) if self._perm is not None else None
             ev = self.events if (self.events is not None and perm is not None) else None
-            _lib.check(lib.wfs_load_batch(_lib.ptr(coords), n, coords.shape[1], perm, _lib.ptr(self.coords),
-                                          _lib.ptr(self.indices), _lib.ptr(feats), _lib.ptr(self.feats),
-                                          feats.numel() * feats.element_size(), _lib.ptr(labels), _lib.ptr(self.labels),
-                                          labels.numel(), _lib.ptr(self.n_valid), _lib.ptr(ev), self.n_events,
-                                          _lib.stream_ptr()))
+            args = (_lib.ptr(coords), n, coords.shape[1], perm, _lib.ptr(self.coords), _lib.ptr(self.indices),
+                    _lib.ptr(feats), _lib.ptr(self.feats), feats.numel() * feats.element_size(), _lib.ptr(labels),
+                    _lib.ptr(self.labels), labels.numel(), _lib.ptr(self.n_valid), _lib.ptr(ev), self.n_events)
+            if self._images:           # ... and the step's filter images, same launch
+                _lib.check(lib.wfs_load_batch_images(*args, self._filter_image_jobs(), len(self._images),
+                                                     _lib.stream_ptr()))
+            else:
+                _lib.check(lib.wfs_load_batch(*args, _lib.stream_ptr()))
             if ev is None:
                 self._event_offsets()
             return
@@ -231,6 +289,7 @@ class _CapturedRunner(object):
         if self.indices is not None:
             self.indices[:n].copy_(coords[:, self._perm], non_blocking=True)
         self._event_offsets()
+        self._refresh_filter_images()
 
     def _event_offsets(self):
         """The event offsets of the loaded batch when the hand-over launch did not write them (its own launch)."""
@@ -307,6 +366,7 @@ class GraphedTrainStep(_CapturedRunner):
         # ---- warm-up in device-count mode, then capture
         if self.indices is not None:
             net.batch_first_indices = (self.coords, self.indices)
+        self._make_filter_images(backward=True)
         self._load(example_batch)
         failed, err = 0, None
         try:
@@ -331,6 +391,7 @@ class GraphedTrainStep(_CapturedRunner):
 
     def _warm_and_capture(self, warmup):
         for _ in range(warmup):
+            self._refresh_filter_images()         # the previous warm-up step moved the weights; no hand-over in between
             self._body()
             if not self.in_graph_optimizer:
                 self._after()
@@ -351,6 +412,10 @@ class GraphedTrainStep(_CapturedRunner):
         return ([self.coords, self.feats, self.n_valid], self.labels)
 
     def _body(self):
+        with self._filter_images_live():
+            return self._step_body()
+
+    def _step_body(self):
         self.reducer.reset()
         from ..spconv import functional as Fsp
         loss = self.module.training_step(self._static_batch(), 0)
@@ -588,6 +653,7 @@ class GraphedEvalStep(_CapturedRunner):
                 self._calibrate(headroom, 1.0, granule)
                 if self.indices is not None:
                     net.batch_first_indices = (self.coords, self.indices)
+                self._make_filter_images(backward=False)
                 self._load(example_batch)
                 if sweep:
                     self._reuse = ops.reuse_rulebooks()          # stays open until close()
@@ -610,7 +676,8 @@ class GraphedEvalStep(_CapturedRunner):
         net = self.module.model
         if hasattr(net, "batch_size_hint"):
             net.batch_size_hint = self.n_events
-        return net([self.coords, self.feats, self.n_valid]).float()
+        with self._filter_images_live():
+            return net([self.coords, self.feats, self.n_valid]).float()
 
     def __call__(self, batch, occlude_index=None):
         self._load(batch)

@@ -44,6 +44,9 @@ class SparseConvolution(SparseModule, ops.StickyFlags):
             self.bias = nn.Parameter(torch.Tensor(out_channels))
         else:
             self.register_parameter('bias', None)
+        # (row dtype, forward image, dX image or None) of this layer's filter while a captured runner's step runs
+        # (psd/graph.py "filter images"), else None: a plain attribute, neither a parameter nor part of the state_dict
+        self.filter_images = None
         self.reset_parameters()
 
     def calibration_count(self):
@@ -130,10 +133,10 @@ class SparseConvolution(SparseModule, ops.StickyFlags):
                 out_features = features          # stands in until the fused node below has run
                 out_unique = input.unique if self.subm else True
             elif self.subm:
-                out_features = Fsp.indice_subm_conv(features, self.weight, self.bias, rb)
+                out_features = Fsp.indice_subm_conv(features, self.weight, self.bias, rb, getattr(self, "filter_images", None))
                 out_unique = input.unique
             else:
-                out_features = Fsp.indice_conv(features, self.weight, self.bias, rb)
+                out_features = Fsp.indice_conv(features, self.weight, self.bias, rb, getattr(self, "filter_images", None))
                 out_unique = True      # a regular conv numbers DISTINCT output sites
             out_n_valid = rb.m_dev
         out_tensor = SparseConvTensor(out_features, out_indices, out_spatial_shape, batch_size)

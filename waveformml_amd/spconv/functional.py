@@ -114,17 +114,18 @@ def _wide_gather_conv(lib, table, kmap, K, identity_k, R, X, W, transpose_w, bia
     return Y
 
 
-def gather_conv(table, kmap, K, identity_k, R, X, W, transpose_w, bias, r_dev=None, w16=None, packed_kl=0):
+def gather_conv(table, kmap, K, identity_k, R, X, W, transpose_w, bias, r_dev=None, w16=None, packed_kl=0, image=None):
     """Y[r] = bias + sum_k X[table[kmap[k], r]] . W[k]   (W fp32 [K, Cin, Cout]; ^T if transpose_w).
-    ``packed_kl`` > 0: ``table`` is the packed by-input table [K / packed_kl, R] (Rulebook.table_by_in)."""
+    ``packed_kl`` > 0: ``table`` is the packed by-input table [K / packed_kl, R] (Rulebook.table_by_in).
+    ``image``: W's filter image of this orientation in X's row type (include/wfsparse.h "filter images"), or None."""
     lib = _lib.load()
     Cw_in, Cw_out = int(W.shape[-2]), int(W.shape[-1])
     if packed_kl:
         assert transpose_w and kmap is None and table.shape == (K // packed_kl, R), (table.shape, K, packed_kl, R)
         Y = _rows((R, Cw_in), X, r_dev)
-        _lib.check(lib.wfs_gather_conv(_lib.ptr(table), None, K, identity_k, R, _lib.ptr(X), X.shape[0], X.shape[1],
-                                       _lib.ptr(W), Cw_in, Cw_out, 1, None, _lib.ptr(Y), _lib.dtype_code(X),
-                                       _lib.ptr(r_dev), packed_kl, _lib.stream_ptr()))
+        _lib.check(lib.wfs_gather_conv_image(_lib.ptr(table), None, K, identity_k, R, _lib.ptr(X), X.shape[0], X.shape[1],
+                                             _lib.ptr(W), Cw_in, Cw_out, 1, None, _lib.ptr(Y), _lib.dtype_code(X),
+                                             _lib.ptr(r_dev), packed_kl, _lib.ptr(image), _lib.stream_ptr()))
         if ACCOUNT is not None:
             _account("gather_conv", (table >> 3).clamp_(min=-1), R, X.shape[0], X.shape[1], R, Cw_in, K, Cw_in, Cw_out,
                      X.element_size())
@@ -143,9 +144,10 @@ def gather_conv(table, kmap, K, identity_k, R, X, W, transpose_w, bias, r_dev=No
     assert X.dim() == 2 and X.shape[1] == (Cw_out if transpose_w else Cw_in), (X.shape, W.shape, transpose_w)
     assert table is None or (table.dtype == torch.int32 and table.shape == (K, R)), (None if table is None else table.shape, K, R)
     assert bias is None or (bias.dtype == torch.float32 and bias.numel() == Cy)
-    _lib.check(lib.wfs_gather_conv(_lib.ptr(table), kmap, K, identity_k, R, _lib.ptr(X), X.shape[0], X.shape[1],
-                                   _lib.ptr(W), Cw_in, Cw_out, 1 if transpose_w else 0, _lib.ptr(bias),
-                                   _lib.ptr(Y), _lib.dtype_code(X), _lib.ptr(r_dev), 0, _lib.stream_ptr()))
+    _lib.check(lib.wfs_gather_conv_image(_lib.ptr(table), kmap, K, identity_k, R, _lib.ptr(X), X.shape[0], X.shape[1],
+                                         _lib.ptr(W), Cw_in, Cw_out, 1 if transpose_w else 0, _lib.ptr(bias),
+                                         _lib.ptr(Y), _lib.dtype_code(X), _lib.ptr(r_dev), 0, _lib.ptr(image),
+                                         _lib.stream_ptr()))
     _account("gather_conv", table, R, X.shape[0], X.shape[1], R, Cy, K, Cw_in, Cw_out, X.element_size())
     return Y
 
@@ -297,7 +299,7 @@ def gather_dw(table, K, identity_k, R, S, G, swap, kmap=None, r_dev=None, like=N
     return dW
 
 
-def conv_backward(table, K, identity_k, R, X, dY, W, r_dev=None, like=None, packed_kl=0):
+def conv_backward(table, K, identity_k, R, X, dY, W, r_dev=None, like=None, packed_kl=0, image_t=None):
     """(dX, dW) of a conv / SubM layer in one call (include/wfsparse.h wfs_conv_backward): 32 -> 32 layers with 16-bit
     rows run both products in ONE launch.  ``like``: the filter parameter (its gradient goes straight into its slot of a
     registered flat gradient buffer, the slab reduction joins the step's deferred ones)."""
@@ -310,9 +312,10 @@ def conv_backward(table, K, identity_k, R, X, dY, W, r_dev=None, like=None, pack
     dX = _rows((R, Cin), dY, r_dev)
     ws = torch.empty((max(int(lib.wfs_gather_dw_workspace_bytes(K, R, Cin, Cout)), 1),), dtype=torch.uint8, device=X.device)
     job = _dw_job(dW)
-    _lib.check(lib.wfs_conv_backward(_lib.ptr(table), K, identity_k, R, _lib.ptr(X), _lib.ptr(dY), dY.shape[0], Cin, Cout,
-                                     _lib.ptr(W), _lib.ptr(dX), _lib.ptr(dW), _lib.dtype_code(X), _lib.ptr(ws), ws.numel(),
-                                     _lib.ptr(r_dev), job, packed_kl, _lib.stream_ptr()))
+    _lib.check(lib.wfs_conv_backward_image(_lib.ptr(table), K, identity_k, R, _lib.ptr(X), _lib.ptr(dY), dY.shape[0], Cin,
+                                           Cout, _lib.ptr(W), _lib.ptr(dX), _lib.ptr(dW), _lib.dtype_code(X), _lib.ptr(ws),
+                                           ws.numel(), _lib.ptr(r_dev), job, packed_kl, _lib.ptr(image_t),
+                                           _lib.stream_ptr()))
     _queue_dw_job(job, ws)
     if ACCOUNT is not None:
         # SURVEY.md 8d "backward": X, dY and dX once each, the rulebook twice (8 B per pair), the filters twice
@@ -344,7 +347,7 @@ class SparseConvFunction(Function):
     """features [n_in, Cin], filters [*k, Cin, Cout] fp32, bias [Cout] or None -> [n_out, Cout]."""
 
     @staticmethod
-    def forward(ctx, features, filters, bias, rulebook, mode):
+    def forward(ctx, features, filters, bias, rulebook, mode, images=None):
         rb = rulebook
         features = _features_ok(features)
         K = rb.K
@@ -352,6 +355,12 @@ class SparseConvFunction(Function):
         b = None if bias is None else bias.detach().float().contiguous()
         ident = rb.centre_k if rb.subm else -1
         w16 = None
+        # the layer's filter images (psd/graph.py): only for the rows and the filter they were made for
+        img_fwd = img_t = None
+        if (images is not None and mode != INVERSE and images[0] == features.dtype and tuple(W.shape) == (K, 32, 32)
+                and W.data_ptr() == filters.data_ptr() and K <= 27):
+            img_fwd, img_t = images[1], images[2]
+        ctx.img_t = img_t
         if mode == INVERSE:
             assert features.shape[0] == rb.M, "inverse conv input must be the coupled conv's output set"
             w16 = filters16(W, features) if takes_wide_path(K, rb.N, features, W.shape[2]) else None
@@ -362,7 +371,7 @@ class SparseConvFunction(Function):
             assert features.shape[0] == rb.N
             table, kmap = rb.table_by_out()
             w16 = filters16(W, features) if takes_wide_path(K, rb.M, features, W.shape[2]) else None
-            out = gather_conv(table, kmap, K, ident, rb.M, features, W, False, b, rb.m_dev, w16)
+            out = gather_conv(table, kmap, K, ident, rb.M, features, W, False, b, rb.m_dev, w16, image=img_fwd)
         ctx.save_for_backward(features, filters, bias)
         ctx.rb, ctx.mode = rb, mode
         ctx.w16 = w16 if ctx.needs_input_grad[0] else None       # the 16-bit filters of a wide layer: dX reads them again
@@ -390,7 +399,7 @@ class SparseConvFunction(Function):
             table, pk = rb.table_by_in(32, 32, features, 3)
             if pk and rb.table_by_in(32, 32, dY, 1)[1] != pk:
                 table, pk = rb.nbr_out, 0
-            dX, dW = conv_backward(table, K, ident, rb.N, features, dY, W, rb.n_dev, filters, pk)
+            dX, dW = conv_backward(table, K, ident, rb.N, features, dY, W, rb.n_dev, filters, pk, ctx.img_t)
         else:
             if ctx.needs_input_grad[1]:
                 if features.shape[1] == 2 and dY.shape[1] == 32 and K <= 27 and not rb.has_dup:
@@ -402,13 +411,14 @@ class SparseConvFunction(Function):
                     dW = gather_dw(table, K, ident, rb.N, features, dY, False, None, rb.n_dev, filters, pk)
             if ctx.needs_input_grad[0]:
                 table, pk = rb.table_by_in(dY.shape[1], W.shape[1], dY, 1)
-                dX = gather_conv(table, None, K, ident, rb.N, dY, W, True, None, rb.n_dev, ctx.w16, pk)
+                dX = gather_conv(table, None, K, ident, rb.N, dY, W, True, None, rb.n_dev, ctx.w16, pk,
+                                 image=ctx.img_t if dY.dtype == features.dtype else None)
         if dW is not None:
             dW = dW.reshape(filters.shape).to(filters.dtype)
         if bias is not None and ctx.needs_input_grad[2]:
             # dY has one row per OUTPUT of this product: rb.N rows for an inverse conv, rb.M otherwise
             db = _masked_column_sum(dY, rb.n_dev if mode == INVERSE else rb.m_dev).to(bias.dtype)
-        return dX, dW, db, None, None
+        return dX, dW, db, None, None, None
 
 
 def maxpool_fwd(table, kmap, K, R, X, r_dev=None):
@@ -1109,12 +1119,12 @@ def cross_entropy_mean(logits, target, ignore_index=-100):
 
 # 16-bit storage: bf16, and fp16 for the reference's ``half_precision`` / ``use_half`` (float16 features,
 # src/datasets/HDF5Dataset.py:227-228).  Both have native kernels (fp32 accumulate, fp32 master filters).
-def indice_conv(features, filters, bias, rulebook):
-    return SparseConvFunction.apply(features, filters, bias, rulebook, CONV)
+def indice_conv(features, filters, bias, rulebook, images=None):
+    return SparseConvFunction.apply(features, filters, bias, rulebook, CONV, images)
 
 
-def indice_subm_conv(features, filters, bias, rulebook):
-    return SparseConvFunction.apply(features, filters, bias, rulebook, SUBM)
+def indice_subm_conv(features, filters, bias, rulebook, images=None):
+    return SparseConvFunction.apply(features, filters, bias, rulebook, SUBM, images)
 
 
 def indice_inverse_conv(features, filters, bias, rulebook):

@@ -45,6 +45,11 @@ EVENT_LOCAL_MAX_BATCH = 16384
 EVENT_LOCAL_CONV = os.environ.get("WFS_EVENT_LOCAL_CONV", "1") != "0"
 PACKED_TABLES = os.environ.get("WFS_PACKED_TABLES", "1") != "0"
 
+# Filter images (include/wfsparse.h "filter images"; psd/graph.py): a captured runner has the 16-bit LDS images of its
+# 32 -> 32 layers' filters made once per step by the hand-over launch, and the conv launches copy them into LDS instead of
+# converting the fp32 filter in every block.  Bit-identical results.  False (WFS_FILTER_IMAGES=0): every launch converts.
+FILTER_IMAGES = os.environ.get("WFS_FILTER_IMAGES", "1") != "0"
+
 _SIDE_STREAMS = {}
 
 
