@@ -211,6 +211,19 @@ int wfs_wide_gather_conv(const int32_t *table, const int32_t *kmap_host, int32_t
                          int32_t Cw_in, int32_t Cw_out, int32_t transpose_w, const float *bias, void *Y,
                          int32_t dtype, const int64_t *r_dev, void *workspace, size_t workspace_bytes,
                          void *stream);
+/* Rows at or beyond *r_dev of wfs_wide_gather_conv's Y are not written, whichever product order the layer takes
+ * (the direct store of the product and the ordered sum both take the count). */
+
+/* What a wide product of a shape would launch, host only, nothing launched (tests/test_wide_cases_host.py reads from
+ * it which arm a case runs; decided by the planning helpers of csrc/wide.hip themselves).  kind 0: conv forward / dX
+ * (K, R, X_rows, Ca = Cx, Cb = Cy with the channel roles as wfs_wide_gather_conv's caller swaps them, has_table);
+ * 1: conv dW (K, R, Ca = Cs, Cb = Cg); 2: linear forward and 3: linear dW (R = B, Ca = I, Cb = O).  out[7] (may be
+ * NULL): dense_first, nz, nseg, ksplit, kchunk, the fp32 slabs the ordered sum adds per output element (0: it does
+ * not run), the slabs of one offset among them.  Returns 1 / 0 = the wide path takes / does not take the shape
+ * (wfs_wide_conv_ok, the dW arm of wfs_gather_dw, wfs_wide_linear_ok), -WFS_EINVAL for refused arguments.
+ * Additions only: WFS_ABI_VERSION stays. */
+int wfs_wide_plan(int32_t kind, int32_t K, int64_t R, int64_t X_rows, int32_t Ca, int32_t Cb, int32_t has_table,
+                  int32_t dtype, int32_t *out);
 
 /* Dense head layer on the matrix cores (round 3; csrc/wide.hip).
  * Replaces torch.nn.functional.linear for the reference's dense head when it is wide (the hybrid net's

@@ -77,6 +77,7 @@ SIGNATURES = {
     "wfs_wide_filters": (ctypes.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "wfs_wide_gather_conv": (ctypes.c_int, [_vp, c_i32p, _i32, _i32, _i64, _vp, _i64, _i32, _vp, _vp, _i32, _i32, _i32,
                                             _vp, _vp, _i32, _vp, _vp, _sz, _vp]),
+    "wfs_wide_plan": (ctypes.c_int, [_i32, _i32, _i64, _i64, _i32, _i32, _i32, _i32, c_i32p]),
     "wfs_wide_linear_ok": (ctypes.c_int, [_i64, _i32, _i32, _i32]),
     "wfs_wide_linear_workspace_bytes": (_sz, [_i64, _i32, _i32, _i32]),
     "wfs_wide_linear_fwd": (ctypes.c_int, [_vp, _i64, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _sz, _vp]),

@@ -59,6 +59,7 @@ struct GemmArgs {
     int ksplit, kchunk;           // every segment's contraction is cut into ksplit parts of kchunk (multiple of a step):
                                   // block z = zs * ksplit + part writes its own slab of C (summed by k_sum_rows)
     const long long *k_dev;       // optional device-side contraction length (<= Ks): rows of a dW product
+    const long long *m_dev;       // optional device-side row count of C (<= M): rows at or beyond it are not stored
     int out_h;                    // 1: C holds elements of the row type (bias added), 0: fp32 partial products
 };
 
@@ -324,6 +325,11 @@ __global__ void __launch_bounds__(GTHREADS) k_gemm16(GemmArgs g) {
     }
     // C/D map of the 32 x 32 MFMA: column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
     const int h = lane >> 5;
+    int Mv = g.M;                 // rows at or beyond a device-side count keep what the caller left there
+    if (g.m_dev) {
+        const long long md = *g.m_dev;
+        Mv = md < Mv ? (int)(md < 0 ? 0 : md) : Mv;
+    }
 #pragma unroll
     for (int a = 0; a < TM; ++a)
 #pragma unroll
@@ -334,7 +340,7 @@ __global__ void __launch_bounds__(GTHREADS) k_gemm16(GemmArgs g) {
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
                 const int m = m0 + wm * (BM / 2) + a * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
-                if (m >= g.M) continue;
+                if (m >= Mv) continue;
                 const long long e = g.zC * zs + g.pC * part + (long long)m * g.ldc + n;
                 if (g.out_h)
                     wfs_st(reinterpret_cast<H *>(g.C) + e, acc[a][b][i] + bv);
@@ -457,6 +463,7 @@ __global__ void __launch_bounds__(256) k_sum_rows(const int *__restrict__ table,
     const long long r = blockIdx.x;
     long long Rv = r_dev ? *r_dev : R;
     Rv = Rv < R ? Rv : R;
+    if (r >= Rv) return;          // the whole block: nothing beyond the count is written
     if (threadIdx.x < K) {
         const int k = threadIdx.x;
         long long s = -1;
@@ -789,7 +796,7 @@ extern "C" int wfs_wide_gather_conv(const int32_t *table, const int32_t *kmap_ho
     g.lda = (long long)K * Cxp, g.sA = Cxp;
     g.M = (int)R, g.N = Cy, g.nseg = p.nseg, g.nz = p.nz;
     if (p.nz * p.ksplit == 1) {
-        g.C = Y, g.ldc = Cy, g.out_h = 1, g.bias = bias;
+        g.C = Y, g.ldc = Cy, g.out_h = 1, g.bias = bias, g.m_dev = r_dev;
         return gemm(g, 0, b_km, dtype, stream);
     }
     const long long slab = R * (long long)Cyp;
@@ -1006,4 +1013,53 @@ extern "C" int wfs_wide_linear_bwd(const void *X, const float *dY, int64_t B, in
         return launch_sum_rows<float>(nullptr, km, 1, -1, 1, nullptr, dY, 1, 0, 0, (int)B, O, nullptr, O, db, stream);
     }
     return WFS_OK;
+}
+
+// ------------------------------------------------------------------------------------------ the plan, for tests
+// What a wide product of this shape would launch, decided by conv_plan / dw_split / lin_split / plan_ksplit themselves;
+// nothing is launched.  tests/test_wide_cases_host.py takes from here which arm a case of its table runs.
+//   kind 0  conv, forward or dX: K offsets, R destination rows, X_rows source rows, Ca = Cx, Cb = Cy (as the caller
+//           of wfs_wide_gather_conv swaps them for dX), has_table
+//   kind 1  conv dW: K, R, Ca = Cs, Cb = Cg                     (X_rows, has_table unused)
+//   kind 2  linear forward: R = B, Ca = I, Cb = O               (K, X_rows, has_table unused)
+//   kind 3  linear dW [O, I]: R = B, Ca = I, Cb = O
+// out (7 ints, may be NULL): dense_first, nz, nseg, ksplit, kchunk, the number of fp32 slabs k_sum_rows adds per output
+// element (0: it does not run, the product stores its result itself) and P, the slabs of ONE offset (its
+// four-at-a-time loop).  Returns 1 when the wide path takes the shape (wfs_wide_conv_ok / wfs_wide_dw_ok /
+// wfs_wide_linear_ok), 0 when it does not (out still holds the plan), -WFS_EINVAL for arguments the entry points refuse.
+extern "C" int wfs_wide_plan(int32_t kind, int32_t K, int64_t R, int64_t X_rows, int32_t Ca, int32_t Cb,
+                             int32_t has_table, int32_t dtype, int32_t *out) {
+    if (!wfs_dtype_ok(dtype) || kind < 0 || kind > 3 || R < 1 || R >= (1ll << 31) || Ca < 1 || Cb < 1) return -WFS_EINVAL;
+    const int es = wfs_dtype_bytes(dtype);
+    int o[7] = {0, 1, 1, 1, 0, 0, 1};
+    int ok;
+    if (kind == 0) {
+        if (K < 1 || K > 128 || X_rows < 1 || X_rows >= (1ll << 31)) return -WFS_EINVAL;
+        if (!has_table && (K != 1 || X_rows != R)) return -WFS_EINVAL;
+        const WidePlan p = conv_plan(K, R, X_rows, Ca, Cb, Ca, Cb, has_table != 0, es);
+        o[0] = p.dense_first, o[1] = p.nz, o[2] = p.nseg, o[3] = p.ksplit, o[4] = p.kchunk;
+        o[5] = p.dense_first ? K * p.ksplit : (p.nz * p.ksplit > 1 ? p.nz * p.ksplit : 0);
+        o[6] = p.dense_first ? p.ksplit : 1;
+        ok = wfs_wide_conv_ok(K, R, X_rows, Ca, Cb, dtype);
+    } else if (kind == 1) {
+        if (K < 1 || K > 128) return -WFS_EINVAL;
+        o[1] = K;
+        o[3] = dw_split(K, R, Ca, Cb, es, &o[4]);
+        o[5] = o[3] > 1 ? o[3] : 0;
+        o[6] = o[3];
+        ok = wfs_wide_dw_ok(K, R, Ca, Cb, dtype) ? 1 : 0;
+    } else {
+        if (Ca < 8) return -WFS_EINVAL;
+        if (kind == 2) {
+            o[3] = lin_split(R, Ca, Cb, es, &o[4]);
+            o[5] = o[3];
+        } else {
+            o[3] = plan_ksplit(wfs_cdiv(Cb, GT) * wfs_cdiv(Ca, GT), (int)R, es, &o[4]);
+            o[5] = o[3] > 1 ? o[3] : 0;
+        }
+        o[6] = o[3];
+        ok = wfs_wide_linear_ok(R, Ca, Cb, dtype);
+    }
+    for (int i = 0; i < 7 && out; ++i) out[i] = o[i];
+    return ok;
 }
