@@ -5,7 +5,11 @@
 // statistics over the N ACTIVE voxels only, per rank (no SyncBN).  Same arithmetic here, in two launches per
 // direction: a column reduction into <= 256 per-block partials, and the elementwise pass, whose every block first
 // folds those partials in a fixed order (deterministic, no atomics; at the PSD batch sizes a launch costs ~5 us, more
-// than re-reading 64 KB of L2-resident partials per block) and whose block 0 publishes the statistics.
+// than re-reading 64 KB of L2-resident partials per block) and whose block 0 publishes the statistics.  In the
+// register-resident elementwise kernels 16-bit rows move in 16-byte lanes of 8 channels (C % 8 == 0) and a block has
+// 512 threads, of which the first 256 fold (RrLanes, rr_threads; profiles/bn_elementwise_ab.txt).  The forward
+// kernel still loads the shift, and block 0 the running statistics, behind the fold's barriers: replacing those loads
+// by constants saves 0.1 us per launch (WFS_BN_KNOCK bit 16), under the 0.5-us line, so they stay where they are.
 //
 //   forward   mean_c, var_c (biased) over rows;  y = max(0, gamma*(x-mean)*invstd + beta)   [ReLU optional]
 //             running_mean/var updated with momentum (unbiased var), as torch does
@@ -48,6 +52,13 @@ __device__ __forceinline__ void store_vec(T *p, const float *in) {
         v.x = wfs_pack2<T>(in[0], in[1]);
         v.y = wfs_pack2<T>(in[2], in[3]);
         *reinterpret_cast<uint2 *>(p) = v;
+    } else if constexpr (VEC == 8 && sizeof(T) == 2) {
+        uint4 v;
+        v.x = wfs_pack2<T>(in[0], in[1]);
+        v.y = wfs_pack2<T>(in[2], in[3]);
+        v.z = wfs_pack2<T>(in[4], in[5]);
+        v.w = wfs_pack2<T>(in[6], in[7]);
+        *reinterpret_cast<uint4 *>(p) = v;
     } else {
 #pragma unroll
         for (int i = 0; i < VEC; ++i) wfs_st(p + i, in[i]);
@@ -143,32 +154,37 @@ __device__ __forceinline__ int fold_cp(int C) {
     while (Cp < C && Cp < TB) Cp <<= 1;
     return Cp;
 }
+// NT = threads of the block: the first TB fold, the others (NT > TB) only meet them at the barriers.
+template <int NT = TB>
 __device__ __forceinline__ void fold_partials(const float *__restrict__ partial, int nblk, int C, float *sSlice,
                                               float *sA, float *sB) {
     const int Cp = fold_cp(C);
     const int S = TB / Cp;                                  // 1 when C >= TB
     const int col = threadIdx.x % Cp, sl = threadIdx.x / Cp;
     const long long st = 2ll * C;
+    const bool folds = NT == TB || threadIdx.x < TB;
     for (int cbase = 0; cbase < C; cbase += Cp) {          // one pass unless C > TB
         const int c = cbase + col;
         const int cc = c < C ? c : 0;
-        float av[FOLD_PER], bv[FOLD_PER];
+        if (folds) {
+            float av[FOLD_PER], bv[FOLD_PER];
 #pragma unroll
-        for (int i = 0; i < FOLD_PER; ++i) {
-            const int p = sl + i * S;
-            const float *q = partial + (long long)(p < nblk ? p : 0) * st + cc;
-            av[i] = q[0];
-            bv[i] = q[C];
-        }
-        float a = 0.f, bb = 0.f;
+            for (int i = 0; i < FOLD_PER; ++i) {
+                const int p = sl + i * S;
+                const float *q = partial + (long long)(p < nblk ? p : 0) * st + cc;
+                av[i] = q[0];
+                bv[i] = q[C];
+            }
+            float a = 0.f, bb = 0.f;
 #pragma unroll
-        for (int i = 0; i < FOLD_PER; ++i) {
-            const bool ok = (sl + i * S < nblk) & (c < C);
-            a += ok ? av[i] : 0.f;
-            bb += ok ? bv[i] : 0.f;
+            for (int i = 0; i < FOLD_PER; ++i) {
+                const bool ok = (sl + i * S < nblk) & (c < C);
+                a += ok ? av[i] : 0.f;
+                bb += ok ? bv[i] : 0.f;
+            }
+            sSlice[threadIdx.x] = a;
+            sSlice[TB + threadIdx.x] = bb;
         }
-        sSlice[threadIdx.x] = a;
-        sSlice[TB + threadIdx.x] = bb;
         __syncthreads();
         if (sl == 0 && c < C) {
             float ta = 0.f, tb = 0.f;
@@ -325,7 +341,8 @@ __global__ void __launch_bounds__(TB) k_bn_bwd_apply(const T *__restrict__ X, co
 constexpr int RR_BLOCKS = 256;
 // Timing knock-outs (tools/exp/knock_bn.sh, profiles/r02_bn_knockouts.txt): -DWFS_BN_KNOCK=bits builds a library whose
 // register-resident BatchNorm kernels skip a phase -- 1 the fold of the partials, 2 the row loads, 4 the row stores,
-// 8 the block reduction + partial store of the reduce kernel.  Results are wrong by construction; 0 = nothing.
+// 8 the block reduction + partial store of the reduce kernel, 16 the loads behind the fold in the forward elementwise
+// kernel (the shift, block 0's running statistics: constants).  Results are wrong by construction; 0 = nothing.
 #ifndef WFS_BN_KNOCK
 #define WFS_BN_KNOCK 0
 #endif
@@ -471,8 +488,51 @@ __global__ void __launch_bounds__(TB) k_bn_reduce_rr(const T *__restrict__ X, co
     }
 }
 
-template <typename T, int PER>
-__global__ void __launch_bounds__(TB) k_bn_apply_rr(const T *__restrict__ X, long long Ncap,
+// The elementwise kernels move a row in lanes of 16 bytes: 4 fp32 channels (Raw4), or 8 channels of 16-bit rows when
+// C % 8 == 0 (Raw8: one global_load_dwordx4 / global_store_dwordx4 per lane, a wave instruction covers 1 KiB of
+// consecutive rows instead of 512 B).  The reduce kernel keeps 4 channels per lane for every type: its thread-to-row map
+// is the summation order.
+template <typename T>
+struct Raw8 {                                     // eight 16-bit channels as loaded
+    static_assert(sizeof(T) == 2, "8-channel lanes are for 16-bit rows");
+    uint4 v;
+    __device__ __forceinline__ void load(const T *p) { v = *reinterpret_cast<const uint4 *>(p); }
+    __device__ __forceinline__ void get(float *o) const {
+        wfs_unpack2<T>(v.x, o[0], o[1]);
+        wfs_unpack2<T>(v.y, o[2], o[3]);
+        wfs_unpack2<T>(v.z, o[4], o[5]);
+        wfs_unpack2<T>(v.w, o[6], o[7]);
+    }
+};
+template <typename T, int VEC>
+using RawLane = std::conditional_t<VEC == 8, Raw8<T>, Raw4<T>>;
+
+// Thread layout of the elementwise kernels: (row slot, group of VEC channels).  A block owns the rows its number owns
+// in the reduce launch -- slots4 = TB / (C / 4) consecutive rows, PER4 times, gridDim.x * slots4 rows apart -- and
+// spreads them over SPLIT = VEC / 4 * NT / TB times as many row slots (NT = threads of the block, rr_threads below):
+// slot = sub * slots4 + slot4 takes the repeats sub, sub + SPLIT, ...  (PER4 / SPLIT of them, the kernels' PER).
+// VEC = 4 in TB threads: the reduce kernel's own map.  Each output element is the same expression of the same inputs
+// whichever thread computes it, so the results do not depend on VEC or NT.
+template <int VEC, int NT>
+struct RrLanes {
+    int c0;
+    bool active;
+    long long first, step;                        // row of repeat j: first + j * step
+    __device__ __forceinline__ RrLanes(int C) {
+        constexpr int SPLIT = VEC / 4 * (NT / TB);
+        const int groups = C / VEC, slots4 = TB / (C / 4);
+        const int grp = threadIdx.x % groups, slot = threadIdx.x / groups;
+        const int sub = slot / slots4, slot4 = slot % slots4;
+        const long long stride4 = (long long)gridDim.x * slots4;
+        active = sub < SPLIT;
+        c0 = grp * VEC;
+        first = (long long)blockIdx.x * slots4 + slot4 + sub * stride4;
+        step = SPLIT * stride4;
+    }
+};
+
+template <typename T, int PER, int VEC, int NT>
+__global__ void __launch_bounds__(NT) k_bn_apply_rr(const T *__restrict__ X, long long Ncap,
                                                     const long long *__restrict__ n_dev, int C,
                                                     const float *__restrict__ gamma, const float *__restrict__ beta,
                                                     float *__restrict__ running_mean, float *__restrict__ running_var,
@@ -480,15 +540,13 @@ __global__ void __launch_bounds__(TB) k_bn_apply_rr(const T *__restrict__ X, lon
                                                     int relu, T *__restrict__ Y, float *__restrict__ save_mean,
                                                     float *__restrict__ save_invstd, const float *__restrict__ partial,
                                                     int nblk) {
-    constexpr int VEC = 4;
     __shared__ float sSlice[2 * TB];
     __shared__ float sA[MAXC], sB[MAXC];
-    const int groups = C / VEC, slots = TB / groups;
-    const int grp = threadIdx.x % groups, slot = threadIdx.x / groups;
-    const bool active = slot < slots;
-    const int c0 = grp * VEC;
-    const long long stride = (long long)gridDim.x * slots, first = (long long)blockIdx.x * slots + slot;
-    Raw4<T> x[PER];
+    const RrLanes<VEC, NT> ln(C);
+    const bool active = ln.active;
+    const int c0 = ln.c0;
+    const long long stride = ln.step, first = ln.first;
+    RawLane<T, VEC> x[PER];
 #pragma unroll
     for (int i = 0; i < PER; ++i) {
         const long long r = first + i * stride;
@@ -502,15 +560,15 @@ __global__ void __launch_bounds__(TB) k_bn_apply_rr(const T *__restrict__ X, lon
         be[i] = (beta && active) ? beta[c0 + i] : 0.f;
     }
     if (WFS_BN_KNOCK & 1) {
-        for (int c = threadIdx.x; c < C; c += TB) sA[c] = sB[c] = 1.f;
+        for (int c = threadIdx.x; c < C; c += NT) sA[c] = sB[c] = 1.f;
         __syncthreads();
     } else {
-        fold_partials(partial, nblk, C, sSlice, sA, sB);             // its loads join the ones above
+        fold_partials<NT>(partial, nblk, C, sSlice, sA, sB);         // its loads join the ones above
     }
     const float n = N > 0 ? (float)N : 1.f;
-    for (int c = threadIdx.x; c < C; c += TB) {
+    for (int c = threadIdx.x; c < C; c += NT) {
         float mean, var;
-        const float shift = wfs_ld(X + c);
+        const float shift = (WFS_BN_KNOCK & 16) ? 1.f : wfs_ld(X + c);
         const float md = sA[c] / n;
         var = sB[c] / n - md * md;
         mean = shift + md;
@@ -523,8 +581,8 @@ __global__ void __launch_bounds__(TB) k_bn_apply_rr(const T *__restrict__ X, lon
             save_invstd[c] = inv;
             if (running_mean) {
                 float unbiased = N > 1 ? var * (n / (n - 1.f)) : var;
-                running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * mean;
-                running_var[c] = (1.f - momentum) * running_var[c] + momentum * unbiased;
+                running_mean[c] = (1.f - momentum) * ((WFS_BN_KNOCK & 16) ? 1.f : running_mean[c]) + momentum * mean;
+                running_var[c] = (1.f - momentum) * ((WFS_BN_KNOCK & 16) ? 1.f : running_var[c]) + momentum * unbiased;
             }
         }
     }
@@ -553,23 +611,21 @@ __global__ void __launch_bounds__(TB) k_bn_apply_rr(const T *__restrict__ X, lon
     }
 }
 
-template <typename T, int PER>
-__global__ void __launch_bounds__(TB) k_bn_bwd_apply_rr(const T *__restrict__ X, const T *__restrict__ dY,
+template <typename T, int PER, int VEC, int NT>
+__global__ void __launch_bounds__(NT) k_bn_bwd_apply_rr(const T *__restrict__ X, const T *__restrict__ dY,
                                                         long long Ncap, const long long *__restrict__ n_dev, int C,
                                                         const float *__restrict__ partial, int nblk,
                                                         const float *__restrict__ mean, const float *__restrict__ invstd,
                                                         const float *__restrict__ gamma, const float *__restrict__ beta,
                                                         int training, int relu, T *__restrict__ dX,
                                                         float *__restrict__ dgamma, float *__restrict__ dbeta) {
-    constexpr int VEC = 4;
     __shared__ float sSlice[2 * TB];
     __shared__ float sA[MAXC], sB[MAXC];
-    const int groups = C / VEC, slots = TB / groups;
-    const int grp = threadIdx.x % groups, slot = threadIdx.x / groups;
-    const bool active = slot < slots;
-    const int c0 = grp * VEC;
-    const long long stride = (long long)gridDim.x * slots, first = (long long)blockIdx.x * slots + slot;
-    Raw4<T> x[PER], g[PER];
+    const RrLanes<VEC, NT> ln(C);
+    const bool active = ln.active;
+    const int c0 = ln.c0;
+    const long long stride = ln.step, first = ln.first;
+    RawLane<T, VEC> x[PER], g[PER];
 #pragma unroll
     for (int i = 0; i < PER; ++i) {
         const long long r = first + i * stride;
@@ -587,13 +643,13 @@ __global__ void __launch_bounds__(TB) k_bn_bwd_apply_rr(const T *__restrict__ X,
         be[i] = (beta && active) ? beta[c0 + i] : 0.f;
     }
     if (WFS_BN_KNOCK & 1) {
-        for (int c = threadIdx.x; c < C; c += TB) sA[c] = sB[c] = 1.f;
+        for (int c = threadIdx.x; c < C; c += NT) sA[c] = sB[c] = 1.f;
         __syncthreads();
     } else {
-        fold_partials(partial, nblk, C, sSlice, sA, sB);
+        fold_partials<NT>(partial, nblk, C, sSlice, sA, sB);
     }
     if (blockIdx.x == 0) {
-        for (int c = threadIdx.x; c < C; c += TB) {
+        for (int c = threadIdx.x; c < C; c += NT) {
             if (dbeta) dbeta[c] = sA[c];
             if (dgamma) dgamma[c] = sB[c];
         }
@@ -638,6 +694,20 @@ int rr_plan(long long N, int C, int max_per, long long *blocks) {
     for (int per : {2, 4, 8, 16})
         if (need <= per && per <= max_per) return per;
     return 0;
+}
+
+// 16-bit rows of the register-resident elementwise kernels move in lanes of 8 channels when the rows split into such
+// lanes and every row buffer is 16-byte aligned; otherwise, and for fp32 rows, in lanes of 4.  Internal to those two
+// kernels: arm, rows per thread and partial count of a call stay the reduce launch's (rr_plan, wfs_bn_plan).
+// Threads of an elementwise block.  With lanes of 8 and at least 4 rows per thread in the reduce launch the block has
+// 512: the first TB threads fold exactly as a TB-thread block does, all 512 share the block's rows (two waves per SIMD
+// in the row phase, a quarter of the reduce launch's rows per thread).  Registers: 176 forward, 208 backward per wave.
+// The strided rulebook builds (evconv.hip, EC_MIN_WAVES: 2 x 72 registers per SIMD) run beside the FORWARD launches of
+// a step and still fit: 2 x 176 + 144 <= 512.  Nothing of theirs runs beside the backward launches.
+constexpr int rr_threads(int per, int vec) { return vec == 8 && per >= 4 ? 2 * TB : TB; }
+template <typename... P>
+bool rr_lane8(int C, const P *...rows) {
+    return C % 8 == 0 && ((reinterpret_cast<uintptr_t>(rows) | ...) & 15) == 0;
 }
 
 long long bn_reduce_blocks(long long N, int C) {      // = number of partials every elementwise block folds
@@ -898,6 +968,8 @@ extern "C" size_t wfs_bn_workspace_bytes(int64_t N, int32_t C) {
 //   (negative, 1 being taken; also for N < 0, which the entry points leave unchecked)
 // *partials = the number of partials the elementwise pass folds (0: it folds none, the eval forward).  N == 0 launches
 // nothing; the arm reported is the one whose checks the call passes through.
+// *rows_per_thread is the reduce launch's; the elementwise kernels of arm 1 spread the same rows of a block over wider
+// lanes and more threads (rr_lane8, rr_threads), which is not reported here.
 extern "C" int wfs_bn_plan(int64_t N, int32_t C, int32_t dtype, int32_t training, int32_t backward,
                            int32_t *rows_per_thread, int32_t *partials) {
     int per = 0;
@@ -933,7 +1005,9 @@ extern "C" int wfs_bn_plan(int64_t N, int32_t C, int32_t dtype, int32_t training
 }
 
 // C channels starting at X / Y (row stride ld elements): one slice of a wide layer, or the whole layer (ld == C).
-// The choice of kernels below is restated by wfs_bn_plan: change the two together.
+// The choice of kernels below is restated by wfs_bn_plan: change the two together.  Arm, rows per thread and partial
+// count are those of the REDUCE launch; lane width, block size and rows per thread of the register-resident
+// elementwise kernels (rr_lane8, rr_threads) are internal and not reported.
 static int bn_fwd_slice(const void *X, int64_t N, int32_t C, long long ld, const float *gamma, const float *beta,
                         float *running_mean, float *running_var, int64_t *num_batches_tracked, float momentum,
                         float eps, int32_t training, int32_t relu, void *Y, float *save_mean, float *save_invstd,
@@ -961,9 +1035,20 @@ static int bn_fwd_slice(const void *X, int64_t N, int32_t C, long long ld, const
                     constexpr int PER = decltype(per_c)::value;
                     k_bn_reduce_rr<T, PER, 0><<<g2, block, 0, stream>>>((const T *)X, nullptr, N, n_dev, C, nullptr, nullptr,
                                                                          nullptr, nullptr, 0, partial);
-                    k_bn_apply_rr<T, PER><<<g2, block, 0, stream>>>(
-                        (const T *)X, N, n_dev, C, gamma, beta, running_mean, running_var, (long long *)num_batches_tracked,
-                        momentum, eps, relu, (T *)Y, save_mean, save_invstd, partial, (int)rb);
+                    auto apply = [&](auto vec_c) {
+                        constexpr int VEC = decltype(vec_c)::value;
+                        constexpr int NT = rr_threads(PER, VEC);
+                        k_bn_apply_rr<T, PER * 4 / VEC * TB / NT, VEC, NT><<<g2, dim3(NT), 0, stream>>>(
+                            (const T *)X, N, n_dev, C, gamma, beta, running_mean, running_var,
+                            (long long *)num_batches_tracked, momentum, eps, relu, (T *)Y, save_mean, save_invstd, partial,
+                            (int)rb);
+                    };
+                    if constexpr (sizeof(T) == 2) {
+                        if (rr_lane8(C, X, Y)) apply(std::integral_constant<int, 8>{});
+                        else apply(std::integral_constant<int, 4>{});
+                    } else {
+                        apply(std::integral_constant<int, 4>{});
+                    }
                     WFS_LAUNCH_CHECK();
                     return WFS_OK;
                 });
@@ -1024,7 +1109,9 @@ extern "C" int wfs_bn_relu_fwd(const void *X, int64_t N, int32_t C, const float 
     return WFS_OK;
 }
 
-// The choice of kernels below is restated by wfs_bn_plan: change the two together.
+// The choice of kernels below is restated by wfs_bn_plan: change the two together.  Arm, rows per thread and partial
+// count are those of the REDUCE launch; lane width, block size and rows per thread of the register-resident
+// elementwise kernels (rr_lane8, rr_threads) are internal and not reported.
 static int bn_bwd_slice(const void *X, const void *dY, int64_t N, int32_t C, long long ld, const float *gamma,
                         const float *beta, const float *save_mean, const float *save_invstd, int32_t training,
                         int32_t relu, void *dX, float *dgamma, float *dbeta, void *workspace, size_t workspace_bytes,
@@ -1054,9 +1141,19 @@ static int bn_bwd_slice(const void *X, const void *dY, int64_t N, int32_t C, lon
                     constexpr int PER = decltype(per_c)::value;
                     k_bn_reduce_rr<T, PER, 1><<<g2, block, 0, stream>>>((const T *)X, (const T *)dY, N, n_dev, C, save_mean,
                                                                          save_invstd, gamma, beta, relu, partial);
-                    k_bn_bwd_apply_rr<T, PER><<<g2, block, 0, stream>>>((const T *)X, (const T *)dY, N, n_dev, C, partial,
-                                                                        (int)rb, save_mean, save_invstd, gamma, beta,
-                                                                        training, relu, (T *)dX, dgamma, dbeta);
+                    auto apply = [&](auto vec_c) {
+                        constexpr int VEC = decltype(vec_c)::value;
+                        constexpr int NT = rr_threads(PER, VEC);
+                        k_bn_bwd_apply_rr<T, PER * 4 / VEC * TB / NT, VEC, NT><<<g2, dim3(NT), 0, stream>>>(
+                            (const T *)X, (const T *)dY, N, n_dev, C, partial, (int)rb, save_mean, save_invstd, gamma, beta,
+                            training, relu, (T *)dX, dgamma, dbeta);
+                    };
+                    if constexpr (sizeof(T) == 2) {
+                        if (rr_lane8(C, X, dY, dX)) apply(std::integral_constant<int, 8>{});
+                        else apply(std::integral_constant<int, 4>{});
+                    } else {
+                        apply(std::integral_constant<int, 4>{});
+                    }
                     WFS_LAUNCH_CHECK();
                     return WFS_OK;
                 });
