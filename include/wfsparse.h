@@ -1117,6 +1117,41 @@ int wfs_masked_regression_loss_backward(const void *pred, int32_t pred_dtype, co
                                         int32_t nx, int32_t ny, int64_t n_cap, const int64_t *n_dev, int32_t kind,
                                         const int64_t *count, const float *grad, void *dpred, void *stream);
 int wfs_error_edges(double max_abs, int32_t n_bins, double *first_last);
+
+/* the segment loss of the dense-map regression modules, LitZ / LitEZ (csrc/segmaploss.hip) ------------------
+ * Additions only: WFS_ABI_VERSION stays.
+ *
+ * wfs_segment_map_loss (ONE launch on `stream`): the reference's LitBase._calc_segment_loss for up to 4 planes at once.
+ * A row is COUNTED when it lies below the valid count, its (x, y, event) lies inside [nx, ny, B] and, with a mask, its
+ * mask entry is 1.0.  For a counted row and plane p, d = map[event, p, x, y] - target[row, cols[p]] in fp64.  A row that
+ * is not counted is selected out: nothing in it, and no map cell outside the counted rows, reaches a result;
+ * coordinates beyond the valid count are never read.
+ *   map         [B, planes, nx, ny] of map_dtype, planes <= 4, nx * ny <= 256; coords int32 [n_cap, 3] = (x, y, event)
+ *   target      [n_cap, n_cols] of target_dtype; cols HOST int32 [planes]: plane p is scored against column cols[p]
+ *   se_mask     float [nx, ny] or NULL; n_dev as everywhere; kind WFS_LOSS_L1 / WFS_LOSS_MSE
+ *   max_blocks  0 = the default grid (the result does not depend on it)
+ *   workspace   wfs_segment_map_loss_workspace_bytes(n_cap, planes) bytes whose first 4 are ZERO before the first use;
+ *               the launch leaves them zero, so a buffer is zeroed once.  One launch at a time per workspace.
+ *   out         float [planes + 1]: out[p] = the sum over the counted rows of |d| or d^2, divided by the count;
+ *               out[planes] = the sum of those per-plane values, formed in fp64 and rounded once.  count int64 [1].
+ *               fp64 chunk sums folded in a fixed order, no floating-point atomics: bit-identical from run to run and
+ *               independent of max_blocks, n_cap and B.  No row counted: NaN everywhere and a count of 0.
+ * wfs_segment_map_loss_backward (ONE launch) writes ALL of dmap [B, planes, nx, ny] of map_dtype (16-byte aligned):
+ *   grad[0] * s / count[0] at a counted row's cell, s = sign(d) (sign(0) = 0) for L1, 2 d for MSE, and exactly 0 in
+ *   every other cell -- events without rows and events beyond the batch's own included -- and everywhere when count is 0.
+ *   The rows of the batch are grouped by event in ascending order (as for the rulebook builds).  Segments are unique
+ *   within an event; where one is duplicated each row counts in the forward and the cell gets the sum of its rows'
+ *   values in row order. */
+size_t wfs_segment_map_loss_workspace_bytes(int64_t n_cap, int32_t planes);
+int wfs_segment_map_loss(const void *map, int32_t map_dtype, int64_t B, int32_t planes, int32_t nx, int32_t ny,
+                         const int32_t *coords, const void *target, int32_t target_dtype, int32_t n_cols,
+                         const int32_t *cols, const float *se_mask, int64_t n_cap, const int64_t *n_dev, int32_t kind,
+                         int32_t max_blocks, void *workspace, size_t workspace_bytes, float *out, int64_t *count,
+                         void *stream);
+int wfs_segment_map_loss_backward(const void *map, int32_t map_dtype, int64_t B, int32_t planes, int32_t nx, int32_t ny,
+                                  const int32_t *coords, const void *target, int32_t target_dtype, int32_t n_cols,
+                                  const int32_t *cols, const float *se_mask, int64_t n_cap, const int64_t *n_dev,
+                                  int32_t kind, const int64_t *count, const float *grad, void *dmap, void *stream);
 int wfs_segq_row_stats(const int32_t *coords, const void *results, int32_t results_dtype, const void *target,
                        int32_t target_dtype, int32_t n_phys, const void *pid, int32_t pid_int64, int64_t n_cap,
                        const int64_t *n_dev, int32_t E, const float *seg_status, int32_t nx, int32_t ny, int32_t e_index,

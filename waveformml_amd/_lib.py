@@ -218,6 +218,11 @@ SIGNATURES = {
                                                   _i32, _vp, _sz, _vp, _vp, _vp]),
     "wfs_masked_regression_loss_backward": (ctypes.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i64,
                                                            _vp, _i32, _vp, _vp, _vp, _vp]),
+    "wfs_segment_map_loss_workspace_bytes": (_sz, [_i64, _i32]),
+    "wfs_segment_map_loss": (ctypes.c_int, [_vp, _i32, _i64, _i32, _i32, _i32, _vp, _vp, _i32, _i32, c_i32p, _vp, _i64, _vp,
+                                            _i32, _i32, _vp, _sz, _vp, _vp, _vp]),
+    "wfs_segment_map_loss_backward": (ctypes.c_int, [_vp, _i32, _i64, _i32, _i32, _i32, _vp, _vp, _i32, _i32, c_i32p, _vp,
+                                                     _i64, _vp, _i32, _vp, _vp, _vp, _vp]),
     "wfs_error_edges": (ctypes.c_int, [_dbl, _i32, ctypes.POINTER(_dbl)]),
     "wfs_segq_row_stats": (ctypes.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _vp, _i32, _i64, _vp, _i32, _vp, _i32, _i32,
                                           _i32, _i32, _i32, _i32] + [_vp] * 11),

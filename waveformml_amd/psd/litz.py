@@ -4,6 +4,11 @@ predicts a dense [B, out, 14, 11] map, the loss compares it with the targets of 
 and the dense target come from ``SparseConvTensor(...).dense()`` (wfs_to_dense) -- with a sum-reduced criterion divided by
 the number of rows (``net_config.SELoss``: of the single-ended segments only, psd/segments.py).
 
+``net_config.fused_segment_loss`` (this project's own key) trains them on the fused HIP segment loss instead
+(spconv.functional.SegmentMapLossFunction, csrc/segmaploss.hip: one launch forward, one backward, no read-back), which
+also takes a capacity-padded batch: with the key the modules train through ``Trainer(capture=True)`` on
+``FlatSGD`` / ``FlatAdam``.  Without it every bit of the mirrored behaviour stays.
+
 Both sit on psd/litbase.LitBase through ``LitSegmentBase``.  The evaluators the reference's ``test_step`` feeds (ZEvaluatorWF, EZEvaluatorWF without a calibration group) are
 psd/segment_evaluator.py, and for ``LitZ`` with phys test targets (``test_has_phys``) psd/real_z_evaluator.py; ``test_step`` leaves what it would hand them in ``last_test_outputs`` and
 psd/evaluate.segment_test_loop does the hand-over.  Their plots and the calibration-database variants are out of scope.
@@ -42,22 +47,58 @@ class LitSegmentBase(LitBase):
     """What LitZ and LitEZ share: LitBase with ``event_predictions=False`` (a sum-reduced criterion) and the segment loss.
     Their evaluators (LitZ.py:43-60, LitEZ.py:24-35, the case without a calibration group) get
     ``config.evaluation_config`` as keyword arguments."""
-    # the optimizer steps model.parameters() even after Trainer.fit has set optimizer_parameters: a gap kept on purpose
-    # (DESIGN.md, "A preserved gap")
+    # without net_config.fused_segment_loss the optimizer steps model.parameters() even after Trainer.fit has set
+    # optimizer_parameters: a gap kept on purpose (DESIGN.md, "A preserved gap")
     flat_optimizer = False
+    FUSED_KEY = "fused_segment_loss"
 
     def __init__(self, config, trial=None):
         super().__init__(config, trial, event_predictions=False)
         if hasattr(config.net_config, "UseFFT"):
             raise NotImplementedError("UseFFT feeds complex features; not on the mirrored path")
+        self.fused_segment_loss = bool(getattr(config.net_config, self.FUSED_KEY, False))
+        self.segment_loss_kind = None
+        if self.fused_segment_loss:
+            from ..spconv import functional as Fsp
+            self.segment_loss_kind = Fsp.segment_loss_kind(self.criterion)
+            if self.segment_loss_kind is None:
+                # no silent fall-back inside a captured step: the composition cannot take its padded batch
+                raise ValueError("net_config.%s covers a sum-reduced plain L1Loss or MSELoss, not %s: remove the key to "
+                                 "train on the torch composition" % (self.FUSED_KEY, type(self.criterion).__name__))
+            # what Trainer.fit and psd/graph.GraphedTrainStep read: one target per row, padded per row; the flat
+            # parameter goes to the optimizer; validation stays on validation_step (dense maps for the evaluators)
+            self.per_row_targets, self.flat_optimizer, self.captured_validation = True, True, False
 
-    @staticmethod
-    def _unpack(batch):
+    def _unpack(self, batch):
         c, f, n_valid, target = LitBase._unpack(batch)
-        if n_valid is not None:
+        if n_valid is not None and not (self.fused_segment_loss and c.is_cuda):
             raise ValueError("LitZ / LitEZ do not take a capacity-padded batch (a valid-row count as third element of "
                              "the inner list): the segment loss reads the batch size back from the host")
-        return c, f, None, target
+        return c, f, n_valid, target
+
+    def _fuses_segment_loss(self, batch):
+        """The training step takes the fused loss: the key is set and the batch lives on the GPU (CPU tensors, the
+        oracle route, keep the composition).  Padded and exact-size batches alike, so that a replay, an eager step
+        beside it and the eager trainer run the same arithmetic."""
+        return self.fused_segment_loss and batch[0][0].is_cuda
+
+    def _dense_maps_need_exact_size(self, n_valid):
+        if n_valid is not None:
+            raise ValueError("LitZ / LitEZ score a capacity-padded batch in training_step only (net_config.%s): the "
+                             "dense maps of validation_step / test_step read the batch size back from the host"
+                             % self.FUSED_KEY)
+
+    def _dense_map(self, c, f):
+        """The net's map for the dense-map route (validation_step, test_step, the composition): over the batch's OWN
+        events, read off its last coordinate row as ``_calc_segment_loss`` reads them -- whatever ``batch_size_hint`` a
+        captured training step has left on the net (its row capacity, psd/graph.GraphedTrainStep)."""
+        return self.model([c, f], batch_size=int(c[-1, -1]) + 1)
+
+    def _fused_segment_loss(self, c, predictions, target, cols, n_valid):
+        """``(total, per_plane)``: plane ``p`` of ``predictions`` against column ``cols[p]`` of ``target``."""
+        from ..spconv import functional as Fsp
+        return Fsp.segment_map_loss(predictions, c, target, cols, self.segment_loss_kind,
+                                    se_mask=self.SE_mask if self.SE_only else None, n_valid=n_valid)
 
     # reference LitBase._calc_segment_loss, :124-174
     def _calc_segment_loss(self, coo, predictions, target, use_float=True, target_index=None, sparse_mask=None):
@@ -97,13 +138,23 @@ class LitZ(LitSegmentBase):
 
     # reference LitZ._process_batch, :89-108
     def _process_batch(self, batch, target_index=None):
-        c, f, additional_fields, _, target = self._inputs(batch)
-        predictions = self.model([c, f])
+        c, f, additional_fields, n_valid, target = self._inputs(batch)
+        self._dense_maps_need_exact_size(n_valid)
+        predictions = self._dense_map(c, f)
         loss, target_tensor, predictions, _ = self._calc_segment_loss(c, predictions, target, target_index=target_index)
         return loss, predictions, target_tensor, c, f, additional_fields
 
+    def _fused_train_loss(self, batch):
+        """The training loss on the fused kernel: one plane against the per-row target."""
+        c, f, _additional, n_valid, target = self._inputs(batch)
+        predictions = self.model([c, f, n_valid] if n_valid is not None else [c, f])
+        return self._fused_segment_loss(c, predictions, target, (0,), n_valid)[0]
+
     def training_step(self, batch, batch_idx):
-        loss = self._process_batch(batch)[0]
+        if self._fuses_segment_loss(batch):
+            loss = self._fused_train_loss(batch)
+        else:
+            loss = self._process_batch(batch)[0]
         self.log("train_loss", loss, on_epoch=True, prog_bar=True, logger=True)
         return loss
 
@@ -149,15 +200,27 @@ class LitEZ(LitSegmentBase):
         self.e_factor = self.escale / self.e_adjust
         self.phys_coord = nc.algorithm == "features"
 
-    def _process_batch(self, batch):
-        c, f, _, target = self._unpack(batch)
+    def _scaled_features(self, f, in_place):
+        """The head of the reference's ``_process_batch``: columns 0, 2 and 3 of physics-coordinate features times
+        ``e_factor``, in place as the reference does it on the dense-map route.  The fused training route scales a COPY
+        (the same products): a captured step's static feature buffer is read again by the warm-up replays with no
+        hand-over in between, and its calibration step runs on the caller's own first batch, which the trainer then
+        trains on -- an in-place factor would compound in both."""
         if self.phys_coord and self.e_factor != 1.:
+            if not in_place:
+                f = f.clone()
             f[:, 0] *= self.e_factor
             f[:, 2] *= self.e_factor
             f[:, 3] *= self.e_factor
         if self.occlude_index:
             f[:, self.occlude_index] = 0
-        predictions = self.model([c, f])
+        return f
+
+    def _process_batch(self, batch):
+        c, f, n_valid, target = self._unpack(batch)
+        self._dense_maps_need_exact_size(n_valid)
+        f = self._scaled_features(f, in_place=True)
+        predictions = self._dense_map(c, f)
         ZLoss, target_z, predictions_z, sparse_mask = self._calc_segment_loss(c, predictions[:, 0].unsqueeze(1),
                                                                               target[:, 0])
         ELoss, target_E, predictions_E, _ = self._calc_segment_loss(c, predictions[:, 1].unsqueeze(1), target[:, 1],
@@ -167,7 +230,14 @@ class LitEZ(LitSegmentBase):
         return c, f, predictions, target_tensor, ZLoss + ELoss, ELoss, ZLoss
 
     def training_step(self, batch, batch_idx):
-        loss = self._process_batch(batch)[4]
+        if self._fuses_segment_loss(batch):
+            # both planes in ONE launch: per_plane = (ZLoss, ELoss), the loss their sum
+            c, f, n_valid, target = self._unpack(batch)
+            f = self._scaled_features(f, in_place=False)
+            predictions = self.model([c, f, n_valid] if n_valid is not None else [c, f])
+            loss = self._fused_segment_loss(c, predictions, target, (0, 1), n_valid)[0]
+        else:
+            loss = self._process_batch(batch)[4]
         self.log("train_loss", loss, on_epoch=True, prog_bar=True, logger=True)
         return loss
 

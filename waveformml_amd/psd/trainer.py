@@ -403,6 +403,8 @@ class Trainer(object):
         for i, batch in enumerate(loader):
             batch = to_device(batch, self.device, self.feature_dtype)
             res = module.validation_step(batch, i)
+            if torch.is_tensor(res):
+                res = {"val_loss": res}                # LitZ returns the bare loss, as the reference's does
             b = batch[1].shape[0]
             tot += float(res["val_loss"]) * b
             # LitWaveform names it val_accuracy (the reference's key), and a regression module has none: NaN

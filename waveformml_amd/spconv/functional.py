@@ -985,16 +985,20 @@ class CrossEntropyMeanFunction(Function):
 _MRL_WORKSPACE = {}
 
 
-def _mrl_workspace(device, n_cap):
-    nbytes = int(_lib.load().wfs_masked_regression_loss_workspace_bytes(int(n_cap)))
+def _zeroed_workspace(device, nbytes):
     key = (device, nbytes)
     if key not in _MRL_WORKSPACE:
         _MRL_WORKSPACE[key] = torch.zeros((nbytes + 7) // 8, dtype=torch.int64, device=device)
     return _MRL_WORKSPACE[key], nbytes
 
 
+def _mrl_workspace(device, n_cap):
+    return _zeroed_workspace(device, int(_lib.load().wfs_masked_regression_loss_workspace_bytes(int(n_cap))))
+
+
 def reset_regression_loss_workspaces():
-    """Zero every cached workspace of the masked regression loss (after a failed or abandoned launch)."""
+    """Zero every cached workspace of the masked regression loss and of the segment map loss (after a failed or
+    abandoned launch)."""
     for work in _MRL_WORKSPACE.values():
         work.zero_()
 
@@ -1088,6 +1092,91 @@ def can_fuse_regression_loss(criterion, pred, target):
 def masked_regression_loss(pred, target, kind, col=0, coords=None, se_mask=None, n_valid=None, max_blocks=0):
     """``(loss, mse)`` of ``MaskedRegressionLossFunction``; ``kind`` from ``regression_loss_kind``."""
     return MaskedRegressionLossFunction.apply(pred, target, col, coords, se_mask, n_valid, kind, max_blocks)
+
+
+class SegmentMapLossFunction(Function):
+    """The segment loss of LitZ / LitEZ (reference LitBase._calc_segment_loss, LitBase.py:124-174) without its dense
+    target and mask maps: ``map`` [B, planes, nx, ny] is scored at the ACTIVE segments only, plane ``p`` against column
+    ``cols[p]`` of ``target`` [N] or [N, n_cols], over the rows below ``n_valid`` whose (x, y, event) lies inside the map
+    and (with ``se_mask``) on a single-ended segment: the sum of |d| / d^2 over those rows divided by their number.  One
+    HIP launch forward, one backward that writes the whole gradient map (csrc/segmaploss.hip).  Returns
+    ``(total, per_plane)``: ``total`` a 0-dim fp32 scalar, the sum of the per-plane losses and the only differentiable
+    output; ``per_plane`` [planes] (LitEZ's ZLoss, ELoss).  Rows that are not counted, and map cells without a counted
+    row, are selected out: whatever they hold the loss stays finite and their gradient is exactly 0.
+
+    The workspace scheme and the ONE-stream precondition are MaskedRegressionLossFunction's."""
+
+    @staticmethod
+    def forward(ctx, map, coords, target, cols, kind, se_mask=None, n_valid=None, max_blocks=0):
+        lib = _lib.load()
+        for t in (map, coords, target):
+            if not t.is_cuda:
+                raise RuntimeError("waveformml_amd: tensor must live on the GPU (there is no CPU path); got %s" % t.device)
+        map, target, coords = map.contiguous(), target.contiguous(), coords.contiguous()
+        n_cap = int(coords.shape[0])
+        if map.dim() != 4 or coords.dtype != torch.int32 or coords.dim() != 2 or coords.shape[1] != 3 or \
+                target.dim() not in (1, 2) or target.shape[0] != n_cap:
+            raise RuntimeError("segment_map_loss: map must be [B, planes, nx, ny], coords int32 [N, 3] = (x, y, event) and "
+                               "target [N] or [N, n_cols], got %s, %s %s and %s"
+                               % (tuple(map.shape), coords.dtype, tuple(coords.shape), tuple(target.shape)))
+        B, planes, nx, ny = (int(v) for v in map.shape)
+        n_cols = int(target.shape[1]) if target.dim() == 2 else 1
+        cols = tuple(int(c) for c in cols)
+        if len(cols) != planes:
+            raise RuntimeError("segment_map_loss: %d planes need %d target columns, got %r" % (planes, planes, cols))
+        if se_mask is not None:
+            se_mask = se_mask.reshape(se_mask.shape[-2:]).contiguous()
+            if se_mask.dtype != torch.float32 or tuple(se_mask.shape) != (nx, ny):
+                raise RuntimeError("segment_map_loss: the mask must be float32 [%d, %d]" % (nx, ny))
+        if n_valid is not None and (n_valid.dtype != torch.int64 or not n_valid.is_cuda):
+            raise RuntimeError("segment_map_loss: n_valid must be a device int64")
+        work, nbytes = _zeroed_workspace(map.device, int(lib.wfs_segment_map_loss_workspace_bytes(n_cap, planes)))
+        out = torch.empty((planes + 1,), dtype=torch.float32, device=map.device)
+        count = torch.empty((1,), dtype=torch.int64, device=map.device)
+        p = _lib.ptr
+        _lib.check(lib.wfs_segment_map_loss(
+            p(map), _lib.dtype_code(map), B, planes, nx, ny, p(coords), p(target), _lib.dtype_code(target), n_cols,
+            _lib.i32_array(cols), p(se_mask), n_cap, p(n_valid), int(kind), int(max_blocks), p(work), nbytes, p(out),
+            p(count), _lib.stream_ptr()))
+        ctx.save_for_backward(map, coords, target, se_mask, n_valid, count)
+        ctx.args = (n_cols, cols, n_cap, int(kind))
+        total, per_plane = out[planes], out[:planes]
+        ctx.mark_non_differentiable(per_plane)
+        ctx.set_materialize_grads(False)            # no zeros-fill for per_plane's gradient on the way back
+        return total, per_plane
+
+    @staticmethod
+    def backward(ctx, grad_total, _grad_planes):
+        if grad_total is None:
+            return (None,) * 8
+        map, coords, target, se_mask, n_valid, count = ctx.saved_tensors
+        n_cols, cols, n_cap, kind = ctx.args
+        B, planes, nx, ny = (int(v) for v in map.shape)
+        grad = grad_total if grad_total.dtype == torch.float32 else grad_total.float()
+        dmap = torch.empty_like(map)
+        p = _lib.ptr
+        _lib.check(_lib.load().wfs_segment_map_loss_backward(
+            p(map), _lib.dtype_code(map), B, planes, nx, ny, p(coords), p(target), _lib.dtype_code(target), n_cols,
+            _lib.i32_array(cols), p(se_mask), n_cap, p(n_valid), kind, p(count), p(grad.contiguous()), p(dmap),
+            _lib.stream_ptr()))
+        return dmap, None, None, None, None, None, None, None
+
+
+def segment_loss_kind(criterion):
+    """WFS_LOSS_L1 / WFS_LOSS_MSE for a SUM-reduced plain nn.L1Loss / nn.MSELoss (what the segment modules build), else
+    None."""
+    if getattr(criterion, "reduction", None) != "sum":
+        return None
+    if type(criterion) is torch.nn.L1Loss:
+        return _lib.WFS_LOSS_L1
+    if type(criterion) is torch.nn.MSELoss:
+        return _lib.WFS_LOSS_MSE
+    return None
+
+
+def segment_map_loss(map, coords, target, cols, kind, se_mask=None, n_valid=None, max_blocks=0):
+    """``(total, per_plane)`` of ``SegmentMapLossFunction``; ``kind`` from ``segment_loss_kind``."""
+    return SegmentMapLossFunction.apply(map, coords, target, cols, kind, se_mask, n_valid, max_blocks)
 
 
 # ``loss.backward()`` makes autograd fill a fresh ones tensor for d loss / d loss (a launch) and the loss node multiply
