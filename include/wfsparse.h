@@ -1070,7 +1070,7 @@ int wfs_tensor_rows(const void *c, int32_t c_int64, int32_t c_cols, const void *
                     const float *results, int64_t N, const int64_t *n_dev, int32_t nx, int32_t ny, float *params,
                     int32_t *category, int64_t *det_tables, int32_t *flags, void *stream);
 
-/* the per-segment regression module: masked loss and the SegEvaluator's rows (csrc/segquant.hip) -----------
+/* the per-segment regression module: masked loss (csrc/segloss.hip) and the SegEvaluator's rows (csrc/segquant.hip)
  * Additions only: WFS_ABI_VERSION stays.
  *
  * wfs_masked_regression_loss (ONE launch on `stream`): the mean of |d| (WFS_LOSS_L1) or d^2 (WFS_LOSS_MSE),
@@ -1118,7 +1118,7 @@ int wfs_masked_regression_loss_backward(const void *pred, int32_t pred_dtype, co
                                         const int64_t *count, const float *grad, void *dpred, void *stream);
 int wfs_error_edges(double max_abs, int32_t n_bins, double *first_last);
 
-/* the segment loss of the dense-map regression modules, LitZ / LitEZ (csrc/segmaploss.hip) ------------------
+/* the segment loss of the dense-map regression modules, LitZ / LitEZ (csrc/segloss.hip) ---------------------
  * Additions only: WFS_ABI_VERSION stays.
  *
  * wfs_segment_map_loss (ONE launch on `stream`): the reference's LitBase._calc_segment_loss for up to 4 planes at once.

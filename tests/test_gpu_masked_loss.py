@@ -1,10 +1,12 @@
-"""GPU checks of the fused masked regression loss (csrc/segquant.hip, spconv.functional.MaskedRegressionLossFunction)
+"""GPU checks of the fused masked regression loss (csrc/segloss.hip, spconv.functional.MaskedRegressionLossFunction)
 against a float64 torch composition over the same counted rows, and of LitSegQuantifier through the captured step.
 
 Bounds: loss and mse within 1e-5 relative (measured near 1e-7: fp64 sums, one rounding to fp32 at the end); dpred of fp32
 rows within 1e-6 of the gradient's scale; dpred of 16-bit rows within one correctly rounded store of the value -- 2^-8
 (bf16) / 2^-11 (fp16) of it, the convention of tests/conv32_cases.py -- on top of that fp32 bar, and for fp16 half the
-spacing of its subnormals (2^-25) where the value lies below its normal range."""
+spacing of its subnormals (2^-25) where the value lies below its normal range.
+
+Row counts: 1, 65, 1000, and 1023 / 1024 / 1025 around the forward's chunk of 1024 rows (csrc/wfs_lossfold.h)."""
 import copy
 import json
 import os
@@ -81,7 +83,7 @@ def _run(pred, target, c, kind, column, mask, n_valid, max_blocks=0, g=1.0):
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16], ids=["f32", "bf16", "f16"])
-@pytest.mark.parametrize("n", [1, 65, 1000])
+@pytest.mark.parametrize("n", [1, 65, 1000, 1023, 1024, 1025])
 @pytest.mark.parametrize("kind", [0, 1], ids=["L1", "MSE"])
 def test_loss_and_gradient_against_the_float64_composition(kind, n, dtype):
     mask = _mask()

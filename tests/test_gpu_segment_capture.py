@@ -1,5 +1,5 @@
 """LitZ and LitEZ through ``Trainer(capture=True)`` with ``net_config.fused_segment_loss`` (psd/litz.py, the fused loss of
-csrc/segmaploss.hip), after test_gpu_masked_loss.test_seg_quantifier_trains_through_the_captured_step: two batches of 44
+csrc/segloss.hip), after test_gpu_masked_loss.test_seg_quantifier_trains_through_the_captured_step: two batches of 44
 and 38 events, SGD with momentum (or Adam) under an ExponentialLR, 3 epochs, three runs from one seed --
 
   key off, eager     torch's optimizer on ``model.parameters()``, the torch composition of the loss

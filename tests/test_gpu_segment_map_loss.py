@@ -1,4 +1,4 @@
-"""GPU checks of the fused segment loss of LitZ / LitEZ (csrc/segmaploss.hip, spconv.functional.SegmentMapLossFunction)
+"""GPU checks of the fused segment loss of LitZ / LitEZ (csrc/segloss.hip, spconv.functional.SegmentMapLossFunction)
 against a float64 torch composition over the same counted rows, and of the two modules with ``net_config.fused_segment_loss``
 against themselves without it.
 
@@ -9,7 +9,10 @@ subnormals (2^-25) where the value lies below its normal range.
 
 Row counts: 1, 65, 1000, and 1023 / 1024 / 1025 around the forward's chunk of 1024 rows; the backward takes 4 events per
 workgroup, so the map's B runs over 1, 3, 4, 5, 8, 9 in a test of its own (B = 1, 3, 5, 9 end in a partial workgroup whose
-span is no multiple of 16 bytes: the element-wise store)."""
+span is no multiple of 16 bytes: the element-wise store).
+
+The forward is the fold of csrc/wfs_lossfold.h that the masked regression loss shares: on an equivalent problem the two
+losses agree bit for bit (a test of its own)."""
 import copy
 
 import numpy as np
@@ -222,6 +225,39 @@ def test_result_repeats_bit_for_bit_and_does_not_depend_on_the_launch_shape(n):
     padded = _run(m2, c2, target2, (4, 2), 1, mask, n - 37)
     assert torch.equal(padded[0], runs[0][0]) and torch.equal(padded[1], runs[0][1])
     assert torch.equal(padded[2][:B], runs[0][2]) and (padded[2][B:] == 0).all().item()
+
+
+@pytest.mark.parametrize("max_blocks", [0, 2])
+@pytest.mark.parametrize("n", [1025, 5000])
+def test_map_loss_and_masked_loss_agree_bit_for_bit_on_an_equivalent_problem(n, max_blocks):
+    """L1, fp32, one plane, ``map[event, 0, x, y] = pred[row]``: the same counted rows, and no product in the term, so
+    both kernels add the same fp64 terms in the same order through the same fold -- loss, count and the gradient at the
+    rows are the same bits.  (MSE is left out: ``d * d`` may be contracted into the sum in one kernel and not in the
+    other.)"""
+    from waveformml_amd.spconv import functional as Fsp
+    rng = np.random.default_rng(n)
+    g = torch.Generator().manual_seed(n)
+    rows, last = _rows(n, rng)
+    c = torch.tensor(rows, dtype=torch.int32).to(DEV)
+    x, y, e = (c[:, k].long() for k in range(3))
+    pred = torch.rand(n, generator=g).to(DEV).requires_grad_(True)
+    target = torch.rand((n, 7), generator=g).to(DEV)
+    m = torch.zeros((last + 1, 1, NX, NY), device=DEV)
+    m[e, 0, x, y] = pred.detach()
+    m.requires_grad_(True)
+    mask = _mask().to(DEV)
+    nv = torch.tensor([n - 37], dtype=torch.int64, device=DEV)   # padding rows behind the valid ones
+    total, _per = Fsp.segment_map_loss(m, c, target, (4,), 0, se_mask=mask, n_valid=nv, max_blocks=max_blocks)
+    loss, _mse = Fsp.masked_regression_loss(pred, target, 0, col=4, coords=c, se_mask=mask, n_valid=nv,
+                                            max_blocks=max_blocks)
+    counts = [int(t.grad_fn.saved_tensors[-1]) for t in (total, loss)]
+    total.backward()
+    loss.backward()
+    assert torch.isfinite(loss).item() and 0 < counts[0] < n - 37
+    assert torch.equal(total.detach().view(torch.int32), loss.detach().view(torch.int32))
+    assert counts[0] == counts[1]
+    assert torch.equal(m.grad[e, 0, x, y].view(torch.int32), pred.grad.view(torch.int32))
+    assert int((pred.grad != 0).sum()) == counts[0]
 
 
 def test_duplicated_segments_count_each_row_and_add_up_in_the_cell():

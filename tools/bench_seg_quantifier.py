@@ -12,7 +12,7 @@ against the torch composition it replaces; no kernel trace:
   add      SegEvaluator.add alone (HIP events around back-to-back calls) at about 770 and 86.5 k rows, with the batch's
            event count (n_events) and without it, and the RealMetricPairTables accumulate it contains alone on the same
            rows
-  loss     forward + backward of spconv.functional.masked_regression_loss (one launch each way) against
+  loss     forward + backward of spconv.functional.masked_regression_loss (csrc/segloss.hip, one launch each way) against
            psd/litsegq.masked_regression_composition over the same masks (single-ended mask, valid-row count, target
            column 4; L1) at 1024 and 86.5 k rows, with the number of kernel launches of each (torch.profiler, one pass)
 

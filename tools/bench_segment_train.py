@@ -1,5 +1,5 @@
 """Cost of the LitZ / LitEZ training step with and without ``net_config.fused_segment_loss`` (psd/litz.py, the fused segment
-loss of csrc/segmaploss.hip), and of the loss alone against the torch composition it replaces
+loss of csrc/segloss.hip), and of the loss alone against the torch composition it replaces
 (LitSegmentBase._calc_segment_loss); configs: config/segment_z.json and config/segment_ez.json (20 samples, 40 channels),
 fp32 rows, synthetic batches of 256 events / about 765 rows and of 28 800 events / about 86.5 k rows:
 

@@ -1,17 +1,24 @@
-// segmaploss.hip -- the segment loss of the per-segment regression modules LitZ / LitEZ (the reference's
-// LitBase._calc_segment_loss) on the device: a dense prediction map [B, planes, nx, ny] scored against the targets of the
-// ACTIVE segments only, sum-reduced criterion divided by the number of rows.
+// segloss.hip -- the two fused regression losses of the captured training step, both on the fold of wfs_lossfold.h (one
+// forward launch, fp64 sums, no floating-point atomic: the result repeats bit for bit and does not depend on the grid).
 //
-// A row of coords = (x, y, event) is COUNTED when it lies below the valid count, inside [nx, ny, B] and (with a mask) on a
-// segment whose mask entry is 1.0.  For a counted row and plane p: d = map[event, p, x, y] - target[row, cols[p]].
+// Masked regression loss (the reference's LitSegQuantifier): the mean of |d| (L1) or d^2 (MSE), d = pred - target[:, col],
+// over the rows below the valid count that lie on a single-ended segment (when a mask is given), with the mean of d^2 over
+// the same rows beside it.
 //
-//   k_sml_forward    ONE launch, the shape of segquant.hip's k_mrl_forward: the rows are cut into chunks of SML_CHUNK by
-//                    row index, whatever the grid; a workgroup sums a chunk in a fixed shape (every thread its rows in
-//                    row order, then a fixed tree) and stores the chunk's per-plane sums and count; the workgroup that
-//                    draws the last ticket folds the chunk sums in chunk order and writes out[0 .. planes - 1] = sum / count,
-//                    out[planes] = their fp64 sum rounded once, and the count.  d and every sum are fp64, there is no
-//                    floating-point atomic: the result repeats bit for bit and does not depend on the grid, the rows'
-//                    capacity (a chunk beyond the valid rows adds an exact 0) or B.
+//   k_mrl_forward    ONE launch: the fold over (sum of terms, sum of squares); writes loss, mse and the count.
+//   k_mrl_backward   ONE launch, one thread per row: dpred = g * s / count in pred's type, s = sign(d) (sign(0) = 0) or 2 d.
+//
+// A row that is not counted is SELECTED out: none of its values is loaded into the arithmetic (beyond the valid count not
+// even its coordinates), so a NaN, an Inf or the captured step's padding value there cannot reach the loss, and its
+// gradient is a stored 0.  With no row counted the loss is NaN (0 / 0, torch's mean over nothing) and dpred is all zeros.
+//
+// Segment map loss (LitZ / LitEZ, the reference's LitBase._calc_segment_loss): a dense prediction map [B, planes, nx, ny]
+// scored against the targets of the ACTIVE segments only, sum-reduced criterion divided by the number of rows.  A row of
+// coords = (x, y, event) is COUNTED when it lies below the valid count, inside [nx, ny, B] and (with a mask) on a segment
+// whose mask entry is 1.0.  For a counted row and plane p: d = map[event, p, x, y] - target[row, cols[p]].
+//
+//   k_sml_forward    ONE launch: the fold over the per-plane sums; writes out[0 .. planes - 1] = sum / count,
+//                    out[planes] = their fp64 sum rounded once, and the count.  The result does not depend on B either.
 //   k_sml_backward   ONE launch that writes ALL of dmap, so nothing clears it first.  A workgroup takes SML_EVENTS
 //                    consecutive events, one wavefront each.  The wavefront finds its event's row range among the valid
 //                    rows by bisection on the event column (rows are grouped by event in ascending order, as the rulebook
@@ -23,19 +30,80 @@
 //                    cell's rows (its first row owns the cell), and only then the owner lane walks the event's rows again
 //                    and sums the cell's values in row order, so the result is deterministic there too.
 //
-// A row that is not counted is SELECTED out: none of its values, and no map cell outside the counted rows, is loaded into
-// the arithmetic (beyond the valid count not even its coordinates).  With no row counted the losses are NaN (0 / 0) and
-// dmap is all zeros.
+// Here too a row that is not counted is selected out, and no map cell outside the counted rows is loaded into the
+// arithmetic.  With no row counted the losses are NaN (0 / 0) and dmap is all zeros.
 #include "wfs_common.h"
-#include "wfs_rows.h"                         // ldt: rows of a runtime dtype
+#include "wfs_lossfold.h"
+#include "wfs_rows.h"                         // ldt / stt: rows of a runtime dtype
 
 namespace {
 
-constexpr int SML_THREADS = 256;
-constexpr int SML_ROWS = 4;                   // rows per thread and chunk
-constexpr int SML_CHUNK = SML_THREADS * SML_ROWS;
-constexpr int SML_MAX_BLOCKS = 256;
-constexpr int SML_HEAD = 16;                  // workspace: the ticket (and padding), then (planes + 1) x 8 bytes per chunk
+// ---- masked regression loss ------------------------------------------------------------------------------------------
+struct MrlIn {
+    const void *pred, *target;
+    const int *coords;
+    const float *mask;                        // [nx, ny] or NULL
+    const long long *n_dev;
+    long long n_cap;
+    int pred_dtype, target_dtype, n_cols, col, nx, ny, kind;
+};
+
+// row r (below the valid count) is counted: on a single-ended segment when there is a mask
+__device__ __forceinline__ bool mrl_counted(const MrlIn &in, long long r) {
+    if (!in.mask) return true;
+    const int x = in.coords[r * 3], y = in.coords[r * 3 + 1];
+    return x >= 0 && x < in.nx && y >= 0 && y < in.ny && in.mask[x * in.ny + y] == 1.0f;
+}
+
+__device__ __forceinline__ double mrl_diff(const MrlIn &in, long long r) {
+    return (double)ldt(in.pred, r, in.pred_dtype) - (double)ldt(in.target, r * in.n_cols + in.col, in.target_dtype);
+}
+
+__global__ void __launch_bounds__(LF_THREADS)
+k_mrl_forward(MrlIn in, long long n_chunks, unsigned *__restrict__ ticket, double *__restrict__ part,
+              float *__restrict__ out, long long *__restrict__ count) {
+    lossfold_forward<2>(
+        2, wfs_valid_rows_nonneg(in.n_cap, in.n_dev), n_chunks, ticket, part,
+        [&](long long r, double *a) {
+            if (!mrl_counted(in, r)) return false;
+            const double d = mrl_diff(in, r);
+            const double q = d * d;           // formed once: both sums take the same rounded product
+            a[0] += in.kind == WFS_LOSS_L1 ? fabs(d) : q;
+            a[1] += q;
+            return true;
+        },
+        [&](const double *a, long long c) {
+            out[0] = (float)(a[0] / (double)c);   // no row counted: 0 / 0 = NaN
+            out[1] = (float)(a[1] / (double)c);
+            *count = c;
+        });
+}
+
+__global__ void __launch_bounds__(LF_THREADS)
+k_mrl_backward(MrlIn in, const long long *__restrict__ count, const float *__restrict__ grad, void *__restrict__ dpred) {
+    const long long r = (long long)blockIdx.x * LF_THREADS + threadIdx.x;
+    if (r >= in.n_cap) return;
+    const long long nv = wfs_valid_rows_nonneg(in.n_cap, in.n_dev), cnt = *count;
+    float v = 0.f;
+    if (cnt > 0 && r < nv && mrl_counted(in, r))
+        v = (float)((double)*grad * lossfold_sign(in.kind, mrl_diff(in, r)) / (double)cnt);
+    stt(dpred, r, in.pred_dtype, v);
+}
+
+bool mrl_args(const void *pred, int32_t pred_dtype, const void *target, int32_t target_dtype, int32_t n_cols, int32_t col,
+              const int32_t *coords, const float *se_mask, int32_t nx, int32_t ny, int64_t n_cap, const int64_t *n_dev,
+              int32_t kind, MrlIn *in) {
+    if (!wfs_dtype_ok(pred_dtype) || !wfs_dtype_ok(target_dtype) || n_cols < 1 || col < 0 || col >= n_cols) return false;
+    if (n_cap < 0 || n_cap >= (1ll << 31) || (kind != WFS_LOSS_L1 && kind != WFS_LOSS_MSE)) return false;
+    if (n_cap > 0 && (!pred || !target)) return false;
+    if (se_mask && (!coords || nx < 1 || ny < 1)) return false;
+    *in = MrlIn{pred, target, coords, se_mask, (const long long *)n_dev, n_cap, pred_dtype, target_dtype, n_cols, col, nx, ny,
+                kind};
+    return true;
+}
+
+// ---- segment map loss ------------------------------------------------------------------------------------------------
+constexpr int SML_THREADS = LF_THREADS;
 constexpr int SML_PLANES = 4;                 // at most
 constexpr int SML_EVENTS = SML_THREADS / WFS_WAVE;   // events per workgroup of the backward launch
 constexpr int SML_CELLS = 256;                // nx * ny at most (14 x 11 = 154)
@@ -65,102 +133,34 @@ __device__ __forceinline__ double sml_diff(const SmlIn &in, long long r, int e, 
     return (double)ldt(in.map, at, in.map_dtype) - (double)ldt(in.target, r * in.n_cols + in.cols[p], in.target_dtype);
 }
 
-// fixed tree over the workgroup's threads; the results are in every thread
-__device__ __forceinline__ void sml_tree(double (*sa)[SML_THREADS], long long *sc, int planes, double *a, long long &c) {
-    const int t = threadIdx.x;
-#pragma unroll
-    for (int p = 0; p < SML_PLANES; ++p)
-        if (p < planes) sa[p][t] = a[p];
-    sc[t] = c;
-    __syncthreads();
-    for (int s = SML_THREADS / 2; s > 0; s >>= 1) {
-        if (t < s) {
-            for (int p = 0; p < planes; ++p) sa[p][t] += sa[p][t + s];
-            sc[t] += sc[t + s];
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int p = 0; p < SML_PLANES; ++p)
-        if (p < planes) a[p] = sa[p][0];
-    c = sc[0];
-    __syncthreads();
-}
-
 __global__ void __launch_bounds__(SML_THREADS)
 k_sml_forward(SmlIn in, long long n_chunks, unsigned *__restrict__ ticket, double *__restrict__ part,
               float *__restrict__ out, long long *__restrict__ count) {
-    __shared__ double sa[SML_PLANES][SML_THREADS];
-    __shared__ long long sc[SML_THREADS];
-    const long long nv = wfs_valid_rows_nonneg(in.n_cap, in.n_dev);
-    const int t = threadIdx.x, planes = in.planes, stride = planes + 1;
-    for (long long ch = blockIdx.x; ch < n_chunks; ch += gridDim.x) {
-        double a[SML_PLANES] = {0.0, 0.0, 0.0, 0.0};
-        long long c = 0;
-#pragma unroll
-        for (int j = 0; j < SML_ROWS; ++j) {
-            const long long r = ch * SML_CHUNK + (long long)j * SML_THREADS + t;
-            if (r >= nv) continue;
+    const int planes = in.planes;
+    lossfold_forward<SML_PLANES>(
+        planes, wfs_valid_rows_nonneg(in.n_cap, in.n_dev), n_chunks, ticket, part,
+        [&](long long r, double *a) {
             int e;
             const int cell = sml_cell(in, r, e);
-            if (cell < 0) continue;
+            if (cell < 0) return false;
+#pragma unroll
+            for (int p = 0; p < SML_PLANES; ++p)
+                if (p < planes) a[p] += lossfold_term(in.kind, sml_diff(in, r, e, cell, p));
+            return true;
+        },
+        [&](const double *a, long long c) {
+            double total = 0.0;
 #pragma unroll
             for (int p = 0; p < SML_PLANES; ++p) {
                 if (p < planes) {
-                    const double d = sml_diff(in, r, e, cell, p);
-                    a[p] += in.kind == WFS_LOSS_L1 ? fabs(d) : d * d;
+                    const double v = a[p] / (double)c;  // no row counted: 0 / 0 = NaN
+                    out[p] = (float)v;
+                    total += v;
                 }
             }
-            ++c;
-        }
-        sml_tree(sa, sc, planes, a, c);
-        if (t == 0) {
-#pragma unroll
-            for (int p = 0; p < SML_PLANES; ++p)
-                if (p < planes) part[ch * stride + p] = a[p];
-            reinterpret_cast<long long *>(part)[ch * stride + planes] = c;
-        }
-    }
-    // hand-off: the chunk stores drain, one agent-scope release, then the ticket
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (t == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const unsigned drawn = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        sc[0] = drawn == gridDim.x - 1 ? 1 : 0;
-        if (sc[0]) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-    }
-    __syncthreads();
-    const bool last = sc[0] != 0;
-    __syncthreads();
-    if (!last) return;
-    double a[SML_PLANES] = {0.0, 0.0, 0.0, 0.0};
-    long long c = 0;
-    for (long long ch = t; ch < n_chunks; ch += SML_THREADS) {
-#pragma unroll
-        for (int p = 0; p < SML_PLANES; ++p)
-            if (p < planes) a[p] += part[ch * stride + p];
-        c += reinterpret_cast<const long long *>(part)[ch * stride + planes];
-    }
-    sml_tree(sa, sc, planes, a, c);
-    if (t == 0) {
-        double total = 0.0;
-#pragma unroll
-        for (int p = 0; p < SML_PLANES; ++p) {
-            if (p < planes) {
-                const double v = a[p] / (double)c;  // no row counted: 0 / 0 = NaN
-                out[p] = (float)v;
-                total += v;
-            }
-        }
-        out[planes] = (float)total;
-        *count = c;
-        __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+            out[planes] = (float)total;
+            *count = c;
+        });
 }
 
 // the first row at or above `from` (below nv) whose event is >= e; every lane of the wavefront walks the same path
@@ -175,9 +175,7 @@ __device__ __forceinline__ long long sml_lower(const int *coords, long long from
 
 // the value a counted row leaves in its cell of plane p
 __device__ __forceinline__ float sml_grad(const SmlIn &in, long long r, int e, int cell, int p, double g_over_count) {
-    const double d = sml_diff(in, r, e, cell, p);
-    const double s = in.kind == WFS_LOSS_L1 ? (d > 0.0 ? 1.0 : (d < 0.0 ? -1.0 : (d == d ? 0.0 : d))) : 2.0 * d;
-    return (float)(g_over_count * s);
+    return (float)(g_over_count * lossfold_sign(in.kind, sml_diff(in, r, e, cell, p)));
 }
 
 // T: the map's element type.  The tile is laid out as dmap is: [event of the workgroup][plane][cell].
@@ -282,9 +280,53 @@ bool sml_args(const void *map, int32_t map_dtype, int64_t B, int32_t planes, int
 
 }  // namespace
 
+extern "C" size_t wfs_masked_regression_loss_workspace_bytes(int64_t n_cap) {
+    return n_cap < 0 ? 0 : lossfold_workspace_bytes(n_cap, 2);
+}
+
+#define MRL_ARGS_MESSAGE(name)                                                                                        \
+    name ": dtypes %d / %d, column %d of %d, n_cap = %lld, kind %d, mask %d x %d", pred_dtype, target_dtype, col, n_cols, \
+        (long long)n_cap, kind, nx, ny
+
+extern "C" int wfs_masked_regression_loss(const void *pred, int32_t pred_dtype, const void *target, int32_t target_dtype,
+                                          int32_t n_cols, int32_t col, const int32_t *coords, const float *se_mask,
+                                          int32_t nx, int32_t ny, int64_t n_cap, const int64_t *n_dev, int32_t kind,
+                                          int32_t max_blocks, void *workspace, size_t workspace_bytes, float *out,
+                                          int64_t *count, void *stream) {
+    MrlIn in;
+    WFS_REQUIRE(mrl_args(pred, pred_dtype, target, target_dtype, n_cols, col, coords, se_mask, nx, ny, n_cap, n_dev, kind,
+                         &in),
+                WFS_EINVAL, MRL_ARGS_MESSAGE("wfs_masked_regression_loss"));
+    WFS_REQUIRE(workspace && out && count && max_blocks >= 0, WFS_EINVAL, "wfs_masked_regression_loss: NULL argument");
+    WFS_REQUIRE(workspace_bytes >= wfs_masked_regression_loss_workspace_bytes(n_cap), WFS_EWORKSPACE,
+                "wfs_masked_regression_loss: workspace of %zu bytes, %zu needed", workspace_bytes,
+                wfs_masked_regression_loss_workspace_bytes(n_cap));
+    const LossfoldGrid g = lossfold_grid(n_cap, max_blocks);
+    k_mrl_forward<<<g.blocks, LF_THREADS, 0, (hipStream_t)stream>>>(
+        in, g.n_chunks, (unsigned *)workspace, (double *)((char *)workspace + LF_HEAD), out, (long long *)count);
+    WFS_LAUNCH_CHECK();
+    return WFS_OK;
+}
+
+extern "C" int wfs_masked_regression_loss_backward(const void *pred, int32_t pred_dtype, const void *target,
+                                                   int32_t target_dtype, int32_t n_cols, int32_t col,
+                                                   const int32_t *coords, const float *se_mask, int32_t nx, int32_t ny,
+                                                   int64_t n_cap, const int64_t *n_dev, int32_t kind,
+                                                   const int64_t *count, const float *grad, void *dpred, void *stream) {
+    MrlIn in;
+    WFS_REQUIRE(mrl_args(pred, pred_dtype, target, target_dtype, n_cols, col, coords, se_mask, nx, ny, n_cap, n_dev, kind,
+                         &in),
+                WFS_EINVAL, MRL_ARGS_MESSAGE("wfs_masked_regression_loss_backward"));
+    WFS_REQUIRE(count && grad && (n_cap == 0 || dpred), WFS_EINVAL, "wfs_masked_regression_loss_backward: NULL argument");
+    if (n_cap == 0) return WFS_OK;
+    k_mrl_backward<<<(unsigned)wfs_cdiv(n_cap, LF_THREADS), LF_THREADS, 0, (hipStream_t)stream>>>(
+        in, (const long long *)count, grad, dpred);
+    WFS_LAUNCH_CHECK();
+    return WFS_OK;
+}
+
 extern "C" size_t wfs_segment_map_loss_workspace_bytes(int64_t n_cap, int32_t planes) {
-    if (n_cap < 0 || planes < 1 || planes > SML_PLANES) return 0;
-    return (size_t)SML_HEAD + (size_t)(n_cap > 0 ? wfs_cdiv(n_cap, SML_CHUNK) : 1) * (planes + 1) * sizeof(double);
+    return n_cap < 0 || planes < 1 || planes > SML_PLANES ? 0 : lossfold_workspace_bytes(n_cap, planes);
 }
 
 #define SML_ARGS_MESSAGE(name)                                                                                    \
@@ -304,12 +346,9 @@ extern "C" int wfs_segment_map_loss(const void *map, int32_t map_dtype, int64_t 
     WFS_REQUIRE(workspace_bytes >= wfs_segment_map_loss_workspace_bytes(n_cap, planes), WFS_EWORKSPACE,
                 "wfs_segment_map_loss: workspace of %zu bytes, %zu needed", workspace_bytes,
                 wfs_segment_map_loss_workspace_bytes(n_cap, planes));
-    const long long n_chunks = wfs_cdiv(n_cap, SML_CHUNK);       // 0 rows: no chunk, the fold writes NaN and count 0
-    long long blocks = n_chunks < 1 ? 1 : n_chunks;
-    const long long cap = max_blocks > 0 ? max_blocks : SML_MAX_BLOCKS;
-    if (blocks > cap) blocks = cap;
-    k_sml_forward<<<(unsigned)blocks, SML_THREADS, 0, (hipStream_t)stream>>>(
-        in, n_chunks, (unsigned *)workspace, (double *)((char *)workspace + SML_HEAD), out, (long long *)count);
+    const LossfoldGrid g = lossfold_grid(n_cap, max_blocks);
+    k_sml_forward<<<g.blocks, SML_THREADS, 0, (hipStream_t)stream>>>(
+        in, g.n_chunks, (unsigned *)workspace, (double *)((char *)workspace + LF_HEAD), out, (long long *)count);
     WFS_LAUNCH_CHECK();
     return WFS_OK;
 }

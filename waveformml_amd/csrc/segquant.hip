@@ -1,23 +1,6 @@
-// segquant.hip -- the per-segment regression module (the reference's LitSegQuantifier) on the device: its masked loss for
-// the training step, and the per-row half of its evaluator (src/evaluation/SegEvaluator.py with StatsUtils.ErrorAggregator).
-//
-// Masked regression loss: the mean of |d| (L1) or d^2 (MSE), d = pred - target[:, col], over the rows below the valid
-// count that lie on a single-ended segment (when a mask is given), with the mean of d^2 over the same rows beside it.
-//
-//   k_mrl_forward    ONE launch.  The rows are cut into chunks of MRL_CHUNK by row index, whatever the grid: a workgroup
-//                    sums a chunk in a fixed shape (every thread its MRL_CHUNK / MRL_THREADS rows in row order, then a
-//                    fixed tree over the threads) and stores the chunk's (count, sum, sum of squares).  The workgroup that
-//                    draws the last ticket folds the chunk sums -- every thread its chunks in chunk order, then the same
-//                    tree -- and writes count, loss and mse.  d and every sum are fp64; there is no floating-point atomic,
-//                    so the result repeats bit for bit and does not depend on the grid (nor on the rows' capacity: a chunk
-//                    beyond the valid rows adds an exact 0).  The hand-off is one agent-scope release in each workgroup
-//                    (after its chunk stores have drained) in front of a relaxed ticket add, and one agent-scope acquire in
-//                    the last one; the last one puts the ticket back to 0.
-//   k_mrl_backward   ONE launch, one thread per row: dpred = g * s / count in pred's type, s = sign(d) (sign(0) = 0) or 2 d.
-//
-// A row that is not counted is SELECTED out: none of its values is loaded into the arithmetic (beyond the valid count not
-// even its coordinates), so a NaN, an Inf or the captured step's padding value there cannot reach the loss, and its
-// gradient is a stored 0.  With no row counted the loss is NaN (0 / 0, torch's mean over nothing) and dpred is all zeros.
+// segquant.hip -- the per-row half of the evaluator of the per-segment regression module (the reference's
+// LitSegQuantifier: src/evaluation/SegEvaluator.py with StatsUtils.ErrorAggregator) on the device.  The module's masked
+// loss for the training step is in segloss.hip.
 //
 // Evaluator (SegEvaluator.add): after the event offsets of wfs_evoffsets.h,
 //   k_segq_rows      one thread per row: error = results - target[:, ti] in fp64, mae = |error|, multiplicity (the length of
@@ -35,7 +18,7 @@
 //                    through bin_direct (wfs_evalbins.h) as int64 counts.
 #include "wfs_common.h"
 #include "wfs_erroredges.h"
-#include "wfs_rows.h"                         // ldt / stt: rows of a runtime dtype
+#include "wfs_rows.h"                         // ldt: rows of a runtime dtype
 
 namespace {
 
@@ -44,130 +27,8 @@ namespace {
 #include "wfs_evalbins.h"
 
 constexpr int MB = WFS_EVOFF_THREADS;
-constexpr int MRL_THREADS = 256;
-constexpr int MRL_ROWS = 4;                   // rows per thread and chunk
-constexpr int MRL_CHUNK = MRL_THREADS * MRL_ROWS;
-constexpr int MRL_MAX_BLOCKS = 256;
-constexpr int MRL_HEAD = 16;                  // workspace: the ticket (and padding), then 3 x 8 bytes per chunk
 constexpr int SEGQ_SLOTS = 6, SEGQ_CLASSES = 5;
 
-struct MrlIn {
-    const void *pred, *target;
-    const int *coords;
-    const float *mask;                        // [nx, ny] or NULL
-    const long long *n_dev;
-    long long n_cap;
-    int pred_dtype, target_dtype, n_cols, col, nx, ny, kind;
-};
-
-// row r (below the valid count) is counted: on a single-ended segment when there is a mask
-__device__ __forceinline__ bool mrl_counted(const MrlIn &in, long long r) {
-    if (!in.mask) return true;
-    const int x = in.coords[r * 3], y = in.coords[r * 3 + 1];
-    return x >= 0 && x < in.nx && y >= 0 && y < in.ny && in.mask[x * in.ny + y] == 1.0f;
-}
-
-// fixed tree over the workgroup's threads; the result is in thread 0
-__device__ __forceinline__ void mrl_tree(double *sa, double *sb, long long *sc, double &a, double &b, long long &c) {
-    const int t = threadIdx.x;
-    sa[t] = a, sb[t] = b, sc[t] = c;
-    __syncthreads();
-    for (int s = MRL_THREADS / 2; s > 0; s >>= 1) {
-        if (t < s) sa[t] += sa[t + s], sb[t] += sb[t + s], sc[t] += sc[t + s];
-        __syncthreads();
-    }
-    a = sa[0], b = sb[0], c = sc[0];
-    __syncthreads();
-}
-
-__global__ void __launch_bounds__(MRL_THREADS)
-k_mrl_forward(MrlIn in, long long n_chunks, unsigned *__restrict__ ticket, double *__restrict__ part,
-              float *__restrict__ out, long long *__restrict__ count) {
-    __shared__ double sa[MRL_THREADS], sb[MRL_THREADS];
-    __shared__ long long sc[MRL_THREADS];
-    const long long nv = wfs_valid_rows_nonneg(in.n_cap, in.n_dev);
-    const int t = threadIdx.x;
-    for (long long ch = blockIdx.x; ch < n_chunks; ch += gridDim.x) {
-        double a = 0.0, b = 0.0;
-        long long c = 0;
-#pragma unroll
-        for (int j = 0; j < MRL_ROWS; ++j) {
-            const long long r = ch * MRL_CHUNK + (long long)j * MRL_THREADS + t;
-            if (r < nv && mrl_counted(in, r)) {
-                const double d = (double)ldt(in.pred, r, in.pred_dtype) -
-                                 (double)ldt(in.target, r * in.n_cols + in.col, in.target_dtype);
-                const double q = d * d;
-                a += in.kind == WFS_LOSS_L1 ? fabs(d) : q;
-                b += q;
-                ++c;
-            }
-        }
-        mrl_tree(sa, sb, sc, a, b, c);
-        if (t == 0) {
-            part[ch * 3] = a, part[ch * 3 + 1] = b;
-            reinterpret_cast<long long *>(part)[ch * 3 + 2] = c;
-        }
-    }
-    // hand-off: the chunk stores drain, one agent-scope release, then the ticket
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (t == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const unsigned drawn = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        sc[0] = drawn == gridDim.x - 1 ? 1 : 0;
-        if (sc[0]) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-    }
-    __syncthreads();
-    const bool last = sc[0] != 0;
-    __syncthreads();
-    if (!last) return;
-    double a = 0.0, b = 0.0;
-    long long c = 0;
-    for (long long ch = t; ch < n_chunks; ch += MRL_THREADS) {
-        a += part[ch * 3], b += part[ch * 3 + 1];
-        c += reinterpret_cast<const long long *>(part)[ch * 3 + 2];
-    }
-    mrl_tree(sa, sb, sc, a, b, c);
-    if (t == 0) {
-        out[0] = (float)(a / (double)c);      // no row counted: 0 / 0 = NaN
-        out[1] = (float)(b / (double)c);
-        *count = c;
-        __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-}
-
-__global__ void __launch_bounds__(MRL_THREADS)
-k_mrl_backward(MrlIn in, const long long *__restrict__ count, const float *__restrict__ grad, void *__restrict__ dpred) {
-    const long long r = (long long)blockIdx.x * MRL_THREADS + threadIdx.x;
-    if (r >= in.n_cap) return;
-    const long long nv = wfs_valid_rows_nonneg(in.n_cap, in.n_dev), cnt = *count;
-    float v = 0.f;
-    if (cnt > 0 && r < nv && mrl_counted(in, r)) {
-        const double d = (double)ldt(in.pred, r, in.pred_dtype) -
-                         (double)ldt(in.target, r * in.n_cols + in.col, in.target_dtype);
-        const double s = in.kind == WFS_LOSS_L1 ? (d > 0.0 ? 1.0 : (d < 0.0 ? -1.0 : (d == d ? 0.0 : d))) : 2.0 * d;
-        v = (float)((double)*grad * s / (double)cnt);
-    }
-    stt(dpred, r, in.pred_dtype, v);
-}
-
-bool mrl_args(const void *pred, int32_t pred_dtype, const void *target, int32_t target_dtype, int32_t n_cols, int32_t col,
-              const int32_t *coords, const float *se_mask, int32_t nx, int32_t ny, int64_t n_cap, const int64_t *n_dev,
-              int32_t kind, MrlIn *in) {
-    if (!wfs_dtype_ok(pred_dtype) || !wfs_dtype_ok(target_dtype) || n_cols < 1 || col < 0 || col >= n_cols) return false;
-    if (n_cap < 0 || n_cap >= (1ll << 31) || (kind != WFS_LOSS_L1 && kind != WFS_LOSS_MSE)) return false;
-    if (n_cap > 0 && (!pred || !target)) return false;
-    if (se_mask && (!coords || nx < 1 || ny < 1)) return false;
-    *in = MrlIn{pred, target, coords, se_mask, (const long long *)n_dev, n_cap, pred_dtype, target_dtype, n_cols, col, nx, ny,
-                kind};
-    return true;
-}
-
-// ---- evaluator -------------------------------------------------------------------------------------------------------
 struct SegqPlan {
     int nx, ny, n_phys, e_index, psd_index, z_index, t_index, has_pid, pid_int64;
 };
@@ -271,54 +132,6 @@ k_segq_bins(const void *__restrict__ results, int r_dtype, const void *__restric
 }
 
 }  // namespace
-
-extern "C" size_t wfs_masked_regression_loss_workspace_bytes(int64_t n_cap) {
-    if (n_cap < 0) return 0;
-    return (size_t)MRL_HEAD + (size_t)(n_cap > 0 ? wfs_cdiv(n_cap, MRL_CHUNK) : 1) * 3 * sizeof(double);
-}
-
-extern "C" int wfs_masked_regression_loss(const void *pred, int32_t pred_dtype, const void *target, int32_t target_dtype,
-                                          int32_t n_cols, int32_t col, const int32_t *coords, const float *se_mask,
-                                          int32_t nx, int32_t ny, int64_t n_cap, const int64_t *n_dev, int32_t kind,
-                                          int32_t max_blocks, void *workspace, size_t workspace_bytes, float *out,
-                                          int64_t *count, void *stream) {
-    MrlIn in;
-    WFS_REQUIRE(mrl_args(pred, pred_dtype, target, target_dtype, n_cols, col, coords, se_mask, nx, ny, n_cap, n_dev, kind,
-                         &in),
-                WFS_EINVAL, "wfs_masked_regression_loss: dtypes %d / %d, column %d of %d, n_cap = %lld, kind %d, mask %d x %d",
-                pred_dtype, target_dtype, col, n_cols, (long long)n_cap, kind, nx, ny);
-    WFS_REQUIRE(workspace && out && count && max_blocks >= 0, WFS_EINVAL, "wfs_masked_regression_loss: NULL argument");
-    WFS_REQUIRE(workspace_bytes >= wfs_masked_regression_loss_workspace_bytes(n_cap), WFS_EWORKSPACE,
-                "wfs_masked_regression_loss: workspace of %zu bytes, %zu needed", workspace_bytes,
-                wfs_masked_regression_loss_workspace_bytes(n_cap));
-    const long long n_chunks = wfs_cdiv(n_cap, MRL_CHUNK);       // 0 rows: no chunk, the fold writes NaN and count 0
-    long long blocks = n_chunks < 1 ? 1 : n_chunks;
-    const long long cap = max_blocks > 0 ? max_blocks : MRL_MAX_BLOCKS;
-    if (blocks > cap) blocks = cap;
-    k_mrl_forward<<<(unsigned)blocks, MRL_THREADS, 0, (hipStream_t)stream>>>(
-        in, n_chunks, (unsigned *)workspace, (double *)((char *)workspace + MRL_HEAD), out, (long long *)count);
-    WFS_LAUNCH_CHECK();
-    return WFS_OK;
-}
-
-extern "C" int wfs_masked_regression_loss_backward(const void *pred, int32_t pred_dtype, const void *target,
-                                                   int32_t target_dtype, int32_t n_cols, int32_t col,
-                                                   const int32_t *coords, const float *se_mask, int32_t nx, int32_t ny,
-                                                   int64_t n_cap, const int64_t *n_dev, int32_t kind,
-                                                   const int64_t *count, const float *grad, void *dpred, void *stream) {
-    MrlIn in;
-    WFS_REQUIRE(mrl_args(pred, pred_dtype, target, target_dtype, n_cols, col, coords, se_mask, nx, ny, n_cap, n_dev, kind,
-                         &in),
-                WFS_EINVAL,
-                "wfs_masked_regression_loss_backward: dtypes %d / %d, column %d of %d, n_cap = %lld, kind %d, mask %d x %d",
-                pred_dtype, target_dtype, col, n_cols, (long long)n_cap, kind, nx, ny);
-    WFS_REQUIRE(count && grad && (n_cap == 0 || dpred), WFS_EINVAL, "wfs_masked_regression_loss_backward: NULL argument");
-    if (n_cap == 0) return WFS_OK;
-    k_mrl_backward<<<(unsigned)wfs_cdiv(n_cap, MRL_THREADS), MRL_THREADS, 0, (hipStream_t)stream>>>(
-        in, (const long long *)count, grad, dpred);
-    WFS_LAUNCH_CHECK();
-    return WFS_OK;
-}
 
 extern "C" int wfs_error_edges(double max_abs, int32_t n_bins, double *first_last) {
     WFS_REQUIRE(first_last && n_bins >= 1, WFS_EINVAL, "wfs_error_edges: NULL argument or n_bins = %d", n_bins);

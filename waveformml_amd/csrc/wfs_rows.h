@@ -1,5 +1,5 @@
 // wfs_rows.h -- what the row-wise waveform front ends (tcn.hip, tcnc.hip, rnn.hip) share: the dropout generator, rows of a
-// runtime dtype (ldt / stt, also segquant.hip's), the dropout argument check, the dW pass's block count and the TCNs' record of parameter addresses.
+// runtime dtype (ldt / stt, also segquant.hip's and segloss.hip's), the dropout argument check, the dW pass's block count and the TCNs' record of parameter addresses.
 #pragma once
 #include "wfs_common.h"
 

@@ -6,7 +6,7 @@
 logged beside it (``val_mse`` / ``test_mse``; the reference's torchmetrics ``MeanSquaredError`` per step).
 
 The loss.  A mean-reduced ``L1Loss`` / ``MSELoss`` on the GPU is one HIP launch forward and one backward
-(spconv.functional.MaskedRegressionLossFunction, csrc/segquant.hip): the single-ended mask, the target column and the
+(spconv.functional.MaskedRegressionLossFunction, csrc/segloss.hip): the single-ended mask, the target column and the
 valid-row count of a captured step (psd/graph.GraphedTrainStep, ``per_row_targets``: rows and targets padded to a
 capacity, the padding targets hold the captured step's fill value) are applied inside the kernel, which selects the
 rows that do not count OUT, so whatever they hold the loss stays finite and their gradient is exactly 0.  Any other

@@ -5,7 +5,7 @@ and the dense target come from ``SparseConvTensor(...).dense()`` (wfs_to_dense) 
 the number of rows (``net_config.SELoss``: of the single-ended segments only, psd/segments.py).
 
 ``net_config.fused_segment_loss`` (this project's own key) trains them on the fused HIP segment loss instead
-(spconv.functional.SegmentMapLossFunction, csrc/segmaploss.hip: one launch forward, one backward, no read-back), which
+(spconv.functional.SegmentMapLossFunction, csrc/segloss.hip: one launch forward, one backward, no read-back), which
 also takes a capacity-padded batch: with the key the modules train through ``Trainer(capture=True)`` on
 ``FlatSGD`` / ``FlatAdam``.  Without it every bit of the mirrored behaviour stays.
 

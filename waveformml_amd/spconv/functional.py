@@ -979,35 +979,73 @@ class CrossEntropyMeanFunction(Function):
         return ctx.dlogits * grad_output, None, None
 
 
-# zero-initialised workspaces of the masked regression loss, one per device and size: the kernel's ticket word must be 0
-# before the first launch and every launch leaves it 0, so a buffer is zeroed once and reused (a captured step bakes its
-# address into the graph; the entry is never freed).  One stream at a time per device, as everything in this module.
-_MRL_WORKSPACE = {}
-
-
-def _zeroed_workspace(device, nbytes):
-    key = (device, nbytes)
-    if key not in _MRL_WORKSPACE:
-        _MRL_WORKSPACE[key] = torch.zeros((nbytes + 7) // 8, dtype=torch.int64, device=device)
-    return _MRL_WORKSPACE[key], nbytes
-
-
-def _mrl_workspace(device, n_cap):
-    return _zeroed_workspace(device, int(_lib.load().wfs_masked_regression_loss_workspace_bytes(int(n_cap))))
+# zero-initialised workspaces of the two fused regression losses (the fold of csrc/wfs_lossfold.h), one per device and size:
+# the kernel's ticket word must be 0 before the first launch and every launch leaves it 0, so a buffer is zeroed once and
+# reused (a captured step bakes its address into the graph; the entry is never freed).  One stream at a time per device, as
+# everything in this module.
+_LOSS_WORKSPACE = {}
 
 
 def reset_regression_loss_workspaces():
     """Zero every cached workspace of the masked regression loss and of the segment map loss (after a failed or
     abandoned launch)."""
-    for work in _MRL_WORKSPACE.values():
+    for work in _LOSS_WORKSPACE.values():
         work.zero_()
+
+
+def _coords_ok(coords, n_cap):
+    return coords is not None and coords.dtype == torch.int32 and coords.dim() == 2 and coords.shape[1] == 3 and \
+        coords.shape[0] == n_cap
+
+
+def _loss_checks(name, tensors, shapes, target, n_cap, se_mask, mask_shape, n_valid):
+    """The argument checks of the two fused losses, in the order both had them: ``tensors`` on the GPU, the loss's own
+    ``shapes`` -- (ok, text) pairs, the first with ``target`` [N] or [N, n_cols] -- the mask as a contiguous float32
+    [nx, ny] (of ``mask_shape`` when that is given) and ``n_valid`` a device int64.  Returns ``(n_cols, se_mask)``."""
+    for t in tensors:
+        if not t.is_cuda:
+            raise RuntimeError("waveformml_amd: tensor must live on the GPU (there is no CPU path); got %s" % t.device)
+    target_ok = target.dim() in (1, 2) and target.shape[0] == n_cap
+    for k, (ok, text) in enumerate(shapes):
+        if not (ok and (k > 0 or target_ok)):
+            raise RuntimeError("%s: %s" % (name, text))
+    if se_mask is not None:
+        se_mask = se_mask.reshape(se_mask.shape[-2:]).contiguous()
+        if se_mask.dtype != torch.float32 or (mask_shape is not None and tuple(se_mask.shape) != mask_shape):
+            raise RuntimeError("%s: the mask must be float32%s" % (name, " [%d, %d]" % mask_shape if mask_shape else ""))
+    if n_valid is not None and (n_valid.dtype != torch.int64 or not n_valid.is_cuda):
+        raise RuntimeError("%s: n_valid must be a device int64" % name)
+    return (int(target.shape[1]) if target.dim() == 2 else 1), se_mask
+
+
+def _loss_buffers(device, nbytes, n_out):
+    """The cached zeroed workspace of ``nbytes`` with its size, and fresh ``out`` fp32 [n_out] and ``count`` int64 [1]."""
+    key = (device, nbytes)
+    if key not in _LOSS_WORKSPACE:
+        _LOSS_WORKSPACE[key] = torch.zeros((nbytes + 7) // 8, dtype=torch.int64, device=device)
+    return (_LOSS_WORKSPACE[key], nbytes, torch.empty((n_out,), dtype=torch.float32, device=device),
+            torch.empty((1,), dtype=torch.int64, device=device))
+
+
+def _loss_grad(grad):
+    return (grad if grad.dtype == torch.float32 else grad.float()).contiguous()
+
+
+def _loss_kind(criterion, reduction):
+    if getattr(criterion, "reduction", None) != reduction:
+        return None
+    if type(criterion) is torch.nn.L1Loss:
+        return _lib.WFS_LOSS_L1
+    if type(criterion) is torch.nn.MSELoss:
+        return _lib.WFS_LOSS_MSE
+    return None
 
 
 class MaskedRegressionLossFunction(Function):
     """Mean-reduced nn.L1Loss / nn.MSELoss of ``pred`` [N] against ``target`` [N] or column ``col`` of ``target``
     [N, n_cols] over the rows below ``n_valid`` that lie on a single-ended segment (``se_mask`` [nx, ny] == 1.0 at the
     row's (x, y)): the reference's ``criterion(predictions[se_inds], target[se_inds, target_index])``
-    (src/engineering/LitSegQuantifier.py) with a static shape.  One HIP launch forward, one backward (csrc/segquant.hip);
+    (src/engineering/LitSegQuantifier.py) with a static shape.  One HIP launch forward, one backward (csrc/segloss.hip);
     returns ``(loss, mse)``, fp32 scalars, ``mse`` = the mean of d^2 over the same rows whatever the kind (no gradient).
     Rows that are not counted are selected out: whatever they hold, the loss stays finite and their gradient is 0.
 
@@ -1021,38 +1059,25 @@ class MaskedRegressionLossFunction(Function):
     @staticmethod
     def forward(ctx, pred, target, col, coords, se_mask, n_valid, kind, max_blocks=0):
         lib = _lib.load()
-        for t in (pred, target):
-            if not t.is_cuda:
-                raise RuntimeError("waveformml_amd: tensor must live on the GPU (there is no CPU path); got %s" % t.device)
-        pred, target = pred.contiguous(), target.contiguous()
         n_cap = int(pred.shape[0])
-        if pred.dim() != 1 or target.dim() not in (1, 2) or target.shape[0] != n_cap:
-            raise RuntimeError("masked_regression_loss: pred must be [N] and target [N] or [N, n_cols], got %s and %s"
-                               % (tuple(pred.shape), tuple(target.shape)))
-        n_cols = int(target.shape[1]) if target.dim() == 2 else 1
+        n_cols, mask = _loss_checks(
+            "masked_regression_loss", (pred, target),
+            ((pred.dim() == 1, "pred must be [N] and target [N] or [N, n_cols], got %s and %s"
+              % (tuple(pred.shape), tuple(target.shape))),
+             (se_mask is None or _coords_ok(coords, n_cap), "a mask needs coords int32 [N, 3] = (x, y, event)")),
+            target, n_cap, se_mask, None, n_valid)
+        pred, target = pred.contiguous(), target.contiguous()
         col = int(col) if target.dim() == 2 else 0
         nx = ny = 0
-        if se_mask is not None:
-            if coords is None or coords.dtype != torch.int32 or coords.dim() != 2 or coords.shape[1] != 3 or \
-                    coords.shape[0] != n_cap:
-                raise RuntimeError("masked_regression_loss: a mask needs coords int32 [N, 3] = (x, y, event)")
-            se_mask = se_mask.reshape(se_mask.shape[-2:]).contiguous()
-            if se_mask.dtype != torch.float32:
-                raise RuntimeError("masked_regression_loss: the mask must be float32")
-            nx, ny = int(se_mask.shape[0]), int(se_mask.shape[1])
-            coords = coords.contiguous()
-        else:
-            coords = None
-        if n_valid is not None and (n_valid.dtype != torch.int64 or not n_valid.is_cuda):
-            raise RuntimeError("masked_regression_loss: n_valid must be a device int64")
-        work, nbytes = _mrl_workspace(pred.device, n_cap)
-        out = torch.empty((2,), dtype=torch.float32, device=pred.device)
-        count = torch.empty((1,), dtype=torch.int64, device=pred.device)
+        if mask is not None:
+            nx, ny = int(mask.shape[0]), int(mask.shape[1])
+        coords = coords.contiguous() if mask is not None else None
+        work, nbytes, out, count = _loss_buffers(pred.device, int(lib.wfs_masked_regression_loss_workspace_bytes(n_cap)), 2)
         p = _lib.ptr
         _lib.check(lib.wfs_masked_regression_loss(
-            p(pred), _lib.dtype_code(pred), p(target), _lib.dtype_code(target), n_cols, col, p(coords), p(se_mask), nx, ny,
+            p(pred), _lib.dtype_code(pred), p(target), _lib.dtype_code(target), n_cols, col, p(coords), p(mask), nx, ny,
             n_cap, p(n_valid), int(kind), int(max_blocks), p(work), nbytes, p(out), p(count), _lib.stream_ptr()))
-        ctx.save_for_backward(pred, target, coords, se_mask, n_valid, count)
+        ctx.save_for_backward(pred, target, coords, mask, n_valid, count)
         ctx.args = (n_cols, col, nx, ny, n_cap, int(kind))
         loss, mse = out[0], out[1]
         ctx.mark_non_differentiable(mse)
@@ -1062,24 +1087,17 @@ class MaskedRegressionLossFunction(Function):
     def backward(ctx, grad_loss, _grad_mse):
         pred, target, coords, se_mask, n_valid, count = ctx.saved_tensors
         n_cols, col, nx, ny, n_cap, kind = ctx.args
-        grad = grad_loss if grad_loss.dtype == torch.float32 else grad_loss.float()
         dpred = torch.empty_like(pred)
         p = _lib.ptr
         _lib.check(_lib.load().wfs_masked_regression_loss_backward(
             p(pred), _lib.dtype_code(pred), p(target), _lib.dtype_code(target), n_cols, col, p(coords), p(se_mask), nx, ny,
-            n_cap, p(n_valid), kind, p(count), p(grad.contiguous()), p(dpred), _lib.stream_ptr()))
+            n_cap, p(n_valid), kind, p(count), p(_loss_grad(grad_loss)), p(dpred), _lib.stream_ptr()))
         return dpred, None, None, None, None, None, None, None
 
 
 def regression_loss_kind(criterion):
     """WFS_LOSS_L1 / WFS_LOSS_MSE for a mean-reduced nn.L1Loss / nn.MSELoss, else None."""
-    if getattr(criterion, "reduction", None) != "mean":
-        return None
-    if type(criterion) is torch.nn.L1Loss:
-        return _lib.WFS_LOSS_L1
-    if type(criterion) is torch.nn.MSELoss:
-        return _lib.WFS_LOSS_MSE
-    return None
+    return _loss_kind(criterion, "mean")
 
 
 def can_fuse_regression_loss(criterion, pred, target):
@@ -1099,7 +1117,7 @@ class SegmentMapLossFunction(Function):
     target and mask maps: ``map`` [B, planes, nx, ny] is scored at the ACTIVE segments only, plane ``p`` against column
     ``cols[p]`` of ``target`` [N] or [N, n_cols], over the rows below ``n_valid`` whose (x, y, event) lies inside the map
     and (with ``se_mask``) on a single-ended segment: the sum of |d| / d^2 over those rows divided by their number.  One
-    HIP launch forward, one backward that writes the whole gradient map (csrc/segmaploss.hip).  Returns
+    HIP launch forward, one backward that writes the whole gradient map (csrc/segloss.hip).  Returns
     ``(total, per_plane)``: ``total`` a 0-dim fp32 scalar, the sum of the per-plane losses and the only differentiable
     output; ``per_plane`` [planes] (LitEZ's ZLoss, ELoss).  Rows that are not counted, and map cells without a counted
     row, are selected out: whatever they hold the loss stays finite and their gradient is exactly 0.
@@ -1109,30 +1127,20 @@ class SegmentMapLossFunction(Function):
     @staticmethod
     def forward(ctx, map, coords, target, cols, kind, se_mask=None, n_valid=None, max_blocks=0):
         lib = _lib.load()
-        for t in (map, coords, target):
-            if not t.is_cuda:
-                raise RuntimeError("waveformml_amd: tensor must live on the GPU (there is no CPU path); got %s" % t.device)
-        map, target, coords = map.contiguous(), target.contiguous(), coords.contiguous()
         n_cap = int(coords.shape[0])
-        if map.dim() != 4 or coords.dtype != torch.int32 or coords.dim() != 2 or coords.shape[1] != 3 or \
-                target.dim() not in (1, 2) or target.shape[0] != n_cap:
-            raise RuntimeError("segment_map_loss: map must be [B, planes, nx, ny], coords int32 [N, 3] = (x, y, event) and "
-                               "target [N] or [N, n_cols], got %s, %s %s and %s"
-                               % (tuple(map.shape), coords.dtype, tuple(coords.shape), tuple(target.shape)))
+        n_cols, se_mask = _loss_checks(
+            "segment_map_loss", (map, coords, target),
+            ((map.dim() == 4 and _coords_ok(coords, n_cap),
+              "map must be [B, planes, nx, ny], coords int32 [N, 3] = (x, y, event) and target [N] or [N, n_cols], got "
+              "%s, %s %s and %s" % (tuple(map.shape), coords.dtype, tuple(coords.shape), tuple(target.shape))),),
+            target, n_cap, se_mask, tuple(map.shape[-2:]), n_valid)
+        map, target, coords = map.contiguous(), target.contiguous(), coords.contiguous()
         B, planes, nx, ny = (int(v) for v in map.shape)
-        n_cols = int(target.shape[1]) if target.dim() == 2 else 1
         cols = tuple(int(c) for c in cols)
         if len(cols) != planes:
             raise RuntimeError("segment_map_loss: %d planes need %d target columns, got %r" % (planes, planes, cols))
-        if se_mask is not None:
-            se_mask = se_mask.reshape(se_mask.shape[-2:]).contiguous()
-            if se_mask.dtype != torch.float32 or tuple(se_mask.shape) != (nx, ny):
-                raise RuntimeError("segment_map_loss: the mask must be float32 [%d, %d]" % (nx, ny))
-        if n_valid is not None and (n_valid.dtype != torch.int64 or not n_valid.is_cuda):
-            raise RuntimeError("segment_map_loss: n_valid must be a device int64")
-        work, nbytes = _zeroed_workspace(map.device, int(lib.wfs_segment_map_loss_workspace_bytes(n_cap, planes)))
-        out = torch.empty((planes + 1,), dtype=torch.float32, device=map.device)
-        count = torch.empty((1,), dtype=torch.int64, device=map.device)
+        work, nbytes, out, count = _loss_buffers(map.device, int(lib.wfs_segment_map_loss_workspace_bytes(n_cap, planes)),
+                                                 planes + 1)
         p = _lib.ptr
         _lib.check(lib.wfs_segment_map_loss(
             p(map), _lib.dtype_code(map), B, planes, nx, ny, p(coords), p(target), _lib.dtype_code(target), n_cols,
@@ -1152,12 +1160,11 @@ class SegmentMapLossFunction(Function):
         map, coords, target, se_mask, n_valid, count = ctx.saved_tensors
         n_cols, cols, n_cap, kind = ctx.args
         B, planes, nx, ny = (int(v) for v in map.shape)
-        grad = grad_total if grad_total.dtype == torch.float32 else grad_total.float()
         dmap = torch.empty_like(map)
         p = _lib.ptr
         _lib.check(_lib.load().wfs_segment_map_loss_backward(
             p(map), _lib.dtype_code(map), B, planes, nx, ny, p(coords), p(target), _lib.dtype_code(target), n_cols,
-            _lib.i32_array(cols), p(se_mask), n_cap, p(n_valid), kind, p(count), p(grad.contiguous()), p(dmap),
+            _lib.i32_array(cols), p(se_mask), n_cap, p(n_valid), kind, p(count), p(_loss_grad(grad_total)), p(dmap),
             _lib.stream_ptr()))
         return dmap, None, None, None, None, None, None, None
 
@@ -1165,13 +1172,7 @@ class SegmentMapLossFunction(Function):
 def segment_loss_kind(criterion):
     """WFS_LOSS_L1 / WFS_LOSS_MSE for a SUM-reduced plain nn.L1Loss / nn.MSELoss (what the segment modules build), else
     None."""
-    if getattr(criterion, "reduction", None) != "sum":
-        return None
-    if type(criterion) is torch.nn.L1Loss:
-        return _lib.WFS_LOSS_L1
-    if type(criterion) is torch.nn.MSELoss:
-        return _lib.WFS_LOSS_MSE
-    return None
+    return _loss_kind(criterion, "sum")
 
 
 def segment_map_loss(map, coords, target, cols, kind, se_mask=None, n_valid=None, max_blocks=0):
