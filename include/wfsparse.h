@@ -1370,6 +1370,39 @@ int wfs_event_max_fwd(const int32_t *coords, const void *X, int64_t n_cap, int32
 int wfs_event_max_bwd(const int32_t *coords, const void *dY, const int32_t *arg, int64_t n_cap, int32_t D, int32_t B,
                       void *dX, int32_t dtype, const int64_t *n_dev, void *stream);
 
+/* ---- Classification metrics: accuracy, confusion matrix, cross-entropy mean, ROC tables (csrc/classmetrics.hip) ----
+ * What the reference's LitPSD / LitSegClassifier keep per validation / test step: torchmetrics' Accuracy and
+ * ConfusionMatrix(num_classes = n_type), and ROCCurve's binary confusion matrices of softmax(logits)[:, k] against T
+ * thresholds (src/evaluation/ROCCurve.py) -- here for every class k at once.  Additions only: WFS_ABI_VERSION stays.
+ *
+ * wfs_class_metrics_accumulate: ONE launch on `stream`; no read-back, no allocation, no memset.
+ *   logits      [N, C] of `dtype`, row r at logits + r * row_stride ELEMENTS (row_stride >= C); element alignment only
+ *   labels      int64 [N]; a row whose label is ignore_index is counted in the head's "ignored" and nowhere else
+ *   loss_mask   uint8 [N] or NULL: the cross-entropy term enters the loss sum only where it is non-zero
+ *   N, n_dev    rows, and the optional device-side valid count (as everywhere): rows at and beyond it are not read
+ *   thresholds  device float [T], ASCENDING; the callers fill it with (float)((i + 1.0) / T)
+ *   tables      int64 [wfs_class_metrics_table_ints(C, T)], persistent, in this order:
+ *                 head [5]            rows counted, rows correct, loss rows, loss sum, rows ignored
+ *                 confusion [C, C]    [label, prediction]
+ *                 roc [C, 2, T + 1]   [class k, label == k, b_k]
+ *   flags       int32 [1], STICKY: 1 a non-finite logit in a counted row, 2 a label outside [0, C) that is not
+ *               ignore_index, 4 a loss term of 2^15 or more, or the loss sum left int64.  A flagged row is in no table.
+ *   max_blocks  0: the launch's own block count; the tables do not depend on it
+ * Per counted row: prediction = the FIRST index of the largest logit; p_k = exp(x_k - m) / sum_j exp(x_j - m) in fp64 from
+ * the stored logits, rounded once to float; b_k = #{i : p_k >= thresholds[i]} in 0 .. T; the loss term m + log(sum_j
+ * exp(x_j - m)) - x_label in fp64, summed as round(term * WFS_SEG_FIXED_ONE).  Integer atomics only: the tables are
+ * bit-identical from run to run and for every max_blocks.
+ * Limits: 2 <= C <= 32, 1 <= T <= 1024 and 6 + C * C + 2 * C * (T + 1) + T <= 16384 (the workgroup's 64 KB LDS image);
+ * outside them wfs_class_metrics_table_ints returns 0 and the accumulate WFS_EINVAL. */
+#define WFS_CLASS_METRICS_MAX_CLASSES 32
+#define WFS_CLASS_METRICS_MAX_THRESH 1024
+#define WFS_CLASS_METRICS_LDS_BYTES 65536
+size_t wfs_class_metrics_table_ints(int32_t C, int32_t T);
+int wfs_class_metrics_accumulate(const void *logits, int32_t dtype, int64_t row_stride, const int64_t *labels,
+                                 int64_t ignore_index, const uint8_t *loss_mask, int64_t N, const int64_t *n_dev,
+                                 int32_t C, const float *thresholds, int32_t T, int64_t *tables, int32_t *flags,
+                                 int32_t max_blocks, void *stream);
+
 /* opt-in per-kernel timing (HIP events on the launch stream), used by bench.py's roofline ---- */
 #define WFS_TIMER_GATHER_CONV 0
 #define WFS_TIMER_GATHER_DW 1

@@ -15,6 +15,7 @@ WFS_TENSOR_TARGET_I64 = 3   # wfs_tensor_rows: a target of int64 class indices
 WFS_MAX_DIM = 4
 WFS_RNN_RELU, WFS_RNN_TANH = 0, 1
 WFS_LOSS_L1, WFS_LOSS_MSE = 0, 1
+WFS_CLASS_METRICS_MAX_CLASSES, WFS_CLASS_METRICS_MAX_THRESH, WFS_CLASS_METRICS_LDS_BYTES = 32, 1024, 65536
 WFS_PREDICT_ROWS_PER_BLOCK = 256      # rows per workgroup of wfs_predict_prepare's coordinate scan
 WFS_PREDICT_WAVEFORM, WFS_PREDICT_PULSE = 0, 1
 WFS_PREDICT_DENSE, WFS_PREDICT_EVENT, WFS_PREDICT_ROWS = 0, 1, 2
@@ -213,6 +214,9 @@ SIGNATURES = {
                                                         ctypes.POINTER(_dbl), c_i32p, _i32, _vp, _vp, _vp]),
     "wfs_tensor_rows": (ctypes.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _vp, _i64, _vp, _i32, _i32, _vp, _vp, _vp, _vp,
                                        _vp]),
+    "wfs_class_metrics_table_ints": (_sz, [_i32, _i32]),
+    "wfs_class_metrics_accumulate": (ctypes.c_int, [_vp, _i32, _i64, _vp, _i64, _vp, _i64, _vp, _i32, _vp, _i32, _vp, _vp,
+                                                    _i32, _vp]),
     "wfs_masked_regression_loss_workspace_bytes": (_sz, [_i64]),
     "wfs_masked_regression_loss": (ctypes.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i64, _vp, _i32,
                                                   _i32, _vp, _sz, _vp, _vp, _vp]),

@@ -1,4 +1,5 @@
-// wfs_segtables.h -- what the evaluation kernels with fixed-point tables share (segstats.hip, zreal.hip, metricpairs.hip):
+// wfs_segtables.h -- what the evaluation kernels with fixed-point tables share (segstats.hip, zreal.hip, metricpairs.hip,
+// classmetrics.hip):
 // a plane of a dense [B, P, nx, ny] map, and the (count, fixed-point sum) cells of their int64 tables.  Included into
 // each file's anonymous namespace, after wfs_evalbins.h (add64).
 #pragma once
@@ -40,6 +41,15 @@ __device__ __forceinline__ bool real_image(float r, long long *v, int *flags) {
         return false;
     }
     *v = __double2ll_rn(__dmul_rn((double)r, FIX_ONE));
+    return true;
+}
+// the same for a result held in fp64 (classmetrics.hip: a cross-entropy term), under the caller's flag bit
+__device__ __forceinline__ bool real_image(double r, long long *v, int *flags, int bit) {
+    if (!(fabs(r) < 32768.0)) {               // also catches NaN
+        atomicOr(flags, bit);
+        return false;
+    }
+    *v = __double2ll_rn(__dmul_rn(r, FIX_ONE));
     return true;
 }
 // a cell's sum; flag `bit` when it leaves int64 (the segment tables 8, the real-valued pair tables 16)

@@ -13,7 +13,8 @@ class LitPSD(LitBase):
         super().__init__(config, trial)
         self.n_type = n_type
         self.softmax = nn.LogSoftmax(dim=1)
-        self.last_test_logits = None          # test_step's logits, for evaluate.test_loop(..., evaluator=...)
+        self.last_test_logits = None          # test_step's logits, for evaluate.test_loop(..., evaluator=..., metrics=...)
+        self._metrics = None
 
     def _make_evaluator(self, device):
         """The reference's ``self.evaluator = PSDEvaluator(system_config.type_names, ...)`` (src/engineering/LitPSD.py:
@@ -31,6 +32,23 @@ class LitPSD(LitBase):
             return PhysEvaluator(list(names), device, **evaluation_params(self.config))
         from .evaluator import PSDEvaluator
         return PSDEvaluator(list(names), device, n_samples=getattr(self.config.system_config, "n_samples", 150))
+
+    def _class_names(self):
+        names = getattr(self.config.system_config, "type_names", None)
+        return list(names) if names else None
+
+    @property
+    def metrics(self):
+        """The reference's ``torchmetrics.Accuracy`` / ``ConfusionMatrix(num_classes=n_type)`` (and LitSegClassifier's
+        ``ROCCurve``) as one psd/class_metrics.ClassificationMetrics, built on first use on the device the model lives on,
+        as ``evaluator`` is.  Nothing calls it implicitly: hand it to ``evaluate.test_loop`` /
+        ``evaluate.segment_test_loop(..., metrics=module.metrics)``."""
+        if self._metrics is None:
+            from .class_metrics import ClassificationMetrics
+            self._metrics = ClassificationMetrics(next(self.model.parameters()).device, self.n_type,
+                                                  class_names=self._class_names(),
+                                                  ignore_index=getattr(self.criterion, "ignore_index", -100))
+        return self._metrics
 
     def _predict(self, c, f, target, n_valid=None):
         # the reference reads the batch size back from the last coordinate row (SPConvNet.py:63, a device->host

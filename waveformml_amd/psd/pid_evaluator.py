@@ -9,7 +9,7 @@ read back until ``results()``.  Every table is an exact int64 count.
 
 What is mirrored: the constructor arithmetic (``E_scale``, ``z_scale``, ``default_bins`` with ``bin_overrides``, the four
 metrics energy / psd / multiplicity / z and their ``norm_factor``), the tables of ``add``.  Not mirrored: plots, the
-calibration database, ``ROCCurve``.
+calibration database.  ``ROCCurve`` is psd/class_metrics.ClassificationMetrics (``LitSegClassifier.metrics``).
 
 Where this departs from a reference run, because the reference's code and its intent part:
 

@@ -417,7 +417,8 @@ class Trainer(object):
             tot, acc, n = float(sums[0]), float(sums[1]), int(sums[2])
         return {"val_loss": tot / max(n, 1), "val_acc": acc / max(n, 1)}
 
-    def test(self, module, loader):
-        """``pl.Trainer.test`` for the PSD module (reference Evaluate.py:84): see psd/evaluate.test_loop."""
+    def test(self, module, loader, metrics=None):
+        """``pl.Trainer.test`` for the PSD module (reference Evaluate.py:84): see psd/evaluate.test_loop.  ``metrics``: a
+        psd/class_metrics.ClassificationMetrics (``module.metrics``) that every batch's logits and labels go to."""
         from .evaluate import test_loop
-        return test_loop(module, loader, self.device, self.feature_dtype)
+        return test_loop(module, loader, self.device, self.feature_dtype, metrics=metrics)
