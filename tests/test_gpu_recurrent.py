@@ -10,12 +10,12 @@ Measured on an MI355X (worst tensor of a case, error over the tensor's max): fp3
 import copy
 import math
 
-import numpy as np
 import pytest
 import torch
 
 import waveform_cases as wc
 from recurrent_cases import CASES, assert_live, case_id, make_inputs, make_rnn, run_torch
+from seq_cases import elman as _elman, rnn_hash_masks as _hash_masks
 from waveform_cases import DEV, TOL, max_err as _err
 
 pytestmark = pytest.mark.gpu
@@ -78,42 +78,6 @@ def test_forward_dx_and_parameter_gradients_against_float64(case, dtype):
         _y, h32 = rnn(x.float())
     assert hidden.shape == (layers * dirs, N, H) and hidden.dtype == dtype
     _compare("%s %s" % (case_id(case), dtype), [("hidden", hidden)], [("hidden", href)], [("hidden", h32)], dtype)
-
-
-def _hash_masks(seed, p, N, C, T, layer):
-    """The kernels' dropout multipliers of layer `layer`'s outputs, [N, T, C] in float64, from the documented scheme
-    (include/wfsparse.h, recurrent front end): splitmix64 finaliser over seed + counter * golden ratio, counter =
-    (((row << 3 | layer) << 6 | channel) << 12) | t; dropped when the high 32 bits are below p 2^32, else 1 / (1 - p) in
-    fp32."""
-    row = np.arange(N, dtype=np.uint64)[:, None, None]
-    t = np.arange(T, dtype=np.uint64)[None, :, None]
-    ch = np.arange(C, dtype=np.uint64)[None, None, :]
-    return wc.hash_masks(seed, p, ((((row << np.uint64(3)) | np.uint64(layer)) << np.uint64(6) | ch) << np.uint64(12)) | t)
-
-
-def _elman(rnn, x, masks, dtype=torch.float64):
-    """The Elman recurrence written out (autograd, `dtype`) on rnn's parameters, `masks[l]` multiplying layer l's
-    outputs (None: no mask).  Returns (y, leaf parameters in named_parameters order)."""
-    params = {n: p.detach().to(dtype).requires_grad_(True) for n, p in rnn.named_parameters()}
-    act = torch.relu if rnn.nonlinearity == "relu" else torch.tanh
-    N, T, _ = x.shape
-    inp = x
-    for l in range(rnn.num_layers):
-        outs = []
-        for d, sfx in enumerate(("", "_reverse") if rnn.bidirectional else ("",)):
-            wi, wh = params["weight_ih_l%d%s" % (l, sfx)], params["weight_hh_l%d%s" % (l, sfx)]
-            b = (params["bias_ih_l%d%s" % (l, sfx)] + params["bias_hh_l%d%s" % (l, sfx)]) if rnn.bias else 0
-            pre = inp @ wi.t() + b
-            h = torch.zeros(N, rnn.hidden_size, dtype=dtype)
-            hs = [None] * T
-            for t in (range(T - 1, -1, -1) if d else range(T)):
-                h = act(pre[:, t] + h @ wh.t())
-                hs[t] = h
-            outs.append(torch.stack(hs, 1))
-        inp = torch.cat(outs, 2)
-        if masks[l] is not None:
-            inp = inp * masks[l].to(dtype)
-    return inp, [params[n] for n, _ in rnn.named_parameters()]
 
 
 def test_dropout_masks_rebuilt_in_the_backward_match_a_reference_with_the_same_masks():

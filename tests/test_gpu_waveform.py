@@ -4,27 +4,19 @@ dropout masks, determinism, the bounds, one LitWaveform step against the CPU mod
 eager one on a padded batch, and Trainer(capture=True) from the r3 pulse fixture."""
 import math
 
-import numpy as np
 import pytest
 import torch
 
 import waveform_cases as wc
+from seq_cases import make_tcn, tcn_hash_masks as _hash_masks, tcn_masked_reference as _masked_reference
 from waveform_cases import DEV, TOL, max_err as _max_err
 
 pytestmark = pytest.mark.gpu
 
 
 def _tcn_pair(c0, channels, k, dropout=0.0, seed=0):
-    from waveformml_amd.psd.tcn import TemporalConvNet
-    torch.manual_seed(seed)
-    gpu = TemporalConvNet(c0, channels, kernel_size=k, dropout=dropout, fused=True)
-    with torch.no_grad():
-        for name, p in gpu.named_parameters():  # N(0, 0.01) taps would leave the net almost linear
-            p.copy_(torch.randn_like(p) * 0.5)
-            if name.endswith(("bias", "weight_g", "downsample.weight")):
-                p.abs_().add_(0.1)              # ... and a narrow level can die (all ReLUs off): keep the residuals live
-    ref = TemporalConvNet(c0, channels, kernel_size=k, dropout=dropout).double()
-    ref.load_state_dict({k_: v.double() for k_, v in gpu.state_dict().items()})
+    """The fused module on the GPU with the live-parameter recipe of tests/seq_cases.py, and its float64 twin."""
+    gpu, ref = make_tcn(c0, channels, k, dropout=dropout, seed=seed)
     return gpu.to(DEV), ref
 
 
@@ -65,30 +57,6 @@ def test_forward_dx_and_parameter_gradients_against_float64(case, dtype):
         err, scale = _max_err(a, b)
         print("%s %s: max err %.3e of max %.3e (%.2e)" % (dtype, name, err, scale, err / max(scale, 1e-30)))
         assert err <= tol * scale, (name, err, scale)
-
-
-def _hash_masks(seed, p, N, C, L, conv):
-    """The kernels' dropout multipliers of conv `conv` (= 2 level + {0, 1}), [N, C, L] in float64, computed here from the
-    documented scheme (csrc/tcnc.hip drop_mult: splitmix64 finaliser over seed + counter * golden ratio, counter =
-    (((row << 4 | conv) << 5 | channel) << 12) | t; dropped when the high 32 bits are below p 2^32, else 1 / (1 - p) in
-    fp32)."""
-    row = np.arange(N, dtype=np.uint64)[:, None, None]
-    ch = np.arange(C, dtype=np.uint64)[None, :, None]
-    t = np.arange(L, dtype=np.uint64)[None, None, :]
-    return wc.hash_masks(seed, p, ((((row << np.uint64(4)) | np.uint64(conv)) << np.uint64(5) | ch) << np.uint64(12)) | t)
-
-
-def _masked_reference(ref, x, masks):
-    """The float64 torch composition with the given dropout multipliers in place of nn.Dropout."""
-    h = x
-    for lv, blk in enumerate(ref.network):
-        L = h.shape[2]
-        c1, c2 = blk.convs
-        h1 = torch.relu(c1(h)[:, :, :L]) * masks[2 * lv]
-        h2 = torch.relu(c2(h1)[:, :, :L]) * masks[2 * lv + 1]
-        res = h if blk.downsample is None else blk.downsample(h)
-        h = torch.relu(h2 + res)
-    return h
 
 
 def _check_with_dropout(channels, k, N, L, p, seed_state):
