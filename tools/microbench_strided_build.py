@@ -1,5 +1,6 @@
 """Micro-benchmark of the strided layers' rulebook builds and of the products that read their tables, on the bench
-workload's geometry (run on the GPU box):  python tools/microbench_strided_build.py [iters] [events] [bf16|f32]
+workload's geometry (run on the GPU box):  python tools/microbench_strided_build.py [iters] [events] [bf16|f32] [builds]
+("builds": the event-local build lines only -- what a timing knock-out, whose tables are wrong, may run).
 Event-local build (csrc/evconv.hip, one launch) against the chip-wide build (rulebook.hip, six launches); dX / dW through
 the packed [9, N] table against the dense [27, N] one.  Every timing is GPU time per call inside a replayed HIP graph."""
 import os
@@ -16,6 +17,7 @@ from waveformml_amd.spconv import ops
 iters = int(sys.argv[1]) if len(sys.argv) > 1 else 50
 NB = int(sys.argv[2]) if len(sys.argv) > 2 else 256
 DT = torch.float32 if (len(sys.argv) > 3 and sys.argv[3] == "f32") else torch.bfloat16
+BUILDS_ONLY = len(sys.argv) > 4 and sys.argv[4] == "builds"
 dev = torch.device("cuda:0")
 c, f, y = synthetic.generate(NB, 256, 3, seed=1234)
 torch.cuda.set_stream(torch.cuda.Stream())
@@ -55,7 +57,7 @@ cap1, cap2 = int(M1 * 1.19), int(M2 * 1.19)
 alg1 = N * 16 + 8 * P1 + M1 * 16
 alg2 = M1 * 16 + 8 * P2 + M2 * 16
 last = {}
-for on in (True, False):
+for on in ((True,) if BUILDS_ONLY else (True, False)):
     ops.EVENT_LOCAL_CONV = on
     tag = "event-local" if on else "chip-wide "
     s1, s2 = {}, {}
@@ -74,6 +76,8 @@ for on in (True, False):
 
     timeit("strided build, layer 2 + cell map (%s)" % tag, b2, alg2)
 ops.EVENT_LOCAL_CONV = True
+if BUILDS_ONLY:
+    sys.exit(0)
 
 rb = last[True]
 torch.cuda.synchronize()

@@ -30,7 +30,8 @@
 namespace {
 
 // timing knock-outs (results wrong by construction; tools/exp/eck<bits>/ via `make knock_ec`): 1 no look-back (ids start at
-// 0 in every event), 2 no by-output table, 4 no table / coordinate stores at all, 8 no tickets / first flags
+// 0 in every event), 2 no by-output table, 4 no table / coordinate stores at all, 8 no tickets / first flags, 16 no rows
+// past the first EC_THREADS of an event (what the further rows of the largest events cost a launch)
 #ifndef EC_KNOCK
 #define EC_KNOCK 0
 #endif
@@ -62,8 +63,16 @@ struct ECGeo {
     // candidate slots: packed form: slot = leading-offset index q (the last dim's offset follows from the row);
     // dense form: slot = kernel offset k.  Digits of the offsets, 8 bits per dim (leading dims 0..2, last dim in 24..31)
     unsigned dig[32];
+    // record arm (see Rec): the slots that offset o of a dimension leaves standing (leading dims; the last dim in the
+    // dense form), all slots, and whether a row is one aligned 16-byte load.  The record kernels index g with constants
+    // only: its fields are then scalar operands (with an indexed access among this many the struct is copied to scratch)
+    unsigned dmask[3][4], lmask[8], slotmask;
+    int vec4, sp_last;                       // sp_last = spatial[ndim - 1]
 };
-
+// record arm: what slot t takes off a row's cell base.  An argument of its own, because the wide form indexes it
+struct ECOff {
+    int v[32];
+};
 
 // The candidates of one input row, in registers: slot t (compile-time index) holds the event-local output cell the
 // row reaches through that slot's kernel offset, or -1.  PACKED: o_star = the one offset along the last dim that can
@@ -132,6 +141,85 @@ __device__ __forceinline__ Cand<NQ> digest_row(const ECGeo &g, const int *__rest
         c.cell[t] = v ? lead * g.out_last + oc : -1;
     }
     return c;
+}
+
+// RECORD form of a digested row, for geometries whose candidates are affine in the slot: every leading dimension has
+// stride 1 and the last one is packed (kernel <= stride) or has stride 1.  Then slot t reaches cell cbase - doff[t], with
+// cbase = (sum_d (x_d + p_d) * lmult[d]) * out_last + (the last dim's output coordinate at offset 0) and doff the same for
+// every row, and whether it exists is one bit: two registers per row instead of eleven, so a thread keeps
+// EC_REC_PER_THREAD rows digested through all phases and the largest events are not read and decoded again in every phase.
+struct Rec {
+    int w;                   // cbase | o_star << 28 (cbase < 2^28: host-verified; 0 when m == 0)
+    unsigned m;              // slot t reaches an output cell
+};
+constexpr int EC_REC_PER_THREAD = 3;          // rows a thread keeps digested: 1536 of an event at 512 threads
+
+template <bool PACKED>
+__device__ __forceinline__ Rec digest_rec(const ECGeo &g, const int *__restrict__ idx, long long j, int *f_range) {
+    const int last = g.ndim - 1;
+    int x[4];
+    if (g.vec4) {
+        const int4 v = *reinterpret_cast<const int4 *>(idx + j * 4);
+        x[0] = v.y;
+        x[1] = v.z;
+        x[2] = v.w;
+        x[3] = 0;
+    } else {
+        const int *row = idx + j * (g.ndim + 1);
+#pragma unroll
+        for (int d = 0; d < 4; ++d) x[d] = d <= last ? row[1 + d] : 0;
+    }
+    const int xl = last == 0 ? x[0] : last == 1 ? x[1] : last == 2 ? x[2] : x[3];
+    bool ok = (unsigned)xl < (unsigned)g.sp_last;
+    int lead = 0;
+    unsigned m = g.slotmask;
+#pragma unroll
+    for (int d = 0; d < 3; ++d)
+        if (d < last) {
+            ok = ok && (unsigned)x[d] < (unsigned)g.spatial[d];
+            const int t = x[d] + g.lp[d];
+            lead += t * g.lmult[d];
+            unsigned sel = 0u;
+#pragma unroll
+            for (int o = 0; o < 4; ++o) sel |= (unsigned)(t - o * g.ld[d]) < (unsigned)g.lout[d] ? g.dmask[d][o] : 0u;
+            m &= sel;
+        }
+    const int tl = xl + g.pl;
+    int cb, os = 0;
+    if (PACKED) {
+        const int oc = (int)(((unsigned)(tl < 0 ? 0 : tl) * g.last_magic) >> 16);
+        os = tl - oc * g.sl;
+        if (!(os < g.kl && oc < g.out_last)) m = 0u;
+        cb = lead * g.out_last + oc;
+    } else {
+        unsigned sel = 0u;
+#pragma unroll
+        for (int o = 0; o < 8; ++o) sel |= (unsigned)(tl - o * g.dl) < (unsigned)g.out_last ? g.lmask[o] : 0u;
+        m &= sel;
+        cb = lead * g.out_last + tl;
+    }
+    if (!ok) {
+        m = 0u;
+        *f_range = 1;
+    }
+    return Rec{m != 0u ? (cb | (os << 28)) : 0, m};
+}
+
+// record i of a thread's three: selects of VALUES (i is the same in every thread)
+__device__ __forceinline__ Rec ec_pick(int i, Rec a, Rec b, Rec c) {
+    return Rec{i == 1 ? b.w : i == 2 ? c.w : a.w, i == 1 ? b.m : i == 2 ? c.m : a.m};
+}
+
+// f(t) for the slots of a geometry: unrolled (t a constant: doff[t] is a scalar operand) where they fit 9
+template <int NQ, typename F>
+__device__ __forceinline__ void ec_slots(int nslots, F f) {
+    if constexpr (NQ <= 9) {
+#pragma unroll
+        for (int t = 0; t < NQ; ++t) f(t);
+    } else {
+#pragma unroll 1
+        for (int t = 0; t < nslots; ++t) f(t);
+    }
 }
 
 // The same enumeration without the register cache, for geometries with more slots than fit one (NQ > 9): calls
@@ -220,8 +308,8 @@ __device__ __forceinline__ int ec_block_scan(int v, int *sWave, int *total) {
     return base + inc - v;
 }
 
-template <bool PACKED, int NQ, int EC_THREADS>
-__global__ void __launch_bounds__(EC_THREADS) __attribute__((amdgpu_waves_per_eu(EC_THREADS <= 512 ? EC_MIN_WAVES : 4))) k_ev_conv(ECGeo g, int img_bytes, const int *__restrict__ idx, long long N,
+template <bool REC, bool PACKED, int NQ, int EC_THREADS>
+__global__ void __launch_bounds__(EC_THREADS) __attribute__((amdgpu_waves_per_eu(EC_THREADS <= 512 ? EC_MIN_WAVES : 4))) k_ev_conv(ECGeo g, ECOff doff, int img_bytes, const int *__restrict__ idx, long long N,
                                                         const long long *__restrict__ n_dev,
                                                         const int *__restrict__ ev_in, int B, long long M_cap,
                                                         int *__restrict__ out_idx, long long *__restrict__ m_dev,
@@ -262,9 +350,34 @@ __global__ void __launch_bounds__(EC_THREADS) __attribute__((amdgpu_waves_per_eu
         ticket[c] = 0xFFFFFFFFu;
         cellid[c] = 0xFFFFu;
     }
-    // CACHE (<= 9 candidate slots): this thread's first row stays digested in registers through all phases (events
-    // beyond EC_THREADS rows re-digest the further ones); wider geometries stream their candidates in every phase
-    constexpr bool CACHE = NQ <= 9;
+    // REC: local rows tid + i * EC_THREADS, i < R, stay digested as records through all phases; rows beyond them (rare)
+    // are digested again in every phase.  Three named records picked by value (ec_pick), and the row loops below not
+    // unrolled: 52 registers and 26 KB of code at the PSD geometry; unrolled (the first chunk peeled, its cells kept
+    // across the phases) the same source takes 113 registers, which the cap of 72 turns into 150 B of scratch
+    constexpr int R = EC_REC_PER_THREAD;
+    Rec rc0{0, 0u}, rc1{0, 0u}, rc2{0, 0u};
+    if constexpr (REC) {
+        if (tid < n) rc0 = digest_rec<PACKED>(g, idx, (long long)r0 + tid, &f_range);
+        if (tid + EC_THREADS < n) rc1 = digest_rec<PACKED>(g, idx, (long long)r0 + tid + EC_THREADS, &f_range);
+        if (tid + 2 * EC_THREADS < n) rc2 = digest_rec<PACKED>(g, idx, (long long)r0 + tid + 2 * EC_THREADS, &f_range);
+    }
+    auto rec_at = [&](int i, int jl) {   // the record of local row jl = tid + i * EC_THREADS
+        Rec r = ec_pick(i, rc0, rc1, rc2);
+        if (i >= R) r = digest_rec<PACKED>(g, idx, (long long)r0 + jl, &f_range);
+        if ((EC_KNOCK & 16) && i > 0) r.m = 0u;
+        return r;
+    };
+    // walk(r, f): f(t, cell, k) for every candidate of the row behind record r, in increasing t
+    auto walk = [&](const Rec &r, auto f) {
+        const int cb = r.w & 0x0FFFFFFF, os = r.w >> 28;
+        ec_slots<NQ>(nslots, [&](int t) {
+            if ((r.m >> t) & 1u) f(t, cb - doff.v[t], PACKED ? t * g.kl + os : t);
+        });
+    };
+    // the geometries the record arm refuses -- CACHE (<= 9 candidate slots): this thread's first row stays digested in
+    // registers through all phases (events beyond EC_THREADS rows re-digest the further ones); wider geometries stream
+    // their candidates in every phase
+    constexpr bool CACHE = !REC && NQ <= 9;
     constexpr int NC = CACHE ? NQ : 1;
     Cand<NC> mine;
 #pragma unroll
@@ -272,9 +385,13 @@ __global__ void __launch_bounds__(EC_THREADS) __attribute__((amdgpu_waves_per_eu
     mine.o_star = 0;
     mine.ok = true;
     if (CACHE && tid < n) mine = digest_row<PACKED, NC>(g, idx + (long long)(r0 + tid) * cols);
-    // visit(jl, f): f(t, cell, k) for every candidate of local row jl that reaches an output cell, in increasing t
-    auto visit = [&](int jl, auto f) {
-        if constexpr (CACHE) {
+    // visit(i, jl, f): f(t, cell, k) for every candidate of local row jl = tid + i * EC_THREADS that reaches an output
+    // cell, in increasing t
+    auto visit = [&](int i, int jl, auto f) {
+        if ((EC_KNOCK & 16) && i > 0) return;
+        if constexpr (REC) {
+            walk(rec_at(i, jl), f);
+        } else if constexpr (CACHE) {
             Cand<NC> c = mine;
             if (jl != tid) c = digest_row<PACKED, NC>(g, idx + (long long)(r0 + jl) * cols);
             if (!c.ok) f_range = 1;
@@ -289,27 +406,38 @@ __global__ void __launch_bounds__(EC_THREADS) __attribute__((amdgpu_waves_per_eu
     };
     lds_barrier();
     // ---- 1: tickets
-    for (int jl = tid; jl < n && !(EC_KNOCK & 8); jl += EC_THREADS)
-        visit(jl, [&](int, int cell, int k) { atomicMin(&ticket[cell], (unsigned)jl * 32u + (unsigned)k); });
+#pragma unroll 1
+    for (int i = 0, jl = tid; jl < n && !(EC_KNOCK & 8); ++i, jl += EC_THREADS)
+        visit(i, jl, [&](int, int cell, int k) { atomicMin(&ticket[cell], (unsigned)jl * 32u + (unsigned)k); });
     lds_barrier();
     // ---- 2: first flags -> ids within the event (cellid)
     int carry = 0;
-    for (int j0 = 0; j0 < n && !(EC_KNOCK & 8); j0 += EC_THREADS) {
+#pragma unroll 1
+    for (int i = 0, j0 = 0; j0 < n && !(EC_KNOCK & 8); ++i, j0 += EC_THREADS) {
         const int jl = j0 + tid;
         unsigned mask = 0u;
-        if (jl < n)
-            visit(jl, [&](int t, int cell, int k) {
-                mask |= ticket[cell] == (unsigned)jl * 32u + (unsigned)k ? (1u << t) : 0u;
-            });
-        int tot;
-        const int rowbase = carry + ec_block_scan<EC_WAVES>(__popc(mask), sWave, &tot);
-        if (mask != 0u)
-            visit(jl, [&](int t, int cell, int) {
-                if ((mask >> t) & 1u) {
-                    const int il = rowbase + __popc(mask & ((1u << t) - 1u));
-                    cellid[cell] = (unsigned short)il;
-                }
-            });
+        auto first = [&](int t, int cell, int k) {
+            mask |= ticket[cell] == (unsigned)jl * 32u + (unsigned)k ? (1u << t) : 0u;
+        };
+        int tot, rowbase = 0;
+        auto number = [&](int t, int cell, int) {
+            if ((mask >> t) & 1u) {
+                const int il = rowbase + __popc(mask & ((1u << t) - 1u));
+                cellid[cell] = (unsigned short)il;
+            }
+        };
+        if constexpr (REC) {
+            Rec r{0, 0u};
+            if (jl < n) r = rec_at(i, jl);
+            walk(r, first);
+            rowbase = carry + ec_block_scan<EC_WAVES>(__popc(mask), sWave, &tot);
+            r.m = mask;                                 // only the first-reached cells get a number
+            walk(r, number);
+        } else {
+            if (jl < n) visit(i, jl, first);
+            rowbase = carry + ec_block_scan<EC_WAVES>(__popc(mask), sWave, &tot);
+            if (mask != 0u) visit(i, jl, number);
+        }
         carry += tot;
     }
     const int M_e = carry;
@@ -334,8 +462,9 @@ __global__ void __launch_bounds__(EC_THREADS) __attribute__((amdgpu_waves_per_eu
         const int nd = ((k1 - k0) * mstride) >> 1;
         for (int i = tid; i < nd; i += EC_THREADS) img32[i] = 0xFFFFFFFFu;
         lds_barrier();
-        for (int jl = tid; jl < n; jl += EC_THREADS)
-            visit(jl, [&](int, int cell, int k) {
+#pragma unroll 1
+        for (int i = 0, jl = tid; jl < n; ++i, jl += EC_THREADS)
+            visit(i, jl, [&](int, int cell, int k) {
                 if (k >= k0 && k < k1) img[(k - k0) * mstride + (int)cellid[cell]] = (unsigned short)jl;
             });
         lds_barrier();
@@ -370,9 +499,21 @@ __global__ void __launch_bounds__(EC_THREADS) __attribute__((amdgpu_waves_per_eu
     const int mw = (long long)M_e < m_room ? M_e : (int)m_room;     // rows of this event that exist
     // ---- 4a: the by-input table (coalesced over the rows)
     if (!(EC_KNOCK & 4)) {
-        for (int jl = tid; jl < n; jl += EC_THREADS) {
+#pragma unroll 1
+        for (int i = 0, jl = tid; jl < n; ++i, jl += EC_THREADS) {
             const long long j = (long long)r0 + jl;
-            if (CACHE && jl == tid) {
+            if constexpr (REC) {
+                const Rec r = rec_at(i, jl);
+                const int cb = r.w & 0x0FFFFFFF, os = r.w >> 28;
+                ec_slots<NQ>(nslots, [&](int t) {
+                    int v = -1;
+                    if ((r.m >> t) & 1u) {
+                        const int il = (int)cellid[cb - doff.v[t]];
+                        if (il < mw) v = PACKED ? ((((int)base + il) << 3) | os) : (int)base + il;
+                    }
+                    if (t < nslots) nbr_out[(long long)t * N + j] = v;
+                });
+            } else if (CACHE && jl == tid) {
 #pragma unroll
                 for (int t = 0; t < NC; ++t)
                     if (t < nslots) {
@@ -383,7 +524,7 @@ __global__ void __launch_bounds__(EC_THREADS) __attribute__((amdgpu_waves_per_eu
                     }
             } else {
                 unsigned done = 0u;
-                visit(jl, [&](int t, int cell, int k) {
+                visit(i, jl, [&](int t, int cell, int k) {
                     const int il = (int)cellid[cell];
                     int v = -1;
                     if (il < mw) v = PACKED ? ((((int)base + il) << 3) | (k - t * g.kl)) : (int)base + il;
@@ -561,6 +702,41 @@ void fill_digits(const wfs_geometry *g, ECGeo *G, bool packed) {
     }
 }
 
+// The record arm's tables (see Rec) from the slots' digits; false: this geometry's candidates are not affine in the slot
+// (a leading stride, or a strided last dimension that does not pack) and it keeps the Cand / stream_row path
+bool fill_records(const wfs_geometry *g, ECGeo *G, ECOff *doff, bool packed, const void *indices) {
+    const int last = g->ndim - 1;
+    const int nslots = packed ? G->Kq : g->K;
+    bool rec = packed || G->sl == 1;
+    for (int d = 0; d < last; ++d) rec = rec && G->ls[d] == 1;
+    G->slotmask = nslots >= 32 ? 0xFFFFFFFFu : (1u << nslots) - 1u;
+    G->vec4 = g->ndim == 3 && ((uintptr_t)indices & 15) == 0;
+    G->sp_last = g->spatial[last];
+    for (int d = 0; d < 3; ++d)
+        for (int o = 0; o < 4; ++o) G->dmask[d][o] = 0u;
+    for (int o = 0; o < 8; ++o) G->lmask[o] = 0u;
+    for (int t = 0; t < 32; ++t) {
+        doff->v[t] = 0;
+        if (t >= nslots) continue;
+        const unsigned dg = G->dig[t];
+        long long off = 0;
+        for (int d = 0; d < last; ++d) {
+            const int o = (int)((dg >> (8 * d)) & 255u);
+            G->dmask[d][o] |= 1u << t;
+            off += (long long)o * G->ld[d] * G->lmult[d];
+        }
+        off *= G->out_last;
+        if (!packed) {
+            const int o = (int)(dg >> 24);
+            G->lmask[o] |= 1u << t;
+            off += (long long)o * G->dl;
+        }
+        rec = rec && off + G->cells_e < (1ll << 28);
+        doff->v[t] = (int)off;
+    }
+    return rec;
+}
+
 }  // namespace
 
 extern "C" int wfs_event_rulebook_conv_ok(const wfs_geometry *g) {
@@ -613,37 +789,44 @@ extern "C" int wfs_event_rulebook_conv(const wfs_geometry *g, const int32_t *ind
     const dim3 grid((unsigned)B);
     const bool packed = packed_kl != 0;
     fill_digits(g, &G, packed);
+    ECOff doff;
+    const bool rec = fill_records(g, &G, &doff, packed, indices);
     const int nslots = packed ? G.Kq : g->K;
-#define WFS_EC(P, NQ, TH)                                                                                                \
+#define WFS_EC(RC, P, NQ, TH)                                                                                               \
     do {                                                                                                                 \
         static bool attr = false;                                                                                        \
         if (!attr) {                                                                                                     \
-            WFS_HIP_CHECK(hipFuncSetAttribute((const void *)k_ev_conv<P, NQ, TH>,                                        \
+            WFS_HIP_CHECK(hipFuncSetAttribute((const void *)k_ev_conv<RC, P, NQ, TH>,                                    \
                                               hipFuncAttributeMaxDynamicSharedMemorySize,                                \
                                               158 * 1024));                                                              \
             attr = true;                                                                                                 \
         }                                                                                                                \
-        k_ev_conv<P, NQ, TH><<<grid, dim3(TH), lds, stream>>>(G, (int)img, indices, N, (const long long *)n_dev, events_in, B, \
+        k_ev_conv<RC, P, NQ, TH><<<grid, dim3(TH), lds, stream>>>(G, doff, (int)img, indices, N, (const long long *)n_dev, events_in, B, \
                                                        M_cap, out_indices, (long long *)m_dev, events_out, nbr_out,      \
                                                        nbr_in, cell_row, overflow_dev, flags, pub, st);                   \
     } while (0)
-    // threads per workgroup: 512.  Alone, at the PSD batch (one event per CU), 1024 threads are faster (31 vs 45 us: the
-    // launch lasts as long as its largest event, one row per thread and phase) -- but inside a training step the builds
+    // threads per workgroup: 512.  Alone, at the PSD batch (one event per CU), 1024 threads were faster while every row
+    // past a thread's first was digested again in each phase (31 vs 45 us: the launch lasts as long as its largest
+    // event); with the record arm the 512-thread form takes 29 / 24 us there -- and inside a training step the builds
     // run on a side branch beside the first layers with time to spare, and what counts is the room they leave those
     // layers' kernels on every CU (EC_MIN_WAVES above); beyond 256 events throughput counts: three 512-thread workgroups
-    // to a CU (128 vs 174 us at 2048 events).  WFS_EC_THREADS = 256 / 512 / 1024 overrides (experiments)
+    // to a CU (128 vs 174 us at 2048 events).  WFS_EC_THREADS = 256 / 512 / 1024 overrides (experiments; the packed record arm)
     static const int ec_forced = [] {
         const char *e = getenv("WFS_EC_THREADS");
         const int v = e ? atoi(e) : 0;
         return v == 256 || v == 512 || v == 1024 ? v : 0;
     }();
     const int ec_threads = ec_forced ? ec_forced : 512;
-    if (packed && nslots <= 9 && ec_threads == 1024) WFS_EC(true, 9, 1024);
-    else if (packed && nslots <= 9 && ec_threads == 256) WFS_EC(true, 9, 256);
-    else if (packed && nslots <= 9) WFS_EC(true, 9, 512);
-    else if (packed) WFS_EC(true, 32, 512);
-    else if (nslots <= 9) WFS_EC(false, 9, 512);
-    else WFS_EC(false, 32, 512);
+    if (rec && packed && nslots <= 9 && ec_threads == 1024) WFS_EC(true, true, 9, 1024);
+    else if (rec && packed && nslots <= 9 && ec_threads == 256) WFS_EC(true, true, 9, 256);
+    else if (rec && packed && nslots <= 9) WFS_EC(true, true, 9, 512);
+    else if (rec && packed) WFS_EC(true, true, 32, 512);
+    else if (rec && nslots <= 9) WFS_EC(true, false, 9, 512);
+    else if (rec) WFS_EC(true, false, 32, 512);
+    else if (packed && nslots <= 9) WFS_EC(false, true, 9, 512);
+    else if (packed) WFS_EC(false, true, 32, 512);
+    else if (nslots <= 9) WFS_EC(false, false, 9, 512);
+    else WFS_EC(false, false, 32, 512);
 #undef WFS_EC
     WFS_LAUNCH_CHECK();
     return WFS_OK;
