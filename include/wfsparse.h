@@ -848,6 +848,22 @@ int wfs_load_batch_images(const int32_t *coords, int64_t n, int32_t cols, const 
                           const int64_t *labels, int64_t *labels_dst, int64_t B, int64_t *n_valid_dst,
                           int32_t *event_offsets, int32_t events, const wfs_filter_image_job *jobs, int32_t njobs,
                           void *stream);
+/* wfs_load_rows_batch: the hand-over of a PER-ROW batch (one target row per coordinate row) in one launch.  Additions
+ * only: WFS_ABI_VERSION stays.  Coordinates, permutation, row count, event offsets and image jobs are wfs_load_batch's /
+ * wfs_load_batch_images' (cols 1 .. 8; the 16-byte row path for cols == 4 when all three pointers are 16-byte aligned).
+ *   feats        n rows of row_bytes bytes, copied as bytes into the first n rows of feats_dst [n_cap rows]: 16-byte
+ *                lanes with a byte tail when source and destination are 16-byte aligned, bytes otherwise.  Rows at and
+ *                beyond n are not written.
+ *   targets      n rows of target_row_bytes bytes of `elem`-byte elements (elem 4 or 8, target_row_bytes % elem == 0,
+ *                pointers aligned to elem) into rows [0, n) of targets_dst; rows [n, n_cap) of targets_dst get the pad
+ *                element in every position: pad_host points at 8 HOST bytes of which the first `elem` are used (the
+ *                int64 ignore_index, or its float32 / float64 image).
+ * n <= n_cap.  A source may be NULL when it has no bytes to give; a destination with bytes to take may not. */
+int wfs_load_rows_batch(const int32_t *coords, int64_t n, int64_t n_cap, int32_t cols, const int32_t *perm_host,
+                        int32_t *coords_dst, int32_t *indices_dst, const void *feats, void *feats_dst, int64_t row_bytes,
+                        const void *targets, void *targets_dst, int64_t target_row_bytes, int32_t elem,
+                        const void *pad_host, int64_t *n_valid_dst, int32_t *event_offsets, int32_t events,
+                        const wfs_filter_image_job *jobs, int32_t njobs, void *stream);
 int wfs_gather_conv_image(const int32_t *table, const int32_t *kmap_host, int32_t K, int32_t identity_k,
                           int64_t R, const void *X, int64_t X_rows, int32_t Cx, const float *W,
                           int32_t Cw_in, int32_t Cw_out, int32_t transpose_w, const float *bias, void *Y,

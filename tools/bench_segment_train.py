@@ -28,6 +28,14 @@ the two figures with ``--launches FUSED TORCH``.
 ``--previous FILE`` takes the last line of an earlier ``--out`` file of the same command and prints its B-cost figures
 beside this run's: a difference of two medians is only worth what it repeats to.
 
+``--row-handover`` runs another arm pair INSTEAD of the above (its own result line and profile text,
+profiles/row_handover_ab.txt): the captured step of LitZ (config/segment_z.json, key on) and of LitSegClassifier
+(config/segment_classifier_graph.json, 130 channels, 6 rows per event) with the hand-over of the per-row batch as the
+torch copies, fills and gather (psd/graph.ROW_HANDOVER = 0, WFS_ROW_HANDOVER=0) and as the one launch of
+wfs_load_rows_batch (1), at about 765 and about 86 k rows; and the hand-over alone (GraphedTrainStep._load) in both forms.
+The switch is read by every hand-over, so ONE captured step serves both arms: the same graph, the same buffers, windows
+alternating.
+
 usage: python tools/bench_segment_train.py [--rounds 7] [--calls 30] [--out FILE] [--profile FILE] [--launches F T]
                                            [--previous FILE]
 prints one JSON line; --out appends it to FILE; --profile writes profiles/segment_loss_ab.txt's text to FILE"""
@@ -160,6 +168,103 @@ def loss_routes(torch, name, events, dev, g):
     return fused, composed, {"rows": int(c.shape[0]), "events": events, "planes": planes}, pred
 
 
+HANDOVER_MODULES = (("LitZ", "segment_z.json", 3, 40), ("LitSegClassifier", "segment_classifier_graph.json", 6, 130))
+
+
+class RowStepper(Stepper):
+    """A captured Stepper of one of HANDOVER_MODULES."""
+
+    def __init__(self, torch, name, config, dev):
+        from waveformml_amd.psd import litseg, litz
+        from waveformml_amd.psd.config import load_config
+        from waveformml_amd.psd.ddp import FlatGradAllReducer
+        from waveformml_amd.psd.trainer import Trainer
+        with open(os.path.join(ROOT, "config", config)) as f:
+            cfg = json.load(f)
+        if name == "LitZ":
+            cfg["net_config"]["fused_segment_loss"] = True
+        cfg["optimize_config"].update(lr=1e-4)
+        cfg["optimize_config"].pop("scheduler_class", None)
+        torch.manual_seed(0)
+        self.module = (litz.LitZ if name == "LitZ" else litseg.LitSegClassifier)(load_config(cfg)).to(dev)
+        self.module.train()
+        self.reducer = FlatGradAllReducer(self.module.model.parameters())
+        self.module.optimizer_parameters = self.reducer.optimizer_parameters()
+        opt = self.module.configure_optimizers()
+        self.optimizer = opt[0][0] if isinstance(opt, tuple) else opt
+        self.trainer = Trainer(max_epochs=1, device=dev, capture=True, check_every=0)
+        self.capture = True
+
+
+def row_handover_ab(torch, args, dev, g):
+    """The result of --row-handover (see the module docstring)."""
+    from waveformml_amd import _lib
+    from waveformml_amd.psd import graph
+    out = {"library": os.path.relpath(_lib.LIB_PATH, ROOT), "rounds": args.rounds, "calls": args.calls}
+    for name, config, per_event, channels in HANDOVER_MODULES:
+        for tag, events in SIZES:
+            events = events * 3 // per_event
+            (c, f), y = segment_batch(torch, g, events, per_event, channels, 1)
+            if name == "LitSegClassifier":
+                y = torch.randint(0, 5, (c.shape[0],), generator=g)
+            batch = ((c.to(dev), f.to(dev)), y.to(dev))
+            stepper = RowStepper(torch, name, config, dev)
+            stepper.step(batch)                                   # captures
+            runner = stepper.trainer._graph
+
+            def arm(on, fn):
+                def call():
+                    graph.ROW_HANDOVER = on
+                    fn()
+                return call
+            calls = args.calls if events <= 1024 else max(5, args.calls // 3)
+            was = graph.ROW_HANDOVER
+            try:
+                res = alternate(torch, {"step_torch": arm(False, lambda: stepper.step(batch)),
+                                        "step_one_launch": arm(True, lambda: stepper.step(batch))}, args.rounds, calls)
+                res.update(alternate(torch, {"handover_torch": arm(False, lambda: runner._load(batch)),
+                                             "handover_one_launch": arm(True, lambda: runner._load(batch))},
+                                     args.rounds, calls * 3))
+            finally:
+                graph.ROW_HANDOVER = was
+            res.update(events=events, rows=int(c.shape[0]), n_cap=int(runner.n_cap), calls=calls,
+                       eager_fallbacks=stepper.trainer.eager_fallbacks, event_offsets_in_launch=runner.events is not None)
+            out["%s_%s" % (name, tag)] = res
+            stepper.close()
+            del stepper, runner
+            torch.cuda.empty_cache()
+    return out
+
+
+def render_row_handover(d, line):
+    """The text of profiles/row_handover_ab.txt from one --row-handover result."""
+    rows = ["Hand-over of a per-row batch into a captured training step: the torch copies, fills and gather of",
+            "psd/graph._CapturedRunner._load (WFS_ROW_HANDOVER=0) against the one launch of wfs_load_rows_batch (1).",
+            "tools/bench_segment_train.py --row-handover --profile; MI355X.  Written by the tool; method: its docstring.  fp32 rows,",
+            "device-resident synthetic batches, ONE captured step per module and size serving both arms (the switch is read by",
+            "every hand-over), the arms alternating window by window, %d windows; median over windows, spread = max - min."
+            % d["rounds"],
+            "",
+            "module            rows    capacity  what                          arm          us per call   spread"]
+    for name, _config, _pe, _ch in HANDOVER_MODULES:
+        for tag, _events in SIZES:
+            s = d["%s_%s" % (name, tag)]
+            for what, key in (("captured step", "step"), ("hand-over alone (host-bound)", "handover")):
+                for arm_key, label in (("torch", "torch"), ("one_launch", "one launch")):
+                    r = s["%s_%s" % (key, arm_key)]
+                    rows.append("%-17s %-7d %-9d %-29s %-12s %-13s %s" % (name, s["rows"], s["n_cap"], what, label,
+                                                                           r["us_per_call"], r["spread_us"]))
+            gain = s["step_torch"]["us_per_call"] - s["step_one_launch"]["us_per_call"]
+            spread = max(s["step_torch"]["spread_us"], s["step_one_launch"]["spread_us"])
+            rows.append("                  step: torch - one launch = %+.1f us (larger spread of the two arms %.1f us)%s"
+                        % (gain, spread, "; eager fallbacks %d" % s["eager_fallbacks"] if s["eager_fallbacks"] else ""))
+    rows += ["", "A window of steps is %d (about 765 rows) or %d (about 86 k rows) back-to-back calls between two HIP events and"
+             % (d["calls"], max(5, d["calls"] // 3)),
+             "ends in a device synchronise; a window of hand-overs alone is three times as many calls, and is bound by the host's",
+             "enqueue time (several eager launches against one), not by the device.", "", "raw line of the tool:", line, ""]
+    return "\n".join(rows)
+
+
 def count_kernels(directory):
     """Kernel launches in the kernel_stats.csv files of a rocprofv3 --kernel-trace --stats run under ``directory``."""
     total, names = 0, 0
@@ -246,6 +351,8 @@ def main():
                     help="print the kernel launches per call from the kernel_stats.csv files under DIR (no GPU needed)")
     ap.add_argument("--previous", default=None, metavar="FILE",
                     help="an earlier --out file of the same command: its B-cost figures are printed beside this run's")
+    ap.add_argument("--row-handover", action="store_true",
+                    help="the WFS_ROW_HANDOVER arm pair instead of the arms above (profiles/row_handover_ab.txt)")
     ap.add_argument("--launches", type=float, nargs=2, default=None, metavar=("FUSED", "TORCH"),
                     help="kernel launches per call of the two loss routes, from --count-kernels")
     args = ap.parse_args()
@@ -266,6 +373,17 @@ def main():
         for _ in range(args.trace_calls):
             (fused if args.trace_loss == "fused" else composed)()
         torch.cuda.synchronize()
+        return
+    if args.row_handover:
+        out = row_handover_ab(torch, args, dev, g)
+        line = json.dumps(out)
+        print(line)
+        if args.profile:
+            with open(args.profile, "w") as f:
+                f.write(render_row_handover(out, line))
+        if args.out:
+            with open(args.out, "a") as f:
+                f.write(line + "\n")
         return
     out = {"library": os.path.relpath(_lib.LIB_PATH, ROOT), "rounds": args.rounds, "calls": args.calls, "final_losses": {}}
     if args.launches:

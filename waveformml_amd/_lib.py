@@ -180,6 +180,8 @@ SIGNATURES = {
     "wfs_conv_filter_images": (ctypes.c_int, [_vp, _i32, _i32, _vp, _vp, _vp]),
     "wfs_load_batch_images": (ctypes.c_int, [_vp, _i64, _i32, c_i32p, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp,
                                              _i32, ctypes.POINTER(FilterImageJob), _i32, _vp]),
+    "wfs_load_rows_batch": (ctypes.c_int, [_vp, _i64, _i64, _i32, c_i32p, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32,
+                                           _vp, _vp, _vp, _i32, ctypes.POINTER(FilterImageJob), _i32, _vp]),
     "wfs_gather_conv_image": (ctypes.c_int, [_vp, c_i32p, _i32, _i32, _i64, _vp, _i64, _i32, _vp, _i32, _i32, _i32,
                                              _vp, _vp, _i32, _vp, _i32, _vp, _vp]),
     "wfs_conv_backward_image": (ctypes.c_int, [_vp, _i32, _i32, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _i32, _vp,

@@ -16,6 +16,7 @@
 #include <stdlib.h>
 
 #include "wfs_common.h"
+#include "wfs_evtable.h"
 
 namespace {
 
@@ -54,24 +55,7 @@ __device__ __forceinline__ void offset_digits(const EGeo &g, int k, int *off) {
 // batch index out of [0, B) or smaller than its predecessor's.  Every word is written by every launch (no clearing).
 __global__ void __launch_bounds__(256) k_event_offsets(const int *__restrict__ idx, long long N, int cols, int B,
                                                        const long long *__restrict__ n_dev, int *__restrict__ off) {
-    const long long Nv = wfs_valid_rows(N, n_dev);
-    int bad = 0;
-    if (Nv == 0) {
-        for (int e = blockIdx.x * 256 + threadIdx.x; e <= B; e += gridDim.x * 256) off[e] = 0;
-    }
-    for (long long j = (long long)blockIdx.x * 256 + threadIdx.x; j < Nv; j += (long long)gridDim.x * 256) {
-        const int b = idx[j * cols];
-        const int bp = j > 0 ? idx[(j - 1) * cols] : -1;
-        const bool ok = b >= 0 && b < B && b >= bp && bp >= -1 && bp < B;
-        bad |= ok ? 0 : 1;
-        if (ok) {
-            for (int e = bp + 1; e <= b; ++e) off[e] = (int)j;
-            if (j == Nv - 1)
-                for (int e = b + 1; e <= B; ++e) off[e] = (int)Nv;
-        }
-    }
-    bad = __syncthreads_or(bad);
-    if (threadIdx.x == 0) off[B + 1 + blockIdx.x] = bad;
+    wfs_event_table_block(idx, wfs_valid_rows(N, n_dev), cols, 0, B, off, (int)gridDim.x);
 }
 
 // ------------------------------------------------------------------------------------------ SubM

@@ -9,7 +9,10 @@
 //     buf = g                                   (first step)      buf = momentum * buf + (1 - dampening) * g
 //     g = nesterov ? g + momentum * buf : buf
 //     p -= lr * g
+#include <string.h>
+
 #include "wfs_common.h"
+#include "wfs_evtable.h"
 #include "wfs_filterimg.h"
 
 namespace {
@@ -201,6 +204,32 @@ struct Perm {
     int v[8];
 };
 
+// coords [n, cols] as they are to coords_dst and, columns permuted, to indices_dst (either may be NULL)
+__device__ __forceinline__ void load_coords(const int *__restrict__ coords, long long n, int cols, const Perm &perm,
+                                            int *__restrict__ coords_dst, int *__restrict__ indices_dst, long long tid,
+                                            long long nth) {
+    if (cols == 4 && ((reinterpret_cast<uintptr_t>(coords) | reinterpret_cast<uintptr_t>(coords_dst) |
+                       reinterpret_cast<uintptr_t>(indices_dst)) & 15) == 0) {
+        // the PSD nets' rows (x, y, t, event): one 16-byte row per thread, no division
+        const int4 *src = reinterpret_cast<const int4 *>(coords);
+        int4 *dst = reinterpret_cast<int4 *>(coords_dst), *idx = reinterpret_cast<int4 *>(indices_dst);
+        const int p0 = perm.v[0], p1 = perm.v[1], p2 = perm.v[2], p3 = perm.v[3];
+        auto pick = [](const int4 &r, int p) { return p == 0 ? r.x : (p == 1 ? r.y : (p == 2 ? r.z : r.w)); };
+        for (long long row = tid; row < n; row += nth) {
+            const int4 r = src[row];
+            if (dst) dst[row] = r;
+            if (idx) idx[row] = int4{pick(r, p0), pick(r, p1), pick(r, p2), pick(r, p3)};
+        }
+    } else {
+        for (long long i = tid; i < n * cols; i += nth) {
+            const long long row = i / cols;
+            const int col = (int)(i - row * cols);
+            if (coords_dst) coords_dst[i] = coords[i];
+            if (indices_dst) indices_dst[i] = coords[row * cols + perm.v[col]];
+        }
+    }
+}
+
 __global__ void __launch_bounds__(256) k_load_batch(const int *__restrict__ coords, long long n, int cols, Perm perm,
                                                     int *__restrict__ coords_dst, int *__restrict__ indices_dst,
                                                     const uint4 *__restrict__ feats, uint4 *__restrict__ feats_dst,
@@ -222,47 +251,50 @@ __global__ void __launch_bounds__(256) k_load_batch(const int *__restrict__ coor
     if (tid == 0 && n_valid_dst) *n_valid_dst = n;
     // event offsets of the batch (evrulebook.hip k_event_offsets, same words, same flags): the first WFS_EVENT_FLAG_WORDS
     // blocks walk the batch column of the SOURCE rows -- the captured step then starts with the rulebook build itself
-    if (ev_off && blockIdx.x < WFS_EVENT_FLAG_WORDS) {
-        int bad = 0;
-        if (n == 0)
-            for (int e = blockIdx.x * 256 + threadIdx.x; e <= ev_B; e += WFS_EVENT_FLAG_WORDS * 256) ev_off[e] = 0;
-        for (long long j = (long long)blockIdx.x * 256 + threadIdx.x; j < n; j += (long long)WFS_EVENT_FLAG_WORDS * 256) {
-            const int b = coords[j * cols + ev_col];
-            const int bp = j > 0 ? coords[(j - 1) * cols + ev_col] : -1;
-            const bool ok = b >= 0 && b < ev_B && b >= bp && bp >= -1 && bp < ev_B;
-            bad |= ok ? 0 : 1;
-            if (ok) {
-                for (int e = bp + 1; e <= b; ++e) ev_off[e] = (int)j;
-                if (j == n - 1)
-                    for (int e = b + 1; e <= ev_B; ++e) ev_off[e] = (int)n;
-            }
-        }
-        bad = __syncthreads_or(bad);
-        if (threadIdx.x == 0) ev_off[ev_B + 1 + blockIdx.x] = bad;
-    }
-    if (cols == 4 && ((reinterpret_cast<uintptr_t>(coords) | reinterpret_cast<uintptr_t>(coords_dst) |
-                       reinterpret_cast<uintptr_t>(indices_dst)) & 15) == 0) {
-        // the PSD nets' rows (x, y, t, event): one 16-byte row per thread, no division
-        const int4 *src = reinterpret_cast<const int4 *>(coords);
-        int4 *dst = reinterpret_cast<int4 *>(coords_dst), *idx = reinterpret_cast<int4 *>(indices_dst);
-        const int p0 = perm.v[0], p1 = perm.v[1], p2 = perm.v[2], p3 = perm.v[3];
-        auto pick = [](const int4 &r, int p) { return p == 0 ? r.x : (p == 1 ? r.y : (p == 2 ? r.z : r.w)); };
-        for (long long row = tid; row < n; row += nth) {
-            const int4 r = src[row];
-            if (dst) dst[row] = r;
-            if (idx) idx[row] = int4{pick(r, p0), pick(r, p1), pick(r, p2), pick(r, p3)};
-        }
-    } else {
-        for (long long i = tid; i < n * cols; i += nth) {
-            const long long row = i / cols;
-            const int col = (int)(i - row * cols);
-            if (coords_dst) coords_dst[i] = coords[i];
-            if (indices_dst) indices_dst[i] = coords[row * cols + perm.v[col]];
-        }
-    }
+    if (ev_off && blockIdx.x < WFS_EVENT_FLAG_WORDS)
+        wfs_event_table_block(coords, n, cols, ev_col, ev_B, ev_off, WFS_EVENT_FLAG_WORDS);
+    load_coords(coords, n, cols, perm, coords_dst, indices_dst, tid, nth);
     for (long long i = tid; i < feat_words; i += nth) feats_dst[i] = feats[i];
     for (long long i = tid; i < tail_bytes; i += nth) feats_tail_dst[i] = feats_tail[i];
     for (long long i = tid; i < B; i += nth) labels_dst[i] = labels[i];
+}
+
+// Hand-over of a PER-ROW batch (one target row per coordinate row: LitZ, LitEZ, LitSegClassifier, LitSegQuantifier,
+// LitWaveform) in one launch.  What differs from k_load_batch: the features are n rows of a [n_cap, row] buffer and
+// their source may be a slice of a packed loader buffer (16-byte aligned only at its start: 16-byte lanes when both
+// ends are aligned, bytes otherwise); the targets are one row per coordinate row, and every target row in [n, n_cap)
+// is filled with the pad element (the criterion's ignore_index, or its float image), so that the padding rows of the
+// captured step neither count nor receive a gradient.  E is the target element: unsigned (4 bytes) or unsigned long
+// long (8 bytes).
+template <typename E>
+__global__ void __launch_bounds__(256) k_load_rows_batch(const int *__restrict__ coords, long long n, int cols, Perm perm,
+                                                         int *__restrict__ coords_dst, int *__restrict__ indices_dst,
+                                                         const unsigned char *__restrict__ feats,
+                                                         unsigned char *__restrict__ feats_dst, long long feat_words,
+                                                         long long feat_bytes, const E *__restrict__ targets,
+                                                         E *__restrict__ targets_dst, long long t_valid, long long t_cap,
+                                                         E pad, long long *__restrict__ n_valid_dst,
+                                                         int *__restrict__ ev_off, int ev_B, int ev_col, int copy_blocks,
+                                                         WfsFilterImageJobs images) {
+    if ((int)blockIdx.x >= copy_blocks) {
+        const int b = (int)blockIdx.x - copy_blocks;
+        for (int i = 0; i < images.n; ++i)
+            if (b >= images.first_block[i] && b < images.first_block[i + 1])
+                wfs_filter_images_block(images.j[i], b - images.first_block[i]);
+        return;
+    }
+    const long long tid = (long long)blockIdx.x * 256 + threadIdx.x, nth = (long long)copy_blocks * 256;
+    if (tid == 0 && n_valid_dst) *n_valid_dst = n;
+    if (ev_off && blockIdx.x < WFS_EVENT_FLAG_WORDS)
+        wfs_event_table_block(coords, n, cols, ev_col, ev_B, ev_off, WFS_EVENT_FLAG_WORDS);
+    load_coords(coords, n, cols, perm, coords_dst, indices_dst, tid, nth);
+    // features: feat_words 16-byte lanes (0 when an end is misaligned), then the bytes that are left
+    const uint4 *f4 = reinterpret_cast<const uint4 *>(feats);
+    uint4 *d4 = reinterpret_cast<uint4 *>(feats_dst);
+    for (long long i = tid; i < feat_words; i += nth) d4[i] = f4[i];
+    for (long long i = feat_words * 16 + tid; i < feat_bytes; i += nth) feats_dst[i] = feats[i];
+    // targets: the valid rows' elements, then the pad to the capacity
+    for (long long i = tid; i < t_cap; i += nth) targets_dst[i] = i < t_valid ? targets[i] : pad;
 }
 
 __global__ void __launch_bounds__(256) k_filter_images(wfs_filter_image_job job) {
@@ -275,6 +307,20 @@ int filter_image_job_ok(const wfs_filter_image_job &j) {
     // (the filter may sit anywhere in a flat parameter buffer: 4-byte alignment, as the conv kernels read it)
     WFS_REQUIRE(j.W && ((uintptr_t)j.W & 3) == 0, WFS_EINVAL, "NULL or misaligned filter");
     WFS_REQUIRE((((uintptr_t)j.img_fwd | (uintptr_t)j.img_t) & 15) == 0, WFS_EINVAL, "images must be 16-byte aligned");
+    return WFS_OK;
+}
+
+// the jobs of a hand-over launch, checked, with the extra blocks each of them owns
+int filter_image_jobs(const wfs_filter_image_job *jobs, int njobs, WfsFilterImageJobs &images) {
+    WFS_REQUIRE(njobs >= 0 && njobs <= WFS_FILTER_IMAGE_JOBS_MAX && (njobs == 0 || jobs), WFS_EINVAL,
+                "%d filter image jobs (0 .. %d)", njobs, WFS_FILTER_IMAGE_JOBS_MAX);
+    for (int i = 0; i < njobs; ++i) {
+        const int rc = filter_image_job_ok(jobs[i]);
+        if (rc != WFS_OK) return rc;
+        images.j[i] = jobs[i];
+        images.first_block[i + 1] = images.first_block[i] + jobs[i].K;
+    }
+    images.n = njobs;
     return WFS_OK;
 }
 
@@ -307,16 +353,9 @@ extern "C" int wfs_load_batch_images(const int32_t *coords, int64_t n, int32_t c
                                      int64_t *n_valid_dst, int32_t *event_offsets, int32_t events,
                                      const wfs_filter_image_job *jobs, int32_t njobs, void *stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    WFS_REQUIRE(njobs >= 0 && njobs <= WFS_FILTER_IMAGE_JOBS_MAX && (njobs == 0 || jobs), WFS_EINVAL,
-                "%d filter image jobs (0 .. %d)", njobs, WFS_FILTER_IMAGE_JOBS_MAX);
     WfsFilterImageJobs images = {};
-    for (int i = 0; i < njobs; ++i) {
-        const int rc = filter_image_job_ok(jobs[i]);
-        if (rc != WFS_OK) return rc;
-        images.j[i] = jobs[i];
-        images.first_block[i + 1] = images.first_block[i] + jobs[i].K;
-    }
-    images.n = njobs;
+    const int jrc = filter_image_jobs(jobs, njobs, images);
+    if (jrc != WFS_OK) return jrc;
     WFS_REQUIRE(cols >= 1 && cols <= 8, WFS_EINVAL, "bad coordinate width %d", cols);
     WFS_REQUIRE(n >= 0 && B >= 0 && feat_bytes >= 0, WFS_EINVAL, "negative size");
     WFS_REQUIRE((n == 0 || coords) && (feat_bytes == 0 || (feats && feats_dst)) && (B == 0 || (labels && labels_dst)),
@@ -339,6 +378,66 @@ extern "C" int wfs_load_batch_images(const int32_t *coords, int64_t n, int32_t c
         coords, n, cols, pm, coords_dst, indices_dst, (const uint4 *)feats, (uint4 *)feats_dst, words,
         (const unsigned char *)feats + words * 16, (unsigned char *)feats_dst + words * 16, tail, (const long long *)labels,
         (long long *)labels_dst, B, (long long *)n_valid_dst, event_offsets, events, pm.v[0], (int)blocks, images);
+    WFS_LAUNCH_CHECK();
+    return WFS_OK;
+}
+
+extern "C" int wfs_load_rows_batch(const int32_t *coords, int64_t n, int64_t n_cap, int32_t cols, const int32_t *perm_host,
+                                   int32_t *coords_dst, int32_t *indices_dst, const void *feats, void *feats_dst,
+                                   int64_t row_bytes, const void *targets, void *targets_dst, int64_t target_row_bytes,
+                                   int32_t elem, const void *pad_host, int64_t *n_valid_dst, int32_t *event_offsets,
+                                   int32_t events, const wfs_filter_image_job *jobs, int32_t njobs, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    WfsFilterImageJobs images = {};
+    const int jrc = filter_image_jobs(jobs, njobs, images);
+    if (jrc != WFS_OK) return jrc;
+    WFS_REQUIRE(cols >= 1 && cols <= 8, WFS_EINVAL, "bad coordinate width %d", cols);
+    WFS_REQUIRE(n >= 0 && n_cap >= 0 && row_bytes >= 0 && target_row_bytes >= 0, WFS_EINVAL, "negative size");
+    WFS_REQUIRE(n <= n_cap, WFS_EINVAL, "%lld rows, the buffers hold %lld", (long long)n, (long long)n_cap);
+    WFS_REQUIRE(n_cap < (1ll << 31) && row_bytes < (1ll << 31) && target_row_bytes < (1ll << 31), WFS_EINVAL,
+                "rows or row sizes beyond 2^31");
+    WFS_REQUIRE(elem == 4 || elem == 8, WFS_EINVAL, "target elements of %d bytes (4 or 8)", elem);
+    WFS_REQUIRE(target_row_bytes % elem == 0, WFS_EINVAL, "target rows of %lld bytes are no multiple of the %d-byte element",
+                (long long)target_row_bytes, elem);
+    WFS_REQUIRE(n == 0 || coords, WFS_EINVAL, "NULL coordinates");
+    WFS_REQUIRE(n * row_bytes == 0 || (feats && feats_dst), WFS_EINVAL, "NULL feature pointer with %lld bytes to copy",
+                (long long)(n * row_bytes));
+    WFS_REQUIRE(n_cap * target_row_bytes == 0 || (targets_dst && pad_host), WFS_EINVAL,
+                "NULL target destination or pad with %lld bytes to write", (long long)(n_cap * target_row_bytes));
+    WFS_REQUIRE(n * target_row_bytes == 0 || targets, WFS_EINVAL, "NULL targets");
+    WFS_REQUIRE((((uintptr_t)targets | (uintptr_t)targets_dst) & (uintptr_t)(elem - 1)) == 0, WFS_EINVAL,
+                "targets are not aligned to their %d-byte element", elem);
+    WFS_REQUIRE((((uintptr_t)coords | (uintptr_t)coords_dst | (uintptr_t)indices_dst) & 3) == 0, WFS_EINVAL,
+                "coordinates are not 4-byte aligned");
+    Perm pm;
+    for (int c = 0; c < 8; ++c) {
+        pm.v[c] = (perm_host && c < cols) ? perm_host[c] : c;
+        WFS_REQUIRE(pm.v[c] >= 0 && pm.v[c] < (c < cols ? cols : 8), WFS_EINVAL, "bad column permutation");
+    }
+    WFS_REQUIRE(!event_offsets || events >= 1, WFS_EINVAL, "event offsets of %d events", events);
+    const long long feat_bytes = n * row_bytes;
+    const bool aligned = ((uintptr_t)feats % 16 == 0) && ((uintptr_t)feats_dst % 16 == 0);
+    const long long words = aligned ? feat_bytes / 16 : 0;
+    const long long t_valid = n * target_row_bytes / elem, t_cap = n_cap * target_row_bytes / elem;
+    long long work = n * cols > words ? n * cols : words;
+    if (feat_bytes - words * 16 > work) work = feat_bytes - words * 16;
+    if (t_cap > work) work = t_cap;
+    long long blocks = wfs_cdiv(work > 0 ? work : 1, 256);
+    if (blocks > 1024) blocks = 1024;
+    if (event_offsets && blocks < WFS_EVENT_FLAG_WORDS) blocks = WFS_EVENT_FLAG_WORDS;
+    const dim3 grid((unsigned)(blocks + images.first_block[njobs]));
+    unsigned long long pad = 0;
+    if (pad_host) memcpy(&pad, pad_host, 8);
+    if (elem == 8)
+        k_load_rows_batch<unsigned long long><<<grid, dim3(256), 0, stream>>>(
+            coords, n, cols, pm, coords_dst, indices_dst, (const unsigned char *)feats, (unsigned char *)feats_dst, words,
+            feat_bytes, (const unsigned long long *)targets, (unsigned long long *)targets_dst, t_valid, t_cap, pad,
+            (long long *)n_valid_dst, event_offsets, events, pm.v[0], (int)blocks, images);
+    else
+        k_load_rows_batch<unsigned><<<grid, dim3(256), 0, stream>>>(
+            coords, n, cols, pm, coords_dst, indices_dst, (const unsigned char *)feats, (unsigned char *)feats_dst, words,
+            feat_bytes, (const unsigned *)targets, (unsigned *)targets_dst, t_valid, t_cap, (unsigned)pad,
+            (long long *)n_valid_dst, event_offsets, events, pm.v[0], (int)blocks, images);
     WFS_LAUNCH_CHECK();
     return WFS_OK;
 }

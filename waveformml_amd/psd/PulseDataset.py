@@ -31,6 +31,15 @@ class _ConfigMixin(object):
                       label_file_pattern=label_file_pattern, data_cache_size=data_cache_size, normalize=normalize,
                       use_half=use_half, label_map=label_map)
 
+    def _init_rows(self, base, config, dataset_type, n_per_dir, device, *binding, **kw):
+        """The per-segment classes: ``base`` is a h5data.PulseDatasetRows, ``binding`` its positional arguments after
+        ``device`` (none for the bases that fix their own table), ``kw`` whatever the class hands on."""
+        self.config = config.dataset_config
+        self.dataset_type = dataset_type
+        self.n_paths = self.n_categories = len(self.config.paths)
+        self.use_half = kw.get("use_half", False)
+        base.__init__(self, _dirs(config), n_per_dir, device, *binding, **kw)
+
     def get_file_list(self):
         """Files this dataset draws from -- what the data module passes to the next split as ``file_excludes``
         (reference src/datasets/HDF5Dataset.py get_file_list, used at PSDDataModule.py:58,91-93,110-113)."""
@@ -89,3 +98,128 @@ class PulseDataset3D(_ConfigMixin, h5data.PulseDataset3D):
                  use_half=False):
         self._init_from_config(h5data.PulseDataset3D, config, dataset_type, n_per_dir, device, file_excludes, label_name,
                                label_file_pattern, data_cache_size, use_half)
+
+
+# ---- the per-segment classes (reference src/datasets/PulseDataset.py:628-676, :722-1125, :1181-1232): constructor
+# signatures and defaults are the reference's; model_dir / data_dir / dataset_dir are accepted and unused, as above
+
+class PulseDatasetPMT(_ConfigMixin, h5data.PulseDatasetPMT):
+    """[N, 8] rows of ``*PMTCoordSim.h5``, each column scaled by its own factor (reference :628-676)."""
+
+    def __init__(self, config, dataset_type, n_per_dir, device, file_excludes=None, label_name=None,
+                 label_file_pattern=None, data_cache_size=3, model_dir=None, data_dir=None, dataset_dir=None,
+                 use_half=False):
+        self._init_rows(h5data.PulseDatasetPMT, config, dataset_type, n_per_dir, device, file_excludes=file_excludes,
+                        label_name=label_name, label_file_pattern=label_file_pattern, data_cache_size=data_cache_size,
+                        use_half=use_half)
+
+
+class PulseDataset2DWithZ(_ConfigMixin, h5data.PulseDatasetRows):
+    """``WaveformPairsWithZ`` rows of ``*WaveformPairZSim.h5`` with the true z per row (reference :722-761)."""
+
+    def __init__(self, config, dataset_type, n_per_dir, device, file_excludes=None, label_name="z",
+                 label_file_pattern=None, data_cache_size=3, model_dir=None, data_dir=None, dataset_dir=None,
+                 use_half=False):
+        self._init_rows(h5data.PulseDatasetRows, config, dataset_type, n_per_dir, device, "*WaveformPairZSim.h5",
+                        "WaveformPairsWithZ", "coord", "waveform", file_excludes=file_excludes, label_name=label_name,
+                        label_file_pattern=label_file_pattern, data_cache_size=data_cache_size, normalize=True,
+                        use_half=use_half)
+
+
+class PulseDataset2DWithEZ(_ConfigMixin, h5data.PulseDatasetRows):
+    """``WaveformPairsWithEZ`` rows of ``*WaveformPairEZSim.h5``, label (E, z) per row (reference :764-807)."""
+
+    def __init__(self, config, dataset_type, n_per_dir, device, file_excludes=None, label_file_pattern=None,
+                 data_cache_size=3, model_dir=None, data_dir=None, dataset_dir=None, use_half=False, label_index=None):
+        self._init_rows(h5data.PulseDatasetRows, config, dataset_type, n_per_dir, device, "*WaveformPairEZSim.h5",
+                        "WaveformPairsWithEZ", "coord", "waveform", file_excludes=file_excludes, label_name="EZ",
+                        label_file_pattern=label_file_pattern, data_cache_size=data_cache_size, normalize=True,
+                        use_half=use_half, label_index=label_index)
+
+
+class PulseDatasetDetWithZ(_ConfigMixin, h5data.PulseDatasetRows):
+    """``DetPulseCoordWithZ`` rows of ``*DetCoordZSim.h5``: extracted quantities, true z per row (reference :810-853)."""
+
+    def __init__(self, config, dataset_type, n_per_dir, device, file_excludes=None, label_name="z",
+                 label_file_pattern=None, data_cache_size=3, model_dir=None, data_dir=None, dataset_dir=None,
+                 use_half=False, additional_fields=None):
+        self._init_rows(h5data.PulseDatasetRows, config, dataset_type, n_per_dir, device, "*DetCoordZSim.h5",
+                        "DetPulseCoordWithZ", "coord", "pulse", file_excludes=file_excludes, label_name=label_name,
+                        label_file_pattern=label_file_pattern, data_cache_size=data_cache_size, normalize=False,
+                        use_half=use_half, additional_fields=additional_fields)
+
+
+class PulseDatasetDetWithEZ(_ConfigMixin, h5data.PulseDatasetRows):
+    """``DetPulseCoordWithEZ`` rows of ``*DetCoordEZSim.h5``, label (E, z) per row (reference :856-903)."""
+
+    def __init__(self, config, dataset_type, n_per_dir, device, file_excludes=None, label_file_pattern=None,
+                 data_cache_size=3, model_dir=None, data_dir=None, dataset_dir=None, use_half=False, label_index=None,
+                 additional_fields=None):
+        self._init_rows(h5data.PulseDatasetRows, config, dataset_type, n_per_dir, device, "*DetCoordEZSim.h5",
+                        "DetPulseCoordWithEZ", "coord", "pulse", file_excludes=file_excludes, label_name="EZ",
+                        label_file_pattern=label_file_pattern, data_cache_size=data_cache_size, normalize=False,
+                        use_half=use_half, label_index=label_index, additional_fields=additional_fields)
+
+
+class PulseDatasetWFPair(_ConfigMixin, h5data.PulseDatasetRows):
+    """``WaveformPairCal`` rows of ``*WFPairSim.h5``, labelled by directory unless a member is named (reference
+    :906-953)."""
+
+    def __init__(self, config, dataset_type, n_per_dir, device, file_excludes=None, label_file_pattern=None,
+                 data_cache_size=3, model_dir=None, data_dir=None, dataset_dir=None, use_half=False, label_index=None,
+                 label_name=None, additional_fields=None):
+        self._init_rows(h5data.PulseDatasetRows, config, dataset_type, n_per_dir, device, "*WFPairSim.h5",
+                        "WaveformPairCal", "coord", "waveform", file_excludes=file_excludes, label_name=label_name,
+                        label_file_pattern=label_file_pattern, data_cache_size=data_cache_size, normalize=True,
+                        use_half=use_half, label_index=label_index, additional_fields=additional_fields)
+
+
+class PulseDatasetWFPairEZ(PulseDatasetWFPair):
+    """As ``PulseDatasetWFPair`` with the label (E, z) per row by default (reference :956-1003)."""
+
+    def __init__(self, config, dataset_type, n_per_dir, device, file_excludes=None, label_file_pattern=None,
+                 data_cache_size=3, model_dir=None, data_dir=None, dataset_dir=None, use_half=False, label_index=None,
+                 label_name="EZ", additional_fields=None):
+        super().__init__(config, dataset_type, n_per_dir, device, file_excludes=file_excludes,
+                         label_file_pattern=label_file_pattern, data_cache_size=data_cache_size, use_half=use_half,
+                         label_index=label_index, label_name=label_name, additional_fields=additional_fields)
+
+
+class PulseDatasetRealWFPair(_ConfigMixin, h5data.PulseDatasetRealWFPair):
+    """``WaveformPairCal`` rows of real-data files; z and E labels scaled to the nets' range (reference :1006-1062)."""
+
+    def __init__(self, config, dataset_type, n_per_dir, device, file_pattern="*WFCalFilteredSE.h5", file_excludes=None,
+                 label_file_pattern=None, data_cache_size=3, model_dir=None, data_dir=None, dataset_dir=None,
+                 use_half=False, label_name="z", additional_fields=None, label_map=None):
+        self._init_rows(h5data.PulseDatasetRealWFPair, config, dataset_type, n_per_dir, device,
+                        file_pattern=file_pattern, file_excludes=file_excludes, label_name=label_name,
+                        label_file_pattern=label_file_pattern, data_cache_size=data_cache_size, use_half=use_half,
+                        additional_fields=additional_fields, label_map=label_map)
+
+
+class PulseDatasetWFPairNorm(_ConfigMixin, h5data.PulseDatasetWFPairNorm):
+    """``WaveformPairNorm`` rows of ``*WFNorm.h5``: what the per-segment modules (LitZ, LitEZ, LitSegClassifier,
+    LitSegQuantifier) train and test on (reference :1064-1125)."""
+
+    def __init__(self, config, dataset_type, n_per_dir, device, data_name="pulse", file_excludes=None,
+                 label_file_pattern=None, data_cache_size=3, model_dir=None, data_dir=None, dataset_dir=None,
+                 use_half=False, label_index=None, label_name="EZ", additional_fields=None, label_map=None,
+                 waveform_subset=None):
+        self._init_rows(h5data.PulseDatasetWFPairNorm, config, dataset_type, n_per_dir, device, data_name=data_name,
+                        waveform_subset=waveform_subset, file_excludes=file_excludes, label_name=label_name,
+                        label_file_pattern=label_file_pattern, data_cache_size=data_cache_size, use_half=use_half,
+                        label_index=label_index, additional_fields=additional_fields, label_map=label_map)
+
+
+class PulseDatasetNormFeatures(_ConfigMixin, h5data.PulseDatasetRows):
+    """``NormFeatures`` rows of ``*WFFeatures.h5``: extracted waveform features, stored normalised, an item's range
+    counts ROWS (reference :1181-1232)."""
+
+    def __init__(self, config, dataset_type, n_per_dir, device, data_name="features", file_excludes=None,
+                 label_file_pattern=None, data_cache_size=3, model_dir=None, data_dir=None, dataset_dir=None,
+                 use_half=False, label_index=None, label_name="EZ", additional_fields=None, label_map=None):
+        self._init_rows(h5data.PulseDatasetRows, config, dataset_type, n_per_dir, device, "*WFFeatures.h5",
+                        "NormFeatures", "coord", data_name, file_excludes=file_excludes, label_name=label_name,
+                        label_file_pattern=label_file_pattern, data_cache_size=data_cache_size, normalize=False,
+                        event_based=False, use_half=use_half, label_index=label_index,
+                        additional_fields=additional_fields, label_map=label_map)

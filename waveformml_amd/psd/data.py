@@ -319,15 +319,21 @@ class DevicePrefetcher(object):
         if notify and self.on_stage is not None:
             self.on_stage(int(c.shape[0]), int(y.shape[0]))
         ring = isinstance(batch, RingBatch)            # views of a page-locked ring slot: copy straight from it
-        host = [t if (ring or t.is_pinned()) else t.pin_memory() for t in (c, f, y)]
+        # [feats, *additional_fields] (HDF5Dataset's ``additional_fields``): every tensor staged alike under the one
+        # event; the batch is yielded in the same list form
+        n_feats = len(f) if isinstance(f, (list, tuple)) else None
+        flat = [c] + (list(f) if n_feats is not None else [f]) + [y]
+        host = [t if (ring or t.is_pinned()) else t.pin_memory() for t in flat]
         with torch.cuda.stream(self.copy_stream):
             dev = [t.to(self.device, non_blocking=True) for t in host]
             if self.feature_dtype is not None:
-                dev[1] = dev[1].to(self.feature_dtype)
+                dev[1] = dev[1].to(self.feature_dtype)       # the features; fields keep their dtype, as in to_device
             done = torch.cuda.Event()
             done.record(self.copy_stream)
         if ring and batch.token is not None:
             batch.token.guards.append(done)            # reclaim-by-age waits for this copy (see _SlotToken.force)
+        if n_feats is not None:
+            dev = [dev[0], dev[1:-1], dev[-1]]
         # (host buffers kept alive until the copy has been waited on, device tensors, copy event, rows, labels)
         return (batch if ring else host), dev, done, int(c.shape[0]), int(y.shape[0])
 
@@ -367,6 +373,6 @@ class DevicePrefetcher(object):
             if isinstance(host, RingBatch):
                 done.synchronize()        # issued a batch ago: long finished; the slot may now be overwritten
                 host.release()
-            for t in dev:
+            for t in [dev[0], dev[2]] + (dev[1] if isinstance(dev[1], list) else [dev[1]]):
                 t.record_stream(cur)      # allocated on the copy stream, consumed on the compute stream
             yield [dev[0], dev[1]], dev[2]

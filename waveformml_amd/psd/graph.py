@@ -12,8 +12,10 @@ shapes and is captured once into a HIP graph (torch.cuda.CUDAGraph) and replayed
     step.check()                  # occasionally: raises if a capacity was exceeded (results invalid)
 """
 import contextlib
+import ctypes
 import gc
 import os
+import struct
 import sys
 
 import torch
@@ -39,6 +41,32 @@ def _no_gc():
     finally:
         if was:
             gc.enable()
+
+
+# WFS_ROW_HANDOVER: the hand-over of a per-row batch into a captured step -- 1 (default): one launch
+# (wfs_load_rows_batch), 0: the torch copies, fills and gather it replaces.  A/B switch of tools/bench_segment_train.py.
+ROW_HANDOVER = os.environ.get("WFS_ROW_HANDOVER", "1") != "0"
+
+_PAD_FORMATS = {torch.int64: "<q", torch.int32: "<i", torch.float32: "<f", torch.float64: "<d"}
+
+
+def _pad_element(dtype, value):
+    """The 8 host bytes wfs_load_rows_batch reads its pad element from: ``value`` as ``tensor.fill_(value)`` stores it in
+    a tensor of ``dtype``; None for a dtype the one-launch hand-over does not take."""
+    fmt = _PAD_FORMATS.get(dtype)
+    if fmt is None:
+        return None
+    raw = struct.pack(fmt, float(value) if dtype.is_floating_point else int(value))
+    return (ctypes.c_ubyte * 8)(*(raw + b"\0" * (8 - len(raw))))
+
+
+def features_only(batch):
+    """A batch whose features are the ``[feats, *additional_fields]`` list of a dataset with ``additional_fields`` ->
+    the same batch with the features alone: what a training step reads (no ``training_step`` reads the fields)."""
+    (coords, feats), labels = batch
+    if isinstance(feats, (list, tuple)):
+        return [coords, feats[0]], labels
+    return batch
 
 
 def _round_up(v, m):
@@ -100,6 +128,7 @@ class _CapturedRunner(object):
         if per_row:
             self.labels = torch.full((self.n_cap,) + tuple(labels.shape[1:]), self.ignore_index, dtype=labels.dtype,
                                      device=dev)
+            self._pad = _pad_element(labels.dtype, self.ignore_index)
         else:
             self.labels = torch.zeros_like(labels)
         self.n_valid = torch.zeros((1,), dtype=torch.int64, device=dev)
@@ -241,7 +270,7 @@ class _CapturedRunner(object):
         torch.cuda.synchronize(self.coords.device)
 
     def fits(self, batch):
-        (coords, _f), labels = batch
+        (coords, _f), labels = features_only(batch)
         if self.per_row:
             return coords.shape[0] <= self.n_cap and labels.shape[0] == coords.shape[0]
         return coords.shape[0] <= self.n_cap and tuple(labels.shape) == tuple(self.labels.shape)
@@ -249,11 +278,30 @@ class _CapturedRunner(object):
     def _load(self, batch):
         if torch.cuda.current_stream(self.coords.device) == torch.cuda.default_stream(self.coords.device):
             torch.cuda.set_stream(self.stream)         # see "Stream discipline" (_own_stream)
-        (coords, feats), labels = batch
+        (coords, feats), labels = features_only(batch)
         n = coords.shape[0]
         if n > self.n_cap:
             raise RuntimeError("batch has %d voxels, the captured step holds %d" % (n, self.n_cap))
         if self.per_row:
+            if (ROW_HANDOVER and self._pad is not None and coords.is_cuda and coords.dtype == torch.int32
+                    and coords.is_contiguous() and coords.shape[1] == self.coords.shape[1] and feats.is_cuda
+                    and feats.is_contiguous() and feats.dtype == self.feats.dtype
+                    and feats.shape[1:] == self.feats.shape[1:] and labels.is_cuda and labels.is_contiguous()
+                    and labels.dtype == self.labels.dtype and labels.shape[0] == n
+                    and labels.shape[1:] == self.labels.shape[1:]):
+                # one launch: coordinates (as they are and batch-first), feature rows, target rows and their padding, row
+                # count, event offsets, filter images
+                perm = _lib.i32_array(self._perm) if self._perm is not None else None
+                ev = self.events if (self.events is not None and perm is not None) else None
+                _lib.check(_lib.load().wfs_load_rows_batch(
+                    _lib.ptr(coords), n, self.n_cap, coords.shape[1], perm, _lib.ptr(self.coords), _lib.ptr(self.indices),
+                    _lib.ptr(feats), _lib.ptr(self.feats), self.feats.shape[1] * feats.element_size(), _lib.ptr(labels),
+                    _lib.ptr(self.labels), self.labels.numel() // self.n_cap * labels.element_size(),
+                    labels.element_size(), self._pad, _lib.ptr(self.n_valid), _lib.ptr(ev), self.n_events,
+                    self._filter_image_jobs() if self._images else None, len(self._images), _lib.stream_ptr()))
+                if ev is None:
+                    self._event_offsets()
+                return
             self.coords[:n].copy_(coords, non_blocking=True)
             self.feats[:n].copy_(feats, non_blocking=True)
             self.labels.fill_(self.ignore_index)
@@ -302,6 +350,7 @@ class _CapturedRunner(object):
 
 class GraphedTrainStep(_CapturedRunner):
     def __init__(self, module, optimizer, reducer, example_batch, headroom=None, granule=None, warmup=2, min_rows=0):
+        example_batch = features_only(example_batch)      # a [feats, *fields] list: the step trains on the features
         (coords, feats), labels = example_batch
         headroom, granule = self._headroom_granule(int(coords.shape[0]), int(labels.shape[0]), headroom, granule)
         assert labels.is_cuda
@@ -446,6 +495,7 @@ class GraphedTrainStep(_CapturedRunner):
     def eager_step(self, batch):
         """The same step on an exact-size batch without the graph (a batch that does not fit the capture), with the
         SAME sequence of collectives as a replay, so that ranks replaying and ranks stepping eagerly could even mix."""
+        batch = features_only(batch)
         self.reducer.reset()
         net = getattr(self.module, "model", None)
         hint = getattr(net, "batch_size_hint", None)

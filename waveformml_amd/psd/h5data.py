@@ -9,6 +9,9 @@ Host-side mirror of the reference's dataset interface for this row (SURVEY.md 8a
                          named, features scaled by 1/(2^14 - 1) when ``normalize`` (:14-17, :345-346)
   * ``PulseDataset2D`` / ``PulseDataset3D`` / ``PulseDatasetDet``   the table / pattern / batch-column bindings of
                          reference src/datasets/PulseDataset.py:543-625, :679-719
+  * ``PulseDatasetRows`` and ``PulseDatasetPMT`` / ``PulseDatasetRealWFPair`` / ``PulseDatasetWFPairNorm``   the per-segment
+                         bindings of :628-676 and :722-1232 (any table with (x, y, evt) rows, ``label_index``, the PMT
+                         factors, the real-data label scaling, ``waveform_subset``)
 
 What differs from the reference, on purpose:
   * rows are read with hyperslab selections of just the item's range and of just the ``coord`` / ``waveform`` members
@@ -381,3 +384,89 @@ class PulseDataset3D(HDF5Dataset):
     def __init__(self, file_paths, n_per_dir, device=None, **kw):
         super().__init__(file_paths, "*Waveform3DPairSim.h5", "Waveform3DPairs", "coord", "waveform", n_per_dir,
                          device, batch_index=3, **kw)
+
+
+class PulseDatasetRows(HDF5Dataset):
+    """Any compound table with one coordinate row (x, y, evt) per feature row: the binding (file mask, table, coordinate
+    and feature member) is the constructor's, ``label_index`` slices the label columns AFTER ``_convert_label``, as the
+    reference's ``__getitem__`` of every class of src/datasets/PulseDataset.py:722-1232 does."""
+    layout = "2d"
+
+    def __init__(self, file_paths, n_per_dir, device, file_pattern, data_name, coordinate_name, feature_name,
+                 label_index=None, **kw):
+        super().__init__(file_paths, file_pattern, data_name, coordinate_name, feature_name, n_per_dir, device,
+                         batch_index=2, **kw)
+        self.label_index = label_index
+
+    def __getitem__(self, idx):
+        val, label = super().__getitem__(idx)
+        if self.label_index is not None:
+            return val, label[:, self.label_index]
+        return val, label
+
+
+class PulseDatasetPMT(PulseDatasetRows):
+    """``DetPulseCoord`` tables of ``*PMTCoordSim.h5`` files: pulse [8] = two PMTs x four quantities, each column scaled
+    by its own factor (reference src/datasets/PulseDataset.py:628-676)."""
+
+    def __init__(self, file_paths, n_per_dir, device=None, **kw):
+        m = float(2 ** N_CHANNELS - 1)
+        self.normalization_factors = torch.tensor([1. / m, 1. / (m * 10), 0.001, 1.0, 1. / m, 1. / (m * 10), 0.001, 1.0],
+                                                  dtype=torch.float32)
+        kw["normalize"] = False
+        super().__init__(file_paths, n_per_dir, device, "*PMTCoordSim.h5", "DetPulseCoord", "coord", "pulse", **kw)
+
+    def __getitem__(self, idx):
+        (c, f), y = super().__getitem__(idx)
+        return [c, f * self.normalization_factors], y
+
+
+Z_NORMALIZATION_FACTOR, E_NORMALIZATION_FACTOR = 1200., 12.
+
+
+class PulseDatasetRealWFPair(PulseDatasetRows):
+    """``WaveformPairCal`` tables of real-data files (``file_pattern``, default ``*WFCalFilteredSE.h5``): the label ``z``
+    [mm] becomes ``z / 1200 + 0.5``, the label ``E`` [MeV] ``E / 12``; any other label is returned untouched (reference
+    src/datasets/PulseDataset.py:1006-1062)."""
+
+    def __init__(self, file_paths, n_per_dir, device=None, file_pattern="*WFCalFilteredSE.h5", label_name="z", **kw):
+        super().__init__(file_paths, n_per_dir, device, file_pattern, "WaveformPairCal", "coord", "waveform",
+                         label_name=label_name, normalize=True, **kw)
+        self.norm_factor = {"z": 1. / Z_NORMALIZATION_FACTOR, "E": 1. / E_NORMALIZATION_FACTOR}.get(label_name)
+
+    def __getitem__(self, idx):
+        val, label = super().__getitem__(idx)
+        if self.info["label_name"] == "z":
+            return val, label * self.norm_factor + 0.5
+        if self.info["label_name"] == "E":
+            return val, label * self.norm_factor
+        return val, label
+
+
+class PulseDatasetWFPairNorm(PulseDatasetRows):
+    """``WaveformPairNorm`` tables of ``*WFNorm.h5`` files, stored normalised.  ``waveform_subset = [lo, hi]`` keeps
+    samples lo .. hi INCLUSIVE of both halves (left and right PMT) of every row (reference
+    src/datasets/PulseDataset.py:1064-1125; with ``additional_fields`` the reference indexes the [feats, *fields] list
+    itself, which raises: here the subset is taken of the features)."""
+
+    def __init__(self, file_paths, n_per_dir, device=None, data_name="pulse", waveform_subset=None, **kw):
+        super().__init__(file_paths, n_per_dir, device, "*WFNorm.h5", "WaveformPairNorm", "coord", data_name,
+                         normalize=False, **kw)
+        self.waveform_subset = waveform_subset
+        self.waveform_inds = None
+
+    def __getitem__(self, idx):
+        val, label = super().__getitem__(idx)
+        if self.waveform_subset is not None:
+            feats = val[1][0] if isinstance(val[1], list) else val[1]
+            if self.waveform_inds is None:
+                n = feats.shape[1] // 2
+                lo, hi = self.waveform_subset
+                keep = torch.tensor([lo <= i <= hi for i in range(n)], dtype=torch.bool)
+                self.waveform_inds = torch.cat([keep, keep])
+            feats = feats[:, self.waveform_inds]
+            if isinstance(val[1], list):
+                val[1][0] = feats
+            else:
+                val[1] = feats
+        return val, label

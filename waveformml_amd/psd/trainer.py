@@ -222,6 +222,8 @@ class Trainer(object):
     def _captured_step(self, module, reducer, optimizer, batch, batch_idx, agreed=None):
         # several ranks deciding from agreed counts must hold the SAME capacity: a capture is sized on the largest batch
         # any rank has at that step (each rank's own example batch would give each rank its own capacity)
+        from .graph import features_only
+        batch = features_only(batch)          # additional fields of the dataset are not the training step's
         floor = 0
         if agreed is not None:
             from .graph import GraphedTrainStep
