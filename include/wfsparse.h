@@ -686,6 +686,14 @@ size_t wfs_conv2d_saved_floats(int64_t B, int32_t H, int32_t W, int32_t c0, cons
 size_t wfs_conv2d_bwd_workspace_floats(int64_t B, int32_t H, int32_t W, int32_t c0, const int32_t *channels,
                                        const int32_t *fs, const int32_t *st, const int32_t *pd, const int32_t *dil,
                                        int32_t layers, int32_t dtype);
+/* What wfs_conv2d_fwd / wfs_conv2d_bwd do with every layer of a plan; host only, nothing is launched (the tests use
+ * it to know what a case covers).  out[layers][8] = {M = B H' W', row blocks of the statistics / g-sum / dz passes,
+ * row blocks of the BN + ReLU pass, forward GEMM tiles along M, along N, its K steps, dW slices, positions in the last
+ * slice}.  WFS_EINVAL where wfs_conv2d_ok refuses the shape for an eval call, and for out == NULL.  Additions only:
+ * WFS_ABI_VERSION stays. */
+int wfs_conv2d_arms(int64_t B, int32_t H, int32_t W, int32_t c0, const int32_t *channels, const int32_t *fs,
+                    const int32_t *st, const int32_t *pd, const int32_t *dil, int32_t layers, int32_t dtype,
+                    int32_t *out);
 int wfs_conv2d_fwd(const void *X, int64_t B, int32_t H, int32_t W, int32_t c0, const int32_t *channels, const int32_t *fs,
                    const int32_t *st, const int32_t *pd, const int32_t *dil, int32_t layers, const void *param_ptrs,
                    const float *momentum, const float *eps, const float *dropout_p, const int64_t *seed_dev,

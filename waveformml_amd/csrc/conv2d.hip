@@ -663,6 +663,8 @@ int check_common(int32_t c0, const int32_t *channels, const int32_t *fs, const i
     return WFS_OK;
 }
 
+// row_blocks and its two caps, launch_gemm's tile counts and work_layout's nslice are restated by wfs_conv2d_arms
+// (the tests read from it which arm a case reaches): change them together.
 size_t as_floats(size_t elems, int dtype) { return ((elems * wfs_dtype_bytes(dtype) + 7) / 8) * 2; }     // 8-byte granules
 int row_blocks(long long M, int cap) {
     long long b = (M + 4 * RL - 1) / (4 * RL);
@@ -819,6 +821,38 @@ extern "C" size_t wfs_conv2d_bwd_workspace_floats(int64_t B, int32_t H, int32_t 
     Plan pl;
     if (check_common(c0, channels, fs, st, pd, dil, layers, B, H, W, 0, dtype, &pl) != WFS_OK) return 0;
     return work_layout(pl, B, dtype).total;
+}
+
+// Host only, launches nothing: what the launches below do with every layer of the plan, out[layers][8] =
+//   {M = B H' W', row blocks of the statistics / g-sum / dz passes, row blocks of the BN + ReLU pass,
+//    forward GEMM tiles along M, along N, its K steps, dW slices, positions in the last slice}
+// tests/test_dense_cases_host.py takes from here which arm a case of its table reaches.  Built from the helpers the
+// launches use (row_blocks with NRB_MAX / EW_MAXBLK, launch_gemm's tile counts, the step count of k_c2d_gemm's loop,
+// work_layout's nslice): change it together with them.  Refuses what wfs_conv2d_ok refuses for an eval call (there is
+// no `training` here, as in the two size queries).
+extern "C" int wfs_conv2d_arms(int64_t B, int32_t H, int32_t W, int32_t c0, const int32_t *channels, const int32_t *fs,
+                               const int32_t *st, const int32_t *pd, const int32_t *dil, int32_t layers, int32_t dtype,
+                               int32_t *out) {
+    Plan pl;
+    int rc = check_common(c0, channels, fs, st, pd, dil, layers, B, H, W, 0, dtype, &pl);
+    if (rc != WFS_OK) return rc;
+    WFS_REQUIRE(out, WFS_EINVAL, "NULL output");
+    const WorkLayout wl = work_layout(pl, B, dtype);
+    for (int i = 0; i < layers; ++i) {
+        const Layer &ly = pl.ly[i];
+        const long long M = rows_of(ly, B);
+        const int K = ly.cin * ly.fs * ly.fs;
+        int32_t *o = out + 8 * i;
+        o[0] = (int32_t)M;
+        o[1] = row_blocks(M, NRB_MAX);
+        o[2] = row_blocks(M, EW_MAXBLK);
+        o[3] = (int32_t)((M + TM - 1) / TM);
+        o[4] = (ly.cout + TN - 1) / TN;
+        o[5] = (K + TK - 1) / TK;
+        o[6] = wl.nslice[i];
+        o[7] = (int32_t)(M - (long long)(wl.nslice[i] - 1) * DW_CHUNK);
+    }
+    return WFS_OK;
 }
 
 extern "C" int wfs_conv2d_fwd(const void *X, int64_t B, int32_t H, int32_t W, int32_t c0, const int32_t *channels,
