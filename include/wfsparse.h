@@ -610,7 +610,8 @@ int wfs_tcnc_bwd(const void *X, const void *dY, int64_t N, int32_t L, int32_t c0
  * wfs_conv1d_fwd: layers + 1 launches.  training != 0: batch statistics per channel over n_valid x L[i + 1] elements
  *   (biased variance), and running_mean / running_var (unbiased, momentum[i]) / num_batches_tracked updated on the
  *   device; training == 0: the running statistics.  `saved` [wfs_conv1d_saved_floats] fp32 keeps every layer's pre-BN
- *   convolution output and the statistics used, for the backward.
+ *   convolution output and the statistics used, for the backward.  An empty batch (n_valid <= 0) in a training call
+ *   folds mean 0 and variance 0 into the running statistics and counts a batch; torch raises there.
  * wfs_conv1d_bwd: layers + 2 launches.  dX (dtype; NULL: not wanted) from dY (dtype) and `saved`; d conv.weight,
  *   d conv.bias, d bn.weight, d bn.bias straight into the gradient slots; workspace [wfs_conv1d_bwd_workspace_floats]
  *   fp32.  `training` as in the forward call.  Deterministic (fixed-order partial sums, no atomics).  N >= 1.  */
@@ -633,6 +634,14 @@ int wfs_conv1d_bwd(const void *X, const void *dY, int64_t N, int32_t L, int32_t 
                    const int32_t *fs, const int32_t *st, const int32_t *pd, int32_t layers, const void *param_ptrs,
                    int32_t training, const float *saved, void *dX, float *workspace, int32_t dtype,
                    const int64_t *n_valid_dev, void *stream);
+/* Host only, launches nothing: the plan the two calls above follow, for the tests.  out[layers][10] = {L_in, L_out,
+ * position blocks of the forward (and head) pass over N L_out, position blocks of the input-gradient role over N L_in
+ * (as launched when that gradient is wanted), its input-channel chunks, dW blocks per column chunk, column chunks of
+ * the cin fs + 1 dW columns, columns of the last chunk, thread groups of the last chunk, accumulator width CO}, then
+ * out[layers * 10] = blocks of the last forward launch.  WFS_EINVAL where wfs_conv1d_ok refuses the plan (and for a row
+ * count the size queries answer 0 to, and out == NULL).  Additions only: WFS_ABI_VERSION stays. */
+int wfs_conv1d_arms(int64_t N, int32_t L, int32_t c0, const int32_t *channels, const int32_t *fs, const int32_t *st,
+                    const int32_t *pd, int32_t layers, int32_t *out);
 
 /* dense Conv2d + BatchNorm2d + ReLU (+ Dropout) stack on event maps (csrc/conv2d.hip) ------------------------
  * The reference's Conv2DBlock (src/models/ConvBlocks.py:220-289) under DenseConvNet: per layer i of `layers`,

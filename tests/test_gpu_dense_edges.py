@@ -31,21 +31,17 @@ $WFS_DENSE_EDGES_REPORT when that is set (the table of DESIGN.md section 4).
 """
 import collections
 import ctypes
-import os
-import time
 
 import pytest
 import torch
 from torch import nn
 
 import dense_cases as dc
+from edge_harness import NAN, SENT, Buf as _Buf, bits_equal as _bits_equal, error_report
 from waveform_cases import DEV, TOL
 
 pytestmark = pytest.mark.gpu
 
-SENT = -768.0                      # exactly representable in bf16 and fp16
-PAD = 5                            # trailing elements behind every buffer
-NAN = float("nan")
 NBT0 = 41
 GROUPS = ("y", "dx", "dw", "db", "dbn", "running")
 WORST = {}                         # (case, kind, mode) -> {group: worst error / bar}
@@ -56,39 +52,7 @@ def _L():
     return _lib
 
 
-@pytest.fixture(scope="module", autouse=True)
-def _error_report():
-    t0 = time.time()
-    yield
-    lines = ["# worst |got - want| / (bar x scale) per tensor group (<= 1 passes): case, row type, mode, "
-             + ", ".join(GROUPS)]
-    for (name, kind, mode), w in sorted(WORST.items()):
-        lines.append("%-14s %-5s %-5s %s" % (name, kind, mode, " ".join("%.4f" % w[g] if g in w else "-" for g in GROUPS)))
-    text = "\n".join(lines)
-    print("\n" + text + "\n# module wall time %.1f s" % (time.time() - t0))
-    path = os.environ.get("WFS_DENSE_EDGES_REPORT")
-    if path:
-        with open(path, "w") as f:
-            f.write(text + "\n")
-
-
-class _Buf:
-    """`n` elements filled with `fill` and PAD trailing elements filled with `tail`; `.t` is the buffer itself."""
-
-    def __init__(self, shape, dtype, fill, tail=None):
-        n = 1
-        for s in shape:
-            n *= s
-        assert n > 0
-        self.tail = fill if tail is None else tail
-        self.flat = torch.full((n + PAD,), fill, dtype=dtype, device=DEV)
-        self.flat[n:] = self.tail
-        self.t = self.flat[:n].view(shape)
-
-    def check_tail(self, what):
-        tail = self.flat[self.t.numel():].float()
-        kept = torch.isnan(tail) if self.tail != self.tail else tail == self.tail
-        assert bool(kept.all()), "%s: an element behind the buffer was written" % what
+_error_report = error_report(WORST, GROUPS, "WFS_DENSE_EDGES_REPORT")
 
 
 def _group(name):
@@ -195,11 +159,6 @@ def check(i, kind, mode, got, label=None, skip=()):
         old[g] = max(old.get(g, 0.0), w)
     missed = {g: "%.4g" % w for g, w in worst.items() if not w <= 1.0}
     assert not missed, "%s: worst error over its bar: %s" % (label or dc.run_id(i, kind, mode), missed)
-
-
-def _bits_equal(a, b, names):
-    for n in names:
-        assert torch.equal(a[n].contiguous().view(torch.uint8), b[n].contiguous().view(torch.uint8)), n
 
 
 @pytest.mark.parametrize("i,kind,mode", [pytest.param(i, k, m, id=dc.run_id(i, k, m)) for i, k, m in dc.case_params()])

@@ -144,6 +144,7 @@ SIGNATURES = {
     "wfs_conv1d_ok": (ctypes.c_int, [_i32, c_i32p, c_i32p, c_i32p, c_i32p, _i32, _i32, _i32]),
     "wfs_conv1d_saved_floats": (_sz, [_i64, _i32, _i32, c_i32p, c_i32p, c_i32p, c_i32p, _i32]),
     "wfs_conv1d_bwd_workspace_floats": (_sz, [_i64, _i32, _i32, c_i32p, c_i32p, c_i32p, c_i32p, _i32]),
+    "wfs_conv1d_arms": (ctypes.c_int, [_i64, _i32, _i32, c_i32p, c_i32p, c_i32p, c_i32p, _i32, c_i32p]),
     "wfs_conv1d_fwd": (ctypes.c_int, [_vp, _i64, _i32, _i32, c_i32p, c_i32p, c_i32p, c_i32p, _i32, _vp, c_f32p, c_f32p,
                                       _i32, _vp, _vp, _i32, _vp, _vp]),
     "wfs_conv1d_bwd": (ctypes.c_int, [_vp, _vp, _i64, _i32, _i32, c_i32p, c_i32p, c_i32p, c_i32p, _i32, _vp, _i32, _vp,

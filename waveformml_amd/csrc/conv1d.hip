@@ -60,6 +60,17 @@ struct Plan {
     int n;
 };
 
+// The dW role's arithmetic on a chunk of columns, and the accumulator width of a layer.  k_c1d_bwd, its launch and
+// wfs_conv1d_arms (which tells the tests what arm a plan reaches) all take them from here.
+__host__ __device__ inline int dw_mycols(int ncol, int col0) { return ncol - col0 < TB ? ncol - col0 : TB; }
+__host__ __device__ inline int dw_groups(int mycols) { return mycols <= TB / 2 ? TB / mycols : 1; }
+inline int dw_co(int cout) { return cout <= 8 ? 8 : (cout <= 16 ? 16 : (cout <= 32 ? 32 : 64)); }
+inline int in_chunks(int cin) { return (cin + CH - 1) / CH; }
+inline int dw_chunks(int ncol) { return (ncol + TB - 1) / TB; }
+inline int out_blocks(long long total) {
+    const long long b = (total + TB - 1) / TB;
+    return (int)(b > EW_MAXBLK ? EW_MAXBLK : b);
+}
 
 // Sums of the per-block partials [nblk][nv] (nv <= 2 MAXC) into tot[nv], computed by EVERY block in the same order:
 // slice s adds partials s, s + S, ...; the slices are then added in slice order.
@@ -434,8 +445,8 @@ __global__ void __launch_bounds__(TB) k_c1d_bwd(BwdArgs a, const Conv1dPtrs *__r
     // (an input of ones) is db.  This block owns up to TB columns and the tiles b, b + dw_nblk, ...; inside a tile
     // `groups` thread groups take interleaved positions and are added in group order at the end.
     const int bb = (int)blockIdx.x - nA, b = bb % a.dw_nblk, col0 = (bb / a.dw_nblk) * TB;
-    const int ncol = ly.cin * ly.fs + 1, mycols = ncol - col0 < TB ? ncol - col0 : TB;
-    const int groups = mycols <= TB / 2 ? TB / mycols : 1;
+    const int ncol = ly.cin * ly.fs + 1, mycols = dw_mycols(ncol, col0);
+    const int groups = dw_groups(mycols);
     int grp = threadIdx.x / mycols;
     const int col = threadIdx.x - grp * mycols;
     if (grp >= groups) grp = -1;
@@ -590,6 +601,9 @@ int pos_blocks(long long P) {
     return (int)(b < 1 ? 1 : (b > ST_MAXBLK ? ST_MAXBLK : b));
 }
 
+// position blocks of role A of k_c1d_bwd over the layer's input: none when layer 0's input gradient is not wanted
+int role_a_blocks(long long N, const Layer &ly, bool wanted) { return wanted ? pos_blocks(N * ly.lin) : 0; }
+
 size_t even(size_t v) { return (v + 1) & ~(size_t)1; }          // doubles follow floats: keep them 8-byte aligned
 
 // `saved`: z of every layer | [layers][2][MAXC] mean / invstd | the forward's statistics partials (doubles)
@@ -664,6 +678,40 @@ extern "C" size_t wfs_conv1d_bwd_workspace_floats(int64_t N, int32_t L, int32_t 
     return work_layout(pl, N).total;
 }
 
+// Host only, launches nothing: what the launches below do with every layer of the plan, out[layers][10] =
+//   {L_in, L_out, position blocks of the forward / head pass over N L_out, role A's position blocks when its input
+//    gradient is wanted (over N L_in), its input-channel chunks, dW blocks per column chunk, column chunks,
+//    columns of the last chunk, thread groups of the last chunk, CO}
+// and, after the layers, out[layers * 10] = the blocks of k_c1d_out.  tests/test_conv1d_cases_host.py takes from here
+// which arm a case of its table reaches.  Built from what the launches use: make_plan, pos_blocks, work_layout and the
+// helpers under Plan.
+extern "C" int wfs_conv1d_arms(int64_t N, int32_t L, int32_t c0, const int32_t *channels, const int32_t *fs,
+                               const int32_t *st, const int32_t *pd, int32_t layers, int32_t *out) {
+    Plan pl;
+    int rc = check_common(c0, channels, fs, st, pd, layers, N, L, WFS_F32, &pl);
+    if (rc != WFS_OK) return rc;
+    WFS_REQUIRE(out, WFS_EINVAL, "NULL output");
+    const WorkLayout wl = work_layout(pl, N);
+    for (int i = 0; i < layers; ++i) {
+        const Layer &ly = pl.ly[i];
+        const int ncol = ly.cin * ly.fs + 1, chunks = dw_chunks(ncol), mycols = dw_mycols(ncol, (chunks - 1) * TB);
+        int32_t *o = out + 10 * i;
+        o[0] = ly.lin;
+        o[1] = ly.lout;
+        o[2] = pos_blocks(N * ly.lout);
+        o[3] = role_a_blocks(N, ly, true);
+        o[4] = in_chunks(ly.cin);
+        o[5] = wl.dw_nblk[i];
+        o[6] = chunks;
+        o[7] = mycols;
+        o[8] = dw_groups(mycols);
+        o[9] = dw_co(ly.cout);
+    }
+    const Layer &last = pl.ly[layers - 1];
+    out[10 * layers] = out_blocks(N * (long long)last.cout * last.lout);
+    return WFS_OK;
+}
+
 extern "C" int wfs_conv1d_fwd(const void *X, int64_t N, int32_t L, int32_t c0, const int32_t *channels, const int32_t *fs,
                               const int32_t *st, const int32_t *pd, int32_t layers, const void *param_ptrs,
                               const float *momentum, const float *eps, int32_t training, float *saved, void *Y,
@@ -704,9 +752,7 @@ extern "C" int wfs_conv1d_fwd(const void *X, int64_t N, int32_t L, int32_t c0, c
     }
     const Layer &last = pl.ly[layers - 1];
     const long long total = N * (long long)last.cout * last.lout;
-    long long blocks = (total + TB - 1) / TB;
-    blocks = blocks > EW_MAXBLK ? EW_MAXBLK : blocks;
-    k_c1d_out<<<dim3((unsigned)blocks), dim3(TB), 0, stream>>>(
+    k_c1d_out<<<dim3((unsigned)out_blocks(total)), dim3(TB), 0, stream>>>(
         saved + sl.z[layers - 1], last.cout, last.lout, layers - 1, pp, (const double *)(saved + sl.part[layers - 1]),
         pos_blocks(N * last.lout), momentum[layers - 1], eps[layers - 1], saved + sl.stats + (size_t)(layers - 1) * 2 * MAXC,
         Y, dtype, N, n_dev, training);
@@ -753,29 +799,27 @@ extern "C" int wfs_conv1d_bwd(const void *X, const void *dY, int64_t N, int32_t 
         a.Xin = i == 0 ? X : (const void *)(saved + sl.z[i - 1]);
         a.x_dt = i == 0 ? dtype : WFS_F32;
         a.has_prev = i > 0;
-        a.nchunk = (ly.cin + CH - 1) / CH;
+        a.nchunk = in_chunks(ly.cin);
         if (i > 0) {
             a.pstats = saved + sl.stats + (size_t)(i - 1) * 2 * MAXC;
             a.Gout = G[cur ^ 1];
             a.ostat = ST[cur ^ 1];
-            a.nbx = pos_blocks(N * ly.lin);
+            a.nbx = role_a_blocks(N, ly, true);
         } else {
             a.dX = dX;
             a.dx_dt = dtype;
-            a.nbx = dX ? pos_blocks(N * ly.lin) : 0;
+            a.nbx = role_a_blocks(N, ly, dX != nullptr);
         }
         a.part = workspace + wl.part[i];
         a.dw_nblk = wl.dw_nblk[i];
         const int ncol = ly.cin * ly.fs + 1;
-        const unsigned grid = (unsigned)(a.nbx * a.nchunk + a.dw_nblk * ((ncol + TB - 1) / TB));
-        if (ly.cout <= 8)
-            k_c1d_bwd<8><<<dim3(grid), dim3(TB), 0, stream>>>(a, pp, N, n_dev);
-        else if (ly.cout <= 16)
-            k_c1d_bwd<16><<<dim3(grid), dim3(TB), 0, stream>>>(a, pp, N, n_dev);
-        else if (ly.cout <= 32)
-            k_c1d_bwd<32><<<dim3(grid), dim3(TB), 0, stream>>>(a, pp, N, n_dev);
-        else
-            k_c1d_bwd<64><<<dim3(grid), dim3(TB), 0, stream>>>(a, pp, N, n_dev);
+        const unsigned grid = (unsigned)(a.nbx * a.nchunk + a.dw_nblk * dw_chunks(ncol));
+        switch (dw_co(ly.cout)) {
+        case 8: k_c1d_bwd<8><<<dim3(grid), dim3(TB), 0, stream>>>(a, pp, N, n_dev); break;
+        case 16: k_c1d_bwd<16><<<dim3(grid), dim3(TB), 0, stream>>>(a, pp, N, n_dev); break;
+        case 32: k_c1d_bwd<32><<<dim3(grid), dim3(TB), 0, stream>>>(a, pp, N, n_dev); break;
+        default: k_c1d_bwd<64><<<dim3(grid), dim3(TB), 0, stream>>>(a, pp, N, n_dev); break;
+        }
         WFS_LAUNCH_CHECK();
         tab.d[i].cout = ly.cout;
         tab.d[i].ncol = ncol;
